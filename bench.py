@@ -2,15 +2,25 @@
 """Headline benchmark: MLUPS of the D3Q19x2 binary fluctuating-LBM step on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--noise] [--schedule fused|two_pass] [--transport T]
+                  [--full] [--dump-outputs DIR]
 
 A "step" is one LBM_timestep-equivalent (stream + densities + noise + projection + collide,
 LBM_binary.H:545-594) over the whole lattice.  N=1: the headline `value` is the 512^3 periodic box at zero
-noise (stripe init) that BASELINE.json quotes its 60 % target on; configs[1]'s 256^3 is timed in the same run
-and reported, with its own roofline, under config.also.  N>1: weak scaling, every GPU owns a 512x512x512
-z-slab of a 512x512x(512 N) box, +-z planes exchanged and overlapped with the interior planes; at N=4 / N=8 the slab
-shapes of configs[3] (512x512x128, droplet) / configs[4] (1024x1024x64, mixture with kBT > 0, alpha0 = 2.5) are timed in the same
-run under config.also.  --size S / --shape NX,NY,NZ time one explicit case instead.
-Populations are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
+noise (stripe init) that BASELINE.json quotes its 60 % target on.  N>1: weak scaling, every GPU owns a 512x512x512
+z-slab of a 512x512x(512 N) box, +-z planes exchanged and overlapped with the interior planes.  --size S / --shape NX,NY,NZ
+time one explicit case instead.  Populations are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times ONE block of exactly K steps (`ms_per_step` = its wall clock / K) and prints the line.
+--full adds what is measured beside the headline: the K-step block timed --blocks (3) times with the median block reported
+and all of them under `spread`; at N=1 configs[1]'s 256^3 with its own roofline under config.also and the CPU oracle under
+`cpu_baseline`; at N>1 the steps with the exchange after the sweep (config.halo_overlap) and, at N=4 / N=8, the slab shapes of
+configs[3] (512x512x128, droplet) / configs[4] (1024x1024x64, mixture with kBT > 0, alpha0 = 2.5) under config.also.
+
+--dump-outputs DIR: after the timed steps, what the timed lattice holds after its last step -- populations f, g and the 22
+hydrodynamic fields (LBM_hydrovars) on a seeded sample of DUMP_BOXES boxes of up to DUMP_EDGE^3 sites of rank 0's slab
+(dump_boxes(): the same boxes for the same lattice in every run), and the lattice's (rho, phi) sums -- as DIR/f.npy, g.npy,
+hydrovars.npy, mass.npy in float64 (~31 MB at 512^3).  The inputs are fixed by the arguments (analytic initial states, the
+noise seeded by the model parameters), so two builds can be compared output for output.
 
 N > 1, who does what (the reference distributes boxes over MPI ranks, main_run_job.cpp:140-143, and fills ghost cells
 with FillBoundary, LBM_binary.H:553-555):
@@ -54,6 +64,36 @@ TRANSPORT_TEXT = {
     "peer-kernel": "peer, one process drives all GPUs; a gather kernel reads the neighbour's planes in place (xGMI peer memory)",
     "peer-copy": "peer, one process drives all GPUs; copy engine, 38 hipMemcpyPeerAsync per face (no compute units)",
 }
+
+DUMP_BOXES, DUMP_EDGE, DUMP_SEED = 16, 16, 20240531      # --dump-outputs sample: 16 x 16^3 sites = 31 MB of f, g, hydrovars
+
+
+def dump_boxes(nx, ny, z0, z1):
+    """Lower corners (DUMP_BOXES x 3, x y z) and edge (ex, ey, ez) of the --dump-outputs sample: boxes inside
+    0 <= x < nx, 0 <= y < ny, z0 <= z < z1, drawn from a fixed seed, so a lattice is sampled the same way in every run."""
+    import numpy as np
+    ext = (nx, ny, z1 - z0)
+    edge = tuple(min(DUMP_EDGE, e) for e in ext)
+    rng = np.random.default_rng(DUMP_SEED)
+    lo = np.stack([rng.integers(0, e - b + 1, size=DUMP_BOXES) for e, b in zip(ext, edge)], axis=1)
+    lo[:, 2] += z0
+    return lo, edge
+
+
+def dump_outputs(path, pkg, lat, mass):
+    """Write the --dump-outputs sample of `lat` (a BinaryLBM or SlabLattice, rank 0's slab) and `mass` to directory `path`."""
+    import numpy as np
+    lo, (ex, ey, ez) = dump_boxes(lat.n[0], lat.n[1], lat.z0, lat.z1)
+    f = np.empty((len(lo), pkg.NVEL, ez, ey, ex))
+    g = np.empty_like(f)
+    h = np.empty((len(lo), pkg.NHYDRO, ez, ey, ex))
+    for k, c in enumerate(lo):
+        fab = pkg.make_fab(c, c + np.array([ex, ey, ez]) - 1)
+        lat.populations(f[k], g[k], fab)
+        lat.LBM_hydrovars(h[k], fab)
+    os.makedirs(path, exist_ok=True)
+    for name, arr in (("f", f), ("g", g), ("hydrovars", h), ("mass", np.array(mass, dtype=np.float64))):
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def cpu_baseline(noise=False):
@@ -123,18 +163,26 @@ def parse_args():
     ap.add_argument("--init", default=None, choices=["stripe", "droplet", "mixture"],
                     help="initial state; default: stripe at zero noise, mixture with --noise (configs[2] = NoiseCovariance.ipynb's homogeneous mixture)")
     ap.add_argument("--schedule", default=os.environ.get("BFLBM_SCHEDULE", "auto"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--blocks", type=int, default=3, help="the K-step block is timed this many times; value = the median block")
+    ap.add_argument("--full", action="store_true",
+                    help="also time what is reported beside the headline (repeated blocks, config.also, cpu_baseline, halo_overlap)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the timed lattice's state to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help="the K-step block is timed this many times; value = the median block (default: 1, with --full 3)")
     ap.add_argument("--transport", default=os.environ.get("BFLBM_BENCH_TRANSPORT_CHAIN", "auto"),
                     help="N > 1: auto (the chain " + " -> ".join(TRANSPORT_CHAIN) + ", first that completes), one of them, or a comma list")
     ap.add_argument("--attempt-timeout", type=float, default=420.0, help="N > 1: wall-clock limit of one transport attempt, seconds")
-    ap.add_argument("--no-overlap-leg", action="store_true", help="N > 1: skip the informational steps with the exchange after the sweep")
+    ap.add_argument("--no-overlap-leg", action="store_true", help="N > 1, --full: skip the informational steps with the exchange after the sweep")
     ap.add_argument("--second-transport", action="store_true", default=os.environ.get("BFLBM_BENCH_SECOND_TRANSPORT", "0") == "1",
                     help="N > 1, --transport auto: after the first transport completed, time the next transport FAMILY as an informational "
                          "leg (config.second_transport).  Off by default: a transport that has never run on several GPUs should not get "
                          "the chance to disturb the node in the middle of a scaling series once a result exists")
     ap.add_argument("--no-second-transport", action="store_true", help="(kept for older command lines; the leg is off unless --second-transport)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.blocks is None:
+        a.blocks = 3 if a.full else 1
+    return a
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -332,8 +380,9 @@ def work(a):
         n = ctypes_device_count(pkg)
         ring_devices = list(range(min(world, max(n, 1))))
 
-    def run_case(sx, sy, sz, init=None, noise=None, alpha0=None):
-        """Time a.steps steps on a lattice of sx x sy x (sz*world); returns the result fields of this case (rank 0)."""
+    def run_case(sx, sy, sz, init=None, noise=None, alpha0=None, dump=None):
+        """Time a.steps steps on a lattice of sx x sy x (sz*world); returns the result fields of this case (rank 0).
+        dump: directory of --dump-outputs, written from the state the timed steps left."""
         noise = a.noise if noise is None else noise
         # default initial state: the stripe at zero noise; with noise the homogeneous mixture of NoiseCovariance.ipynb (configs[2]).
         # It matters for the time: on a state that the noise has randomised a step takes 2-3 % longer than on the smooth stripe
@@ -394,10 +443,14 @@ def work(a):
         spread = {"blocks_ms_per_step": [round(b[0] / a.steps * 1e3, 4) for b in blocks],
                   "min": round(min(b[0] for b in blocks) / a.steps * 1e3, 4), "max": round(max(b[0] for b in blocks) / a.steps * 1e3, 4),
                   "reported": "median block"}
+        if dump:
+            mass = lat.mass()                          # all ranks: a SlabLattice reduces over them
+            if rank == 0:
+                dump_outputs(dump, pkg, lat.slabs[0] if single_process_ring else lat, mass)
         # N > 1: the same steps with the exchange AFTER the sweep instead of behind it (configs[3]: "overlap
         # efficiency"); outside the timed region, and never allowed to break the headline line
         seq_ms = None
-        if world > 1 and not a.no_overlap_leg:
+        if world > 1 and a.full and not a.no_overlap_leg:
             try:
                 if use_dist:
                     lat.overlap = False
@@ -458,9 +511,9 @@ def work(a):
         }
 
     # Workload.  The 60 % target of BASELINE.json is quoted on a 512^3 step at 1 GPU, so that is the headline
-    # (81.6 GB of populations); configs[1]'s 256^3 is timed in the same run and reported under config.also.
-    # N > 1: weak scaling with the same 512x512x512 slab per GPU, and the slab shapes of configs[3] / configs[4] at the GPU
-    # counts they are quoted on.  --size / --shape select one explicit case.
+    # (81.6 GB of populations); with --full configs[1]'s 256^3 is timed in the same run and reported under config.also.
+    # N > 1: weak scaling with the same 512x512x512 slab per GPU, and with --full the slab shapes of configs[3] / configs[4]
+    # at the GPU counts they are quoted on.  --size / --shape select one explicit case.
     explicit = bool(a.shape) or a.size > 0
     if a.shape:
         head = tuple(int(v) for v in a.shape.split(","))
@@ -471,10 +524,10 @@ def work(a):
 
     def add_also(r):
         also[r["workload"]] = {k: r[k] for k in ("value", "ms_per_step", "spread", "schedule", "roofline", "halo_overlap", "slab_per_gpu", "placement") if r.get(k) is not None}
-    if not explicit and world == 1:
+    if a.full and not explicit and world == 1:
         add_also(run_case(256, 256, 256))
-    res = run_case(*head)
-    if not explicit and world > 1:
+    res = run_case(*head, dump=a.dump_outputs)
+    if a.full and not explicit and world > 1:
         try:                                           # never allowed to cost the headline line
             if world == 4:
                 add_also(run_case(512, 512, 128, init="droplet", noise=False))                # configs[3]: 512^3 droplet on 4 z-slabs
@@ -498,7 +551,7 @@ def work(a):
                        "halo_overlap": res["halo_overlap"], "placement": res["placement"], "also": also or None},
             "roofline": res["roofline"],
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(noise=a.noise)
         sys.stdout.flush()
         os.dup2(real_stdout, 1)

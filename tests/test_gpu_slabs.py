@@ -208,7 +208,7 @@ def _bench(args, env=None, timeout=900):
     """`bench.py --gpus N` as the driver launches it (torch.distributed.run, one supervisor rank per GPU), rehearsed on the
     one GPU of this box: RCCL refuses several ranks per device, so the rccl transports run over gloo (BFLBM_BENCH_BACKEND)
     with the ranks sharing the device, and the peer transports put every slab on device 0.  A rehearsal of the code
-    paths, never a measurement."""
+    paths, never a measurement.  --full: the lines are checked for the repeated blocks and the exchange-after-sweep leg."""
     import json
     import socket
     import subprocess
@@ -218,7 +218,7 @@ def _bench(args, env=None, timeout=900):
     n = args[args.index("--gpus") + 1]
     e = dict(os.environ, BFLBM_BENCH_BACKEND="gloo", **(env or {}))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", n, "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py")] + list(args) + ["--no-cpu-baseline"]
+           "--master-port", str(port), os.path.join(root, "bench.py")] + list(args) + ["--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=e, capture_output=True, text=True, timeout=timeout, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -238,13 +238,20 @@ def _check_line(r, transport_text):
     assert ov and ov["ms_per_step_exchange_after_sweep"] > 0
 
 
-def test_bench_two_slabs_on_one_gpu_default_chain():
+def test_bench_two_slabs_on_one_gpu_default_chain(tmp_path):
     """The N > 1 bench path with the hand-over schedule (what auto runs on the 512^3 slabs of the real bench) as the driver
     starts it: the first transport of the chain (rccl, staged) produces the line -- one JSON line with n_gpus 2, the stripe's
     mass conserved, the halo size and the transport stated, the exchange-after-sweep leg timed -- and the next transport
-    family (the native ring with the copy engine, one process) is timed beside it as an informational leg (--second-transport)."""
-    r, _ = _bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--shape", "128,16,12", "--schedule", "handover", "--second-transport"])
+    family (the native ring with the copy engine, one process) is timed beside it as an informational leg (--second-transport).
+    --dump-outputs: both transports write the sample of rank 0's slab (z < 12) and the lattice's mass."""
+    d = str(tmp_path / "out")
+    r, _ = _bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--shape", "128,16,12", "--schedule", "handover", "--second-transport",
+                   "--dump-outputs", d])
     _check_line(r, "rccl, staged")
+    f, g, h, mass = (np.load(os.path.join(d, k + ".npy")) for k in ("f", "g", "hydrovars", "mass"))
+    assert f.shape == g.shape == (16, 19, 12, 16, 16) and h.shape == (16, 22, 12, 16, 16)
+    assert np.isfinite(f).all() and np.isfinite(g).all() and np.isfinite(h).all()
+    assert abs(mass.sum() - 128 * 16 * 24) < 1e-6
     tried = r["config"]["launcher"]["transports_tried"]
     assert [(t["transport"], t["ok"]) for t in tried] == [("rccl", True), ("peer-copy", True)]
     second = r["config"]["second_transport"]

@@ -4,8 +4,8 @@ n=$1; args="$2"; shift 2
 tmp=$(mktemp)
 for rep in $(seq $n); do
   for v in "$@"; do
-    if [ "$v" = "-" ]; then out=$(timeout -k 10 300 python bench.py --no-cpu-baseline $args 2>&1 | tail -1)
-    else out=$(env $v timeout -k 10 300 python bench.py --no-cpu-baseline $args 2>&1 | tail -1); fi
+    if [ "$v" = "-" ]; then out=$(timeout -k 10 300 python bench.py --full --no-cpu-baseline $args 2>&1 | tail -1)
+    else out=$(env $v timeout -k 10 300 python bench.py --full --no-cpu-baseline $args 2>&1 | tail -1); fi
     python - "$v" "$out" >> $tmp <<'PY'
 import sys, json
 d = json.loads(sys.argv[2]); print(sys.argv[1], d["value"])

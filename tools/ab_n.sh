@@ -5,7 +5,7 @@ tmp=$(mktemp)
 for rep in $(seq $n); do
   for v in "$@"; do
     if [ "$v" = default ]; then unset BFLBM_LIB; else export BFLBM_LIB="$v"; fi
-    out=$(timeout -k 10 300 python bench.py --no-cpu-baseline $args 2>/dev/null | tail -1)
+    out=$(timeout -k 10 300 python bench.py --full --no-cpu-baseline $args 2>/dev/null | tail -1)
     python - "$(basename $v)" "$out" >> $tmp <<'PY'
 import sys, json
 d = json.loads(sys.argv[2]); print(sys.argv[1], d["value"])
