@@ -103,6 +103,14 @@ SIGNATURES = {
     "bflbm_ring_set_ref_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(Fab)]),
     "bflbm_ring_enable_ref_state": (ctypes.c_int, [_vp, ctypes.c_int, _dp]),
     "bflbm_ring_prepare_ref": (ctypes.c_int, [_vp]),
+    "bflbm_batch_create": (ctypes.c_int, [_P(Params), ctypes.c_int, _P(ctypes.c_int), ctypes.c_int, _P(_vp)]),
+    "bflbm_batch_destroy": (ctypes.c_int, [_vp]),
+    "bflbm_batch_size": (ctypes.c_int, [_vp, _P(ctypes.c_int)]),
+    "bflbm_batch_replica": (ctypes.c_int, [_vp, ctypes.c_int, _P(_vp)]),
+    "bflbm_batch_set_schedule": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "bflbm_batch_resolved_schedule": (ctypes.c_int, [_vp, _P(ctypes.c_int)]),
+    "bflbm_batch_step": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "bflbm_batch_sync": (ctypes.c_int, [_vp]),
     "bflbm_set_ref_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(Fab)]),
     "bflbm_enable_ref_state": (ctypes.c_int, [_vp, ctypes.c_int, _dp]),
     "bflbm_ref_state_active": (ctypes.c_int, [_vp, _P(ctypes.c_int)]),

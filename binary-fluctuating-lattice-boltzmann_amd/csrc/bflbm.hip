@@ -17,6 +17,7 @@
 #include "bflbm_kernels.h"
 #include "bflbm_fused.h"
 #include "bflbm_handover.h"
+#include "bflbm_batch.h"
 #ifdef BFLBM_CALIBRATION
 #include "../../tools/calibration_kernels.h"
 #endif
@@ -31,6 +32,12 @@ int fail(const char* fmt, ...) {
   g_err = buf;
   return 1;
 }
+
+// calls a replica view of a batch refuses (include/bflbm.h, "Replica batch")
+#define BFLBM_REFUSE_VIEW(c, call, instead)                                                   \
+  do {                                                                                        \
+    if ((c)->batch) return fail("%s: the context is a replica of a batch; %s", call, instead); \
+  } while (0)
 
 #define HIP_TRY(expr)                                                                         \
   do {                                                                                        \
@@ -119,6 +126,8 @@ struct bflbm_ctx {
   long long ref_kind_step = -1; //   0 COM - com_ref (:588, :653), 1 zero (:690, :739), 2 absolute COM (:623-625)
   double com[3] = {0., 0., 0.}; // global centre of mass (update_com) of the resident state
   bool com_valid = false;
+  bflbm_batch* batch = nullptr; // non-null: a replica view owned by this batch (bflbm_batch_replica)
+  bool batch_dirty = false;     // its parameters changed since the batch last wrote its device record
 };
 
 namespace {
@@ -271,7 +280,9 @@ inline int exact_quiet_schedule(const bflbm_ctx* c) {
 // auto (2): the pipelined hand-over kernel wherever the lattice has full 64 x 4 tiles with distinct neighbours (it
 // generates thermal noise itself but takes no injected noise) where it is the faster one, the parameters are inside the
 // range above and the frames fit in memory; BFLBM_AUTO_EXACT=1 keeps auto on the bit-exact schedules with and without noise.
+int batch_resolved(const bflbm_batch* b);
 inline int resolved_schedule(const bflbm_ctx* c) {
+  if (c->batch) return batch_resolved(c->batch);   // a replica view runs what its batch runs
   if (ref_active(c)) return 0;                   // needs the densities and their centre of mass first
   const bool noisy = c->dp.noise_on || c->inject;
   const int exact = noisy ? 0 : 1;
@@ -404,7 +415,8 @@ int bflbm_device_count(int* n) {
   return 0;
 }
 
-int bflbm_create(const bflbm_params* p, const bflbm_domain* d, bflbm_ctx** out) {
+// ext: a replica of a batch (bflbm_batch_create): runs on the batch's stream ext and draws no placement
+static int create_ctx(const bflbm_params* p, const bflbm_domain* d, hipStream_t ext, bflbm_ctx** out) {
   if (!p || !d || !out) return fail("bflbm_create: null argument");
   if (d->n[0] < 1 || d->n[1] < 1 || d->n[2] < 1) return fail("bflbm_create: lattice size must be >= 1");
   if (d->nranks < 1 || d->rank < 0 || d->rank >= d->nranks) return fail("bflbm_create: bad rank/nranks");
@@ -462,7 +474,10 @@ int bflbm_create(const bflbm_params* p, const bflbm_domain* d, bflbm_ctx** out) 
   if (e == hipSuccess) e = hipMalloc((void**)&c->phi, fbytes);
   c->partial_n = (size_t)((G.plane + 255) / 256) * (size_t)c->nzl;
   if (e == hipSuccess) e = hipMalloc((void**)&c->partial, c->partial_n * 5 * sizeof(double));
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) {
+    if (ext) { c->stream = ext; c->own_stream = false; }
+    else e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+  }
   if (e == hipSuccess) e = hipEventCreate(&c->ev0);
   if (e == hipSuccess) e = hipEventCreate(&c->ev1);
   if (e != hipSuccess) {
@@ -484,9 +499,13 @@ int bflbm_create(const bflbm_params* p, const bflbm_domain* d, bflbm_ctx** out) 
   // profiles/r04_knobs_rescan.txt; a probe there takes 60 ms).
   static const int ncand_env = [] { const char* e = getenv("BFLBM_PLACEMENT_CANDIDATES"); return e ? std::max(1, std::min(atoi(e), 8)) : 0; }();
   const int ncand = ncand_env > 0 ? ncand_env : (2 * sbytes <= ((size_t)24 << 30) ? 8 : 4);
-  if (ncand > 1 && (long long)G.nx * G.ny * c->nzl >= (1LL << 21)) (void)bflbm_tune_placement(c, ncand, nullptr, nullptr);
+  if (!ext && ncand > 1 && (long long)G.nx * G.ny * c->nzl >= (1LL << 21)) (void)bflbm_tune_placement(c, ncand, nullptr, nullptr);
   *out = c;
   return 0;
+}
+
+int bflbm_create(const bflbm_params* p, const bflbm_domain* d, bflbm_ctx** out) {
+  return create_ctx(p, d, nullptr, out);
 }
 
 // ---- physical placement of the state ------------------------------------------------------------------------------
@@ -526,6 +545,7 @@ static int probe_ms(bflbm_ctx* c, float* ms) {
 
 int bflbm_tune_placement(bflbm_ctx* c, int max_candidates, float* ms_per_step, int* kept) {
   if (!c) return fail("null context");
+  BFLBM_REFUSE_VIEW(c, "bflbm_tune_placement", "batches do no placement tuning (bflbm_batch_create)");
   if (c->step_open) return fail("bflbm_tune_placement inside an open step");
   if (max_candidates < 1 || max_candidates > 8) return fail("max_candidates must be 1 ... 8");
   HIP_TRY(hipSetDevice(c->dom.device));
@@ -593,6 +613,7 @@ int bflbm_placement_report(const bflbm_ctx* c, float ms_per_step[8], int* tried,
 }
 int bflbm_destroy(bflbm_ctx* c) {
   if (!c) return 0;
+  BFLBM_REFUSE_VIEW(c, "bflbm_destroy", "the batch owns it: use bflbm_batch_destroy");
   hipSetDevice(c->dom.device);
   if (c->stream && c->own_stream) hipStreamSynchronize(c->stream);
   if (c->S[0]) hipFree(c->S[0]);                 // S[1] lives in the same allocation
@@ -614,6 +635,7 @@ int bflbm_set_params(bflbm_ctx* c, const bflbm_params* p) {
   if (!c || !p) return fail("null argument");
   c->prm = *p;
   derive(c->prm, c->dp);
+  c->batch_dirty = true;                         // a replica view: the batch rewrites its record before the next step
   return 0;
 }
 int bflbm_get_params(const bflbm_ctx* c, bflbm_params* p) {
@@ -624,6 +646,7 @@ int bflbm_get_params(const bflbm_ctx* c, bflbm_params* p) {
 
 int bflbm_set_stream(bflbm_ctx* c, void* s, int external) {
   if (!c) return fail("null context");
+  BFLBM_REFUSE_VIEW(c, "bflbm_set_stream", "it runs on the batch's stream (synchronise with bflbm_batch_sync)");
   HIP_TRY(hipSetDevice(c->dom.device));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (external) {
@@ -645,6 +668,7 @@ int bflbm_resolved_schedule(const bflbm_ctx* c, int* schedule) {
 
 int bflbm_set_schedule(bflbm_ctx* c, int schedule) {
   if (!c) return fail("null context");
+  BFLBM_REFUSE_VIEW(c, "bflbm_set_schedule", "use bflbm_batch_set_schedule");
   if (schedule < 0 || schedule > 3) return fail("unknown schedule %d", schedule);
   c->schedule = schedule;
   return 0;
@@ -805,6 +829,7 @@ int bflbm_download_fg(bflbm_ctx* c, double* f, double* g, const bflbm_fab* box) 
 static int prepare_ref(bflbm_ctx* c);
 int bflbm_step_boundary(bflbm_ctx* c) {
   if (!c) return fail("null context");
+  BFLBM_REFUSE_VIEW(c, "bflbm_step_boundary", "use bflbm_batch_step");
   if (c->step_open) return fail("step already open");
   HIP_TRY(hipSetDevice(c->dom.device));
   if (prepare_ref(c)) return 1;
@@ -832,6 +857,7 @@ int bflbm_step_boundary(bflbm_ctx* c) {
 
 int bflbm_step_interior(bflbm_ctx* c) {
   if (!c) return fail("null context");
+  BFLBM_REFUSE_VIEW(c, "bflbm_step_interior", "use bflbm_batch_step");
   if (!c->step_open) return fail("bflbm_step_interior: call bflbm_step_boundary first");
   HIP_TRY(hipSetDevice(c->dom.device));
   const int lo = own_lo(c), hi = own_hi(c);
@@ -847,6 +873,7 @@ int bflbm_step_interior(bflbm_ctx* c) {
 
 int bflbm_step_finish(bflbm_ctx* c) {
   if (!c) return fail("null context");
+  BFLBM_REFUSE_VIEW(c, "bflbm_step_finish", "use bflbm_batch_step");
   if (!c->step_open) return fail("no open step");
   c->cur = 1 - c->cur;
   c->steps += 1;
@@ -859,6 +886,7 @@ int bflbm_step_finish(bflbm_ctx* c) {
 
 int bflbm_step(bflbm_ctx* c, int nsteps) {
   if (!c) return fail("null context");
+  BFLBM_REFUSE_VIEW(c, "bflbm_step", "use bflbm_batch_step");
   if (nsteps < 0) return fail("nsteps < 0");
   if (!c->G.zwrap && nsteps > 1) return fail("bflbm_step: nranks > 1 needs a halo exchange between steps; use nsteps == 1");
   for (int s = 0; s < nsteps; ++s) {
@@ -901,6 +929,7 @@ int bflbm_set_step_count(bflbm_ctx* c, long long n) {
 // ---- halo exchange support -------------------------------------------------------------
 int bflbm_halo_bytes(const bflbm_ctx* c, int kind, size_t* bytes) {
   if (!c || !bytes) return fail("null argument");
+  BFLBM_REFUSE_VIEW(c, "bflbm_halo_bytes", "replicas are periodic single lattices without halos, advanced by bflbm_batch_step");
   if (kind < 0 || kind > 2) return fail("unknown halo kind %d", kind);
   *bytes = (size_t)2 * Q * (size_t)c->G.plane * sizeof(double);
   return 0;
@@ -908,6 +937,7 @@ int bflbm_halo_bytes(const bflbm_ctx* c, int kind, size_t* bytes) {
 
 int bflbm_halo_pack(bflbm_ctx* c, int kind, int side, void* buf) {
   if (!c || !buf) return fail("null argument");
+  BFLBM_REFUSE_VIEW(c, "bflbm_halo_pack", "replicas are periodic single lattices without halos, advanced by bflbm_batch_step");
   if (c->G.zwrap) return fail("halo exchange on a single slab");
   if (kind < 0 || kind > 2 || side < 0 || side > 1) return fail("bad halo kind/side");
   HIP_TRY(hipSetDevice(c->dom.device));
@@ -919,6 +949,7 @@ int bflbm_halo_pack(bflbm_ctx* c, int kind, int side, void* buf) {
 
 int bflbm_halo_unpack(bflbm_ctx* c, int kind, int side, const void* buf) {
   if (!c || !buf) return fail("null argument");
+  BFLBM_REFUSE_VIEW(c, "bflbm_halo_unpack", "replicas are periodic single lattices without halos, advanced by bflbm_batch_step");
   if (c->G.zwrap) return fail("halo exchange on a single slab");
   if (kind < 0 || kind > 2 || side < 0 || side > 1) return fail("bad halo kind/side");
   HIP_TRY(hipSetDevice(c->dom.device));
@@ -934,6 +965,7 @@ int bflbm_halo_unpack(bflbm_ctx* c, int kind, int side, const void* buf) {
 // kernels wrote it and a receiver straight into the halo plane the next step pulls from.
 int bflbm_halo_planes(bflbm_ctx* c, int kind, int side, int pack, void** planes, size_t* plane_bytes, int* count) {
   if (!c || !planes || !plane_bytes || !count) return fail("null argument");
+  BFLBM_REFUSE_VIEW(c, "bflbm_halo_planes", "replicas are periodic single lattices without halos, advanced by bflbm_batch_step");
   if (c->G.zwrap) return fail("halo exchange on a single slab");
   if (kind < 0 || kind > 2 || side < 0 || side > 1) return fail("bad halo kind/side");
   HaloTable T; halo_table(c, kind, side, pack != 0, T);
@@ -987,6 +1019,7 @@ int bflbm_get_noise(bflbm_ctx* c, double* fn, double* gn, const bflbm_fab* box) 
 
 int bflbm_inject_noise(bflbm_ctx* c, const double* fn, const double* gn, const bflbm_fab* box) {
   if (!c) return fail("null context");
+  BFLBM_REFUSE_VIEW(c, "bflbm_inject_noise", "batches draw generated noise only (set kBT with bflbm_set_params, step with bflbm_batch_step)");
   if (!fn || !gn) { c->inject = false; return 0; }
   HIP_TRY(hipSetDevice(c->dom.device));
   const size_t nb = (size_t)Q * c->nzl * (size_t)c->G.dplane * sizeof(double);
@@ -1047,6 +1080,7 @@ static int prepare_ref(bflbm_ctx* c) {
 
 int bflbm_set_ref_state(bflbm_ctx* c, const double* rho_eq, const double* phi_eq, const double* rhot_eq, const bflbm_fab* box) {
   if (!c || !rho_eq || !phi_eq || !rhot_eq) return fail("null argument");
+  BFLBM_REFUSE_VIEW(c, "bflbm_set_ref_state", "bflbm_batch_step has no reference-state noise (run such a lattice as a lone context)");
   if (check_fab(box)) return 1;
   HIP_TRY(hipSetDevice(c->dom.device));
   const size_t nb = (size_t)c->G.dplane * c->G.nz * sizeof(double);
@@ -1061,6 +1095,7 @@ int bflbm_set_ref_state(bflbm_ctx* c, const double* rho_eq, const double* phi_eq
 
 int bflbm_enable_ref_state(bflbm_ctx* c, int on, const double com_ref[3]) {
   if (!c) return fail("null context");
+  BFLBM_REFUSE_VIEW(c, "bflbm_enable_ref_state", "bflbm_batch_step has no reference-state noise (run such a lattice as a lone context)");
   if (on && (!c->ref[0] || !com_ref)) return fail("bflbm_enable_ref_state: upload the reference state first (bflbm_set_ref_state) and give com_ref");
   c->ref_on = on != 0;
   if (on) for (int d = 0; d < 3; ++d) c->com_ref[d] = com_ref[d];
@@ -1446,6 +1481,192 @@ int bflbm_ring_sync(bflbm_ring* r) {
     if (bflbm_sync(r->ctx[k])) return 1;
     if (k < r->comm.size()) HIP_TRY(hipStreamSynchronize(r->comm[k]));
   }
+  return 0;
+}
+
+}  // extern "C"
+
+// ---- replica batch (include/bflbm.h, "Replica batch"; kernels in bflbm_batch.h) -----------------------------------------
+struct bflbm_batch {
+  std::vector<bflbm_ctx*> ctx;          // the replica views
+  std::vector<long long> steps0;        // per replica: step counter when its record was written
+  hipStream_t stream = nullptr;         // every replica's stream
+  int device = 0;
+  Geo G;                                // the replicas' common geometry
+  int schedule = 2;                     // 0 two-pass, 1 fused, 2 auto
+  BatchRec* d_rec = nullptr;            // per-replica records read by the kernels
+  BatchRec* h_rec = nullptr;            // pinned host copy of what was uploaded
+  bool table_valid = false;
+  long long k = 0;                      // batch steps since the records were written
+};
+
+namespace {
+
+// `auto` of a batch: the rule of exact_quiet_schedule over the whole batch -- the one-pass kernel once the fused
+// workgroups of all replicas fill the compute units, the two-pass schedule otherwise.  Unlike a lone lattice, a batch
+// applies it with noise too (its noise kernel is the 256-thread one of bflbm_batch.h): measured at 32^3 with
+// kBT = 1e-5 (profiles/batch_throughput.txt) 9 replicas (144 workgroups) run two-pass 5240 / fused 4640 MLUPS,
+// 64 replicas (256) 5510 / 6060, 256 replicas 5640 / 6350.
+int batch_resolved(const bflbm_batch* b) {
+  if (b->schedule == 0 || b->schedule == 1) return b->schedule;
+  bool noise = false;
+  for (const bflbm_ctx* c : b->ctx) noise = noise || c->dp.noise_on;
+  FusedGrid F;
+  (void)batch_fused_plan(b->G, (int)b->ctx.size(), noise ? 1 : 0, F);
+  const int ncu = g_fused_ncu > 0 ? g_fused_ncu : 256;
+  return (long long)F.total * (long long)b->ctx.size() < ncu ? 0 : 1;
+}
+
+// Rewrite the device records when some replica changed since they were written: new parameters (bflbm_set_params on a
+// view), a step counter or resident buffer that no longer follows from the batch steps since (an init, an upload,
+// bflbm_set_step_count).  Unchanged replicas cost one comparison per step.
+int batch_sync_table(bflbm_batch* b) {
+  bool stale = !b->table_valid || b->k >= (1LL << 30);
+  for (size_t r = 0; r < b->ctx.size() && !stale; ++r) {
+    const bflbm_ctx* c = b->ctx[r];
+    if (c->batch_dirty || c->steps != b->steps0[r] + b->k || c->cur != (b->h_rec[r].cur0 ^ (int)(b->k & 1))) stale = true;
+  }
+  if (!stale) return 0;
+  HIP_TRY(hipStreamSynchronize(b->stream));      // the previous records may still be in flight to the device
+  for (size_t r = 0; r < b->ctx.size(); ++r) {
+    bflbm_ctx* c = b->ctx[r];
+    BatchRec& R = b->h_rec[r];
+    R.P = c->dp;
+    R.S[0] = c->S[0]; R.S[1] = c->S[1];
+    R.rho = c->rho; R.phi = c->phi;
+    R.idx0 = (uint32_t)c->steps;
+    R.cur0 = c->cur;
+    b->steps0[r] = c->steps;
+    c->batch_dirty = false;
+  }
+  HIP_TRY(hipMemcpyAsync(b->d_rec, b->h_rec, b->ctx.size() * sizeof(BatchRec), hipMemcpyHostToDevice, b->stream));
+  b->k = 0;
+  b->table_valid = true;
+  return 0;
+}
+
+std::string replica_list(const std::vector<int>& v) {
+  std::string out;
+  for (size_t i = 0; i < v.size(); ++i) {
+    if (i == 12) { out += ", ..."; break; }
+    out += (i ? ", " : "") + std::to_string(v[i]);
+  }
+  return out;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bflbm_batch_create(const bflbm_params* p, int nreplicas, const int n[3], int device, bflbm_batch** out) {
+  if (!p || !n || !out) return fail("bflbm_batch_create: null argument");
+  if (nreplicas < 1) return fail("bflbm_batch_create: nreplicas must be >= 1 (got %d)", nreplicas);
+  if (nreplicas > 65535) return fail("bflbm_batch_create: at most 65535 replicas (got %d)", nreplicas);
+  if (n[0] < 1 || n[1] < 1 || n[2] < 1) return fail("bflbm_batch_create: lattice size must be >= 1 (got %d x %d x %d)", n[0], n[1], n[2]);
+  if ((long long)(n[0] + 15) * n[1] * (long long)(n[2] + 4) >= (1LL << 31))
+    return fail("bflbm_batch_create: a replica of %d x %d x %d is too large for 32-bit site offsets", n[0], n[1], n[2]);
+  if ((long long)(n[0] + 15) * n[1] >= (1LL << 28)) return fail("bflbm_batch_create: a plane must stay below 2 GB (32-bit byte offsets inside a plane)");
+  HIP_TRY(hipSetDevice(device));
+  bflbm_batch* b = new bflbm_batch();
+  b->device = device;
+  hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+  if (e != hipSuccess) { b->stream = nullptr; bflbm_batch_destroy(b); return fail("bflbm_batch_create: %s", hipGetErrorString(e)); }
+  for (int r = 0; r < nreplicas; ++r) {
+    bflbm_domain d;
+    for (int a = 0; a < 3; ++a) d.n[a] = n[a];
+    d.z0 = 0; d.z1 = n[2]; d.rank = 0; d.nranks = 1; d.device = device;
+    bflbm_ctx* c = nullptr;
+    if (create_ctx(&p[r], &d, b->stream, &c)) {
+      const std::string msg = g_err;
+      bflbm_batch_destroy(b);
+      return fail("bflbm_batch_create: replica %d: %s", r, msg.c_str());
+    }
+    c->batch = b;
+    b->ctx.push_back(c);
+  }
+  b->G = b->ctx[0]->G;
+  b->steps0.assign(nreplicas, 0);
+  e = hipMalloc((void**)&b->d_rec, (size_t)nreplicas * sizeof(BatchRec));
+  if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_rec, (size_t)nreplicas * sizeof(BatchRec), hipHostMallocDefault);
+  if (e != hipSuccess) { bflbm_batch_destroy(b); return fail("bflbm_batch_create: %s", hipGetErrorString(e)); }
+  memset(b->h_rec, 0, (size_t)nreplicas * sizeof(BatchRec));
+  *out = b;
+  return 0;
+}
+
+int bflbm_batch_destroy(bflbm_batch* b) {
+  if (!b) return 0;
+  hipSetDevice(b->device);
+  if (b->stream) hipStreamSynchronize(b->stream);
+  for (bflbm_ctx* c : b->ctx) { c->batch = nullptr; bflbm_destroy(c); }
+  if (b->d_rec) hipFree(b->d_rec);
+  if (b->h_rec) hipHostFree(b->h_rec);
+  if (b->stream) hipStreamDestroy(b->stream);
+  delete b;
+  return 0;
+}
+
+int bflbm_batch_size(const bflbm_batch* b, int* nreplicas) {
+  if (!b || !nreplicas) return fail("null argument");
+  *nreplicas = (int)b->ctx.size();
+  return 0;
+}
+
+int bflbm_batch_replica(bflbm_batch* b, int r, bflbm_ctx** ctx) {
+  if (!b || !ctx) return fail("null argument");
+  if (r < 0 || r >= (int)b->ctx.size()) return fail("bflbm_batch_replica: replica %d of a batch of %d", r, (int)b->ctx.size());
+  *ctx = b->ctx[r];
+  return 0;
+}
+
+int bflbm_batch_set_schedule(bflbm_batch* b, int schedule) {
+  if (!b) return fail("null batch");
+  if (schedule == 3) return fail("bflbm_batch_set_schedule: schedule 3 (hand-over) is not available for batches; use 0, 1 or 2 (auto)");
+  if (schedule < 0 || schedule > 2) return fail("bflbm_batch_set_schedule: unknown schedule %d", schedule);
+  b->schedule = schedule;
+  return 0;
+}
+
+int bflbm_batch_resolved_schedule(const bflbm_batch* b, int* schedule) {
+  if (!b || !schedule) return fail("null argument");
+  *schedule = batch_resolved(b);
+  return 0;
+}
+
+int bflbm_batch_step(bflbm_batch* b, int nsteps) {
+  if (!b) return fail("null batch");
+  if (nsteps < 0) return fail("nsteps < 0");
+  std::vector<int> quiet, noisy;
+  for (int r = 0; r < (int)b->ctx.size(); ++r) (b->ctx[r]->dp.noise_on ? noisy : quiet).push_back(r);
+  if (!quiet.empty() && !noisy.empty())
+    return fail("bflbm_batch_step: replicas %s have kBT == 0 and replicas %s kBT != 0; a batch steps all replicas with noise or none",
+                replica_list(quiet).c_str(), replica_list(noisy).c_str());
+  for (const bflbm_ctx* c : b->ctx) if (c->step_open) return fail("bflbm_batch_step: a replica has an open step");
+  if (nsteps == 0) return 0;
+  HIP_TRY(hipSetDevice(b->device));
+  const int sch = batch_resolved(b);
+  const bool noise = !noisy.empty();
+  const int nrep = (int)b->ctx.size();
+  for (int s = 0; s < nsteps; ++s) {
+    if (batch_sync_table(b)) return 1;
+    const hipError_t e = sch == 1 ? batch_fused_launch(b->d_rec, b->G, nrep, noise ? 1 : 0, (int)b->k, b->stream)
+                                  : batch_two_pass_launch(b->d_rec, b->G, nrep, noise, (int)b->k, b->stream);
+    if (e != hipSuccess) return fail("bflbm_batch_step: launch failed: %s", hipGetErrorString(e));
+    b->k += 1;
+    for (bflbm_ctx* c : b->ctx) {
+      c->cur = 1 - c->cur;
+      c->steps += 1;
+      c->density_valid = false;
+      c->com_valid = false;
+    }
+  }
+  return 0;
+}
+
+int bflbm_batch_sync(bflbm_batch* b) {
+  if (!b) return fail("null batch");
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 

@@ -565,6 +565,113 @@ class RingLBM(_DropletMixin):
         return a.value, b.value
 
 
+class BatchLBM:
+    """B independent periodic lattices of one shape on one GPU, advanced by one launch per pass (bflbm_batch_*).
+
+    params: one dict of model parameters (with replicas=B: replica r gets seed + r, or seeds[r]) or a list of B dicts
+    (every field may differ, kBT included: all zero or all non-zero).  .replicas are borrowed BinaryLBM views: init,
+    upload, observe, set_params and set_steps_done work on them as on a lone lattice; stepping goes through the batch.
+    Each replica computes, bit for bit, what a lone BinaryLBM with the same parameters, state, step counter and exact
+    schedule computes."""
+
+    def __init__(self, n, params=None, replicas=None, seeds=None, device=0, schedule=None):
+        self.lib = _lib.load()
+        n = (n, n, n) if np.isscalar(n) else tuple(n)
+        if len(n) != 3:
+            raise ValueError("n: one size or three (nx, ny, nz)")
+        self.n = tuple(int(v) for v in n)
+        if params is None or isinstance(params, dict):
+            if replicas is None:
+                raise ValueError("BatchLBM: give replicas= with a single params dict")
+            base = dict(params or {})
+            seed0 = base.pop("seed", int(default_params().seed))
+            if seeds is None:
+                seeds = [seed0 + r for r in range(int(replicas))]
+            plist = [dict(base, seed=int(seeds[r])) for r in range(int(replicas))]
+        else:
+            plist = [dict(p) for p in params]
+            if replicas is not None and int(replicas) != len(plist):
+                raise ValueError(f"BatchLBM: {len(plist)} parameter sets for replicas={replicas}")
+            if seeds is not None:
+                plist = [dict(p, seed=int(s)) for p, s in zip(plist, seeds)]
+        if seeds is not None and len(seeds) != len(plist):
+            raise ValueError("BatchLBM: one seed per replica")
+        self.params = [default_params(**p) for p in plist]
+        arr = (Params * max(1, len(self.params)))(*self.params)
+        n3 = (ctypes.c_int * 3)(*self.n)
+        h = ctypes.c_void_p()
+        check(self.lib.bflbm_batch_create(arr, len(self.params), n3, int(device), ctypes.byref(h)))
+        self._h = h
+        self.replicas = []
+        for r in range(len(self.params)):
+            c = ctypes.c_void_p()
+            check(self.lib.bflbm_batch_replica(self._h, r, ctypes.byref(c)))
+            self.replicas.append(BinaryLBM._borrow(c, self.n, 0, self.n[2], 0, 1, self.params[r]))
+        if schedule is not None:
+            self.set_schedule(schedule)
+
+    def __len__(self):
+        return len(self.replicas)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            for s in self.replicas:
+                for d in list(getattr(s, "_dependents", [])):
+                    d.close()
+            self.lib.bflbm_batch_destroy(self._h)
+            self._h = None
+            for s in self.replicas:
+                s._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_schedule(self, schedule):
+        """"two_pass" (0), "fused" (1) or "auto" (2); the hand-over schedule is not available for batches."""
+        check(self.lib.bflbm_batch_set_schedule(self._h, int(SCHEDULES.get(schedule, schedule))))
+
+    def resolved_schedule(self):
+        v = ctypes.c_int()
+        check(self.lib.bflbm_batch_resolved_schedule(self._h, ctypes.byref(v)))
+        return {0: "two_pass", 1: "fused"}[v.value]
+
+    def LBM_timestep(self, nsteps=1):
+        """LBM_timestep x nsteps on every replica."""
+        check(self.lib.bflbm_batch_step(self._h, int(nsteps)))
+
+    def sync(self):
+        check(self.lib.bflbm_batch_sync(self._h))
+
+    # -- stacked getters: a leading replica axis ------------------------------------------------
+    def populations(self):
+        f = np.empty((len(self.replicas), NVEL, self.n[2], self.n[1], self.n[0]))
+        g = np.empty_like(f)
+        for r, s in enumerate(self.replicas):
+            s.populations(f[r], g[r])
+        return f, g
+
+    def LBM_hydrovars(self, ncomp=NHYDRO):
+        out = np.empty((len(self.replicas), ncomp, self.n[2], self.n[1], self.n[0]))
+        for r, s in enumerate(self.replicas):
+            s.LBM_hydrovars(out[r], ncomp=ncomp)
+        return out
+
+    def LBM_hydrovars_density(self):
+        out = np.empty((len(self.replicas), NHYDROBAR, self.n[2], self.n[1], self.n[0]))
+        for r, s in enumerate(self.replicas):
+            s.LBM_hydrovars_density(out[r])
+        return out
+
+
 def rng_site_normals(seed, site, noise_index):
     """Host evaluation of the project's Gaussian stream: the 33 normals of one site and noise index."""
     out = (ctypes.c_double * 36)()

@@ -225,6 +225,40 @@ int bflbm_ring_set_ref_state(bflbm_ring* r, const double* rho_eq, const double* 
 int bflbm_ring_enable_ref_state(bflbm_ring* r, int on, const double com_ref[3]);
 int bflbm_ring_prepare_ref(bflbm_ring* r);
 
+/* ---- Replica batch: nreplicas independent periodic lattices of one shape n[3] on one GPU, advanced by one launch per
+ * pass (the ensembles of small boxes the reference is run for: several droplets, noise ensembles).
+ *  - replica r is an ordinary single-slab lattice (nranks = 1) with its own parameters p[r] (every field may differ,
+ *    seed and kBT included), its own state and its own step counter.  One bflbm_batch_step advances every replica by
+ *    one LBM_timestep; each replica's result equals, bit for bit, what a lone context with the same parameters, state,
+ *    step counter and (forced) exact schedule computes.
+ *  - bflbm_batch_replica returns a VIEW: a real bflbm_ctx owned by the batch.  Every per-context call works on it
+ *    unchanged (inits, bflbm_upload_fg / bflbm_commit_upload, bflbm_download_fg, bflbm_get_*, bflbm_com_sums,
+ *    bflbm_mass, bflbm_set_params / bflbm_get_params, bflbm_step_count / bflbm_set_step_count, the timers, the
+ *    structure-factor and droplet calls); its work is enqueued on the batch's stream, so it is ordered against
+ *    bflbm_batch_step.  bflbm_set_params on a view takes effect at the next batch step.
+ *  - refused on a view (non-zero return, a message naming the batch call to use, state untouched): bflbm_destroy,
+ *    bflbm_step / _boundary / _interior / _finish, bflbm_set_schedule, bflbm_set_stream, bflbm_tune_placement,
+ *    bflbm_inject_noise, bflbm_set_ref_state / bflbm_enable_ref_state and the halo calls.  Batches do no placement
+ *    tuning, take no injected noise and no reference state, and run on one GPU.
+ *  - noise: every replica draws its generated noise with its own seed and its own step counter as the noise index, so
+ *    bflbm_set_step_count on a view shifts only that replica's stream.  A batch with some replicas at kBT == 0 and
+ *    others at kBT != 0 is refused by bflbm_batch_step before any launch (the message names the replicas); different
+ *    non-zero kBT within one batch are fine.
+ *  - schedules: 0 two-pass, 1 fused (pulled ring), 2 auto (default): 1 at zero noise when the fused workgroups of the
+ *    whole batch fill the device's compute units, 0 otherwise (with noise too).  Both are bit-exact, the choice affects
+ *    speed only.  Schedule 3 is refused.
+ *  - bflbm_batch_create checks its arguments before it touches a device: null pointers, nreplicas < 1 (or > 65535), a
+ *    lattice size < 1, a replica too large for the 32-bit offsets of bflbm_create. */
+typedef struct bflbm_batch bflbm_batch;
+int bflbm_batch_create(const bflbm_params* p /* nreplicas entries */, int nreplicas, const int n[3], int device, bflbm_batch** out);
+int bflbm_batch_destroy(bflbm_batch* b);
+int bflbm_batch_size(const bflbm_batch* b, int* nreplicas);
+int bflbm_batch_replica(bflbm_batch* b, int r, bflbm_ctx** ctx);   /* a view; owned by the batch */
+int bflbm_batch_set_schedule(bflbm_batch* b, int schedule);         /* 0, 1 or 2 (auto); 3 is refused */
+int bflbm_batch_resolved_schedule(const bflbm_batch* b, int* schedule);
+int bflbm_batch_step(bflbm_batch* b, int nsteps);
+int bflbm_batch_sync(bflbm_batch* b);
+
 /* Materialise the per-step fields the reference keeps in MultiFabs, for the state
  * after the last completed step:
  *   hydrovsbar comps 0..8  (LBM_hydrovars_density, LBM_binary.H:315-354)
