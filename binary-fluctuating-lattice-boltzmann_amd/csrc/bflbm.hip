@@ -18,9 +18,6 @@
 #include "bflbm_fused.h"
 #include "bflbm_handover.h"
 #include "bflbm_batch.h"
-#ifdef BFLBM_CALIBRATION
-#include "../../tools/calibration_kernels.h"
-#endif
 
 namespace {
 
@@ -248,12 +245,11 @@ inline bool handover_contract_params(const bflbm_ctx* c) {
 // noise, where the alternative is the one-pass schedule 1, a last tile column that is not mostly idle lanes (96^3: 75 %
 // of the lanes busy, -9 %; 200^3: 78 %, +4 %; 300^3: +13 %; 250^3 with a last tile row of two rows: +9 %).  With noise the
 // alternative is the two-pass schedule and the hand-over kernel wins on every ragged lattice measured (250^3 +25 %).
-// BFLBM_AUTO_MIN_LZ overrides the 16.
 inline bool handover_worthwhile(const bflbm_ctx* c, bool noisy) {
-  static const int min_lz = [] { const char* e = getenv("BFLBM_AUTO_MIN_LZ"); return e ? atoi(e) : 16; }();
+  constexpr int min_lz = 16;
   const int lo = c->G.H, hi = c->G.H + c->nzl;
   const int a = c->G.zwrap ? lo : lo + 2, b = c->G.zwrap ? hi : hi - 2;   // the interior sweep
-  if (b - a < min_lz || b - a < 4) return false;
+  if (b - a < min_lz) return false;
   FusedGrid F;
   handover_plan(c->G, a, b, 0, F);
   if (F.lz < min_lz) return false;
@@ -272,8 +268,7 @@ inline int exact_quiet_schedule(const bflbm_ctx* c) {
   if (b - a < 2) return 0;                       // a slab of 4 or 5 planes is all boundary pairs
   FusedGrid F;
   (void)fused_plan(c->G, a, b, 0, 0, F);
-  const int ncu = g_fused_ncu > 0 ? g_fused_ncu : 256;
-  return F.total < ncu ? 0 : 1;
+  return F.total < device_cus() ? 0 : 1;
 }
 
 // 0 two-pass, 1 fused (pulled ring), 3 hand-over.  The bit-exact choice is 1 at zero noise and 0 with noise.
@@ -288,13 +283,10 @@ inline int resolved_schedule(const bflbm_ctx* c) {
   const int exact = noisy ? 0 : 1;
   if (c->schedule == 3) return (!c->inject && handover_ok(c->G)) ? 3 : exact;
   if (c->schedule != 2) return c->schedule;
-  static const int auto_noise_fused = [] { const char* e = getenv("BFLBM_AUTO_NOISE_HANDOVER"); return e ? atoi(e) != 0 : true; }();
   static const int auto_exact = [] { const char* e = getenv("BFLBM_AUTO_EXACT"); return e && atoi(e) != 0; }();
   const int auto_exact_choice = noisy ? 0 : exact_quiet_schedule(c);
   if (auto_exact || c->inject || c->frames_unavailable || !handover_ok(c->G) || !handover_contract_params(c)) return auto_exact_choice;
-  if (!handover_worthwhile(c, noisy)) return auto_exact_choice;
-  if (noisy && !auto_noise_fused) return 0;
-  return 3;
+  return handover_worthwhile(c, noisy) ? 3 : auto_exact_choice;
 }
 
 // the slab's own planes are [H, H+nzl)
@@ -307,6 +299,20 @@ int ensure_density(bflbm_ctx* c) {
   if (launch_density(c, own_lo(c) - ext, own_hi(c) + ext)) return 1;
   c->density_valid = true;
   return 0;
+}
+
+// One sweep of the resolved schedule sch (0 two-pass, 1 fused, 3 hand-over) over the storage planes [pa, pb).
+// pair_len > 0: only the boundary plane pairs [pa, pa+pair_len) and [pb-pair_len, pb) of a slab; the plane-marching
+// kernels take both in one launch where they are disjoint.
+int launch_sweep(bflbm_ctx* c, int sch, int pa, int pb, int pair_len = 0) {
+  if (sch == 0) {
+    if (ensure_density(c)) return 1;
+    if (pair_len == 0) return launch_collide(c, pa, pb);
+    return launch_collide(c, pa, pa + pair_len) || launch_collide(c, pb - pair_len, pb);
+  }
+  auto launch = [&](int a, int b) { return sch == 3 ? launch_handover(c, a, b, pair_len) : launch_fused(c, a, b, pair_len); };
+  if (pair_len == 0 || pb - pa > 2 * pair_len) return launch(pa, pb);
+  return launch(pa, pa + pair_len) || launch(pb - pair_len, pb);
 }
 
 struct Overlap { int x0, x1, y0, y1, z0, z1; bool empty; };
@@ -441,22 +447,14 @@ static int create_ctx(const bflbm_params* p, const bflbm_domain* d, hipStream_t 
   // multiple of 16 (pitch == nx, same code path).  Most of what such sizes lose against 256^3 is partial
   // tiles, not alignment.  Dense layouts (dplane) are kept for everything that crosses the ABI.
   G.pitch = (G.nx > 16) ? ((G.nx + 15) & ~15) : G.nx;
-  {                                              // tuning override: row pitch in doubles (a multiple of 16, >= nx); see NOTES.md "Round 4"
-    static const int pitch_env = [] { const char* e = getenv("BFLBM_PITCH"); return e ? atoi(e) : 0; }();
-    if (pitch_env > 0) {
-      if (pitch_env < G.nx || (pitch_env & 15)) { delete c; return fail("BFLBM_PITCH must be a multiple of 16 and at least nx"); }
-      G.pitch = pitch_env;
-    }
-  }
   G.plane = (long long)G.pitch * G.ny;
   G.dplane = (long long)G.nx * G.ny;
   // component stride: padded so that the 38 component arrays of a power-of-two lattice do not all start
   // on the same memory channel / L2 set.  Measured on MI355X (256^3): no pad -> 65 lines (1040 doubles):
   // pull-copy 1.96 -> 1.77 ms, fused step 2.57 -> 2.35 ms; a scan with reproducible placement (one
-  // allocation, below) gives 0: 6780, 1040: 6870-6940, 65552: 6935-7000, 262160: 6970, 1048592: 6730 MLUPS
-  // -> 65552 doubles = 512 KB + one line (BFLBM_PAD = doubles, tuning override).
-  static const long long pad = [] { const char* e = getenv("BFLBM_PAD"); return e ? atoll(e) : 1040LL; }();
-  if (pad < 0 || (pad & 1)) { delete c; return fail("BFLBM_PAD must be a non-negative even number of doubles"); }
+  // allocation, below) gives 0: 6780, 1040: 6870-6940, 65552: 6935-7000, 262160: 6970, 1048592: 6730 MLUPS.
+  // The pad is 1040 doubles: 65552 was A/B-tested again in round 2 and is indistinguishable (NOTES.md section 3.1).
+  constexpr long long pad = 1040;
   G.vol = G.plane * G.nzs + pad;
   const size_t sbytes = (size_t)2 * Q * G.vol * sizeof(double);
   const size_t fbytes = (size_t)G.vol * sizeof(double);
@@ -465,9 +463,8 @@ static int create_ctx(const bflbm_params* p, const bflbm_domain* d, hipStream_t 
   // end of A.  With two separate allocations the relative placement of the read and the write stream of a
   // component varied from process to process and with it the step time (6510-7190 MLUPS at 256^3 on one
   // box); inside one allocation it is reproducible to 0.3 %, 520 doubles is a bad displacement (-4 %),
-  // anything from 25k to 1M doubles is equally good (BFLBM_AB_OFF = doubles, tuning override).
-  static const long long ab_off = [] { const char* e = getenv("BFLBM_AB_OFF"); return e ? atoll(e) : 33280LL; }();
-  if (ab_off < 0 || (ab_off & 1)) { delete c; return fail("BFLBM_AB_OFF must be a non-negative even number of doubles"); }
+  // anything from 25k to 1M doubles is equally good.
+  constexpr long long ab_off = 33280;
   e = hipMalloc((void**)&c->S[0], 2 * sbytes + (size_t)ab_off * sizeof(double));
   if (e == hipSuccess) c->S[1] = c->S[0] + (size_t)2 * Q * G.vol + ab_off;
   if (e == hipSuccess) e = hipMalloc((void**)&c->rho, fbytes);
@@ -575,25 +572,22 @@ int bflbm_tune_placement(bflbm_ctx* c, int max_candidates, float* ms_per_step, i
     double* oldS[2] = { c->S[0], c->S[1] };
     double* oldF[2] = { c->frames[0], c->frames[1] };
     double* nS = nullptr; double* nF = nullptr;
-    // diagnostics (tools/level_probe.py): BFLBM_TUNE_WHAT=state|frames draws only that allocation again (which of the two decides the level?)
-    const char* what_env = getenv("BFLBM_TUNE_WHAT");
-    const bool draw_state = !what_env || strcmp(what_env, "frames") != 0, draw_frames = fbytes && (!what_env || strcmp(what_env, "state") != 0);
-    if (draw_state && hipMalloc((void**)&nS, state_bytes) != hipSuccess) { (void)hipGetLastError(); break; }
-    if (draw_frames && hipMalloc((void**)&nF, fbytes) != hipSuccess) { (void)hipGetLastError(); if (nS) hipFree(nS); break; }
-    if (draw_state) { c->S[0] = nS; c->S[1] = nS + (oldS[1] - oldS[0]); hipMemsetAsync(nS, 0, state_bytes, c->stream); }
-    if (draw_frames) { c->frames[0] = nF; c->frames[1] = nF + handover_frame_doubles(G); }
+    if (hipMalloc((void**)&nS, state_bytes) != hipSuccess) { (void)hipGetLastError(); break; }
+    if (fbytes && hipMalloc((void**)&nF, fbytes) != hipSuccess) { (void)hipGetLastError(); hipFree(nS); break; }
+    c->S[0] = nS; c->S[1] = nS + (oldS[1] - oldS[0]); hipMemsetAsync(nS, 0, state_bytes, c->stream);
+    if (nF) { c->frames[0] = nF; c->frames[1] = nF + handover_frame_doubles(G); }
     c->cur = 0;
     float ms = 0.f;
     const int rc = probe_ms(c, &ms);
     if (ms_per_step) ms_per_step[k] = rc ? -1.f : ms;
     if (k < 8) { c->tune_ms[k] = rc ? -1.f : ms; c->tune_n = k + 1; }
     if (!rc && ms < best_ms * 0.995f) {              // keep the new one
-      if (draw_state) hipFree(oldS[0]);
-      if (draw_frames && oldF[0]) hipFree(oldF[0]);
+      hipFree(oldS[0]);
+      if (nF) hipFree(oldF[0]);
       best_ms = ms; best = k;
     } else {                                        // keep the old one
       (void)hipStreamSynchronize(c->stream);
-      if (nS) hipFree(nS);
+      hipFree(nS);
       if (nF) hipFree(nF);
       c->S[0] = oldS[0]; c->S[1] = oldS[1]; c->frames[0] = oldF[0]; c->frames[1] = oldF[1];
       if (rc) { (void)fresh(); return 1; }
@@ -840,17 +834,7 @@ int bflbm_step_boundary(bflbm_ctx* c) {
   c->step_open = true;
   const int lo = own_lo(c), hi = own_hi(c);
   if (c->G.zwrap) return 0;                      // single slab: everything is "interior"
-  const int sch = resolved_schedule(c);
-  int rc;
-  if (sch == 3) {
-    if (hi - lo > 4) rc = launch_handover(c, lo, hi, 2);
-    else rc = launch_handover(c, lo, lo + 2, 2) || launch_handover(c, hi - 2, hi, 2);
-  } else if (sch == 1) {
-    if (hi - lo > 4) rc = launch_fused(c, lo, hi, 2);        // both boundary plane pairs in one launch
-    else rc = launch_fused(c, lo, lo + 2) || launch_fused(c, hi - 2, hi);
-  } else {
-    rc = ensure_density(c) || launch_collide(c, lo, lo + 2) || launch_collide(c, hi - 2, hi);
-  }
+  const int rc = launch_sweep(c, resolved_schedule(c), lo, hi, 2);
   if (rc) c->step_open = false;                  // a failed launch wrote nothing that the resident state S[cur] holds
   return rc;
 }
@@ -862,11 +846,7 @@ int bflbm_step_interior(bflbm_ctx* c) {
   HIP_TRY(hipSetDevice(c->dom.device));
   const int lo = own_lo(c), hi = own_hi(c);
   const int a = c->G.zwrap ? lo : lo + 2, b = c->G.zwrap ? hi : hi - 2;
-  const int sch = resolved_schedule(c);
-  int rc;
-  if (sch == 3) rc = launch_handover(c, a, b);
-  else if (sch == 1) rc = launch_fused(c, a, b);
-  else rc = ensure_density(c) || launch_collide(c, a, b);
+  const int rc = launch_sweep(c, resolved_schedule(c), a, b);
   if (rc) c->step_open = false;                  // as in bflbm_step_boundary: S[cur] is intact, the step may be retried
   return rc;
 }
@@ -896,16 +876,6 @@ int bflbm_step(bflbm_ctx* c, int nsteps) {
   }
   return 0;
 }
-
-#ifdef BFLBM_STAMP
-// diagnostic build only: the phase stamps of the hand-over kernel (tools/ho_stamps.py)
-int bflbm_debug_ho_stamps(unsigned long long* out, int n) {
-  if (!out || n > 4 * HO_STAMP_POS * HO_NSTAMP) return fail("bad argument");
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ho_stamps), (size_t)n * sizeof(unsigned long long)));
-  return 0;
-}
-#endif
 
 int bflbm_step_count(const bflbm_ctx* c, long long* n) {
   if (!c || !n) return fail("null argument");
@@ -1155,10 +1125,6 @@ int bflbm_debug_time_kernel(bflbm_ctx* c, int which, int reps, float* ms) {
     if (r == 0) HIP_TRY(hipEventRecord(c->ev0, c->stream));
     if (which == 0) hipLaunchKernelGGL(k_pull, plane_grid(c, c->nzl), dim3(256), 0, c->stream, c->S[c->cur], c->S[1 - c->cur], c->G, own_lo(c));
     else if (which == 1) hipLaunchKernelGGL(k_density, plane_grid(c, c->nzl), dim3(256), 0, c->stream, c->S[c->cur], c->rho, c->phi, c->G, own_lo(c));
-#ifdef BFLBM_CALIBRATION
-    else if (which == 3 && c->G.pitch == c->G.nx) hipLaunchKernelGGL(k_pull2, dim3((unsigned)((c->G.plane / 2 + 255) / 256), (unsigned)c->nzl), dim3(256), 0, c->stream, c->S[c->cur], c->S[1 - c->cur], c->G, own_lo(c));
-    else if (which == 4 && c->G.zwrap && c->G.pitch == c->G.nx) hipLaunchKernelGGL(k_pull_rows, plane_grid(c, c->nzl), dim3(256), 0, c->stream, c->S[c->cur], c->S[1 - c->cur], c->G, own_lo(c));
-#endif
     else if (which == 2) HIP_TRY(hipMemcpyAsync(c->S[1 - c->cur], c->S[c->cur], sbytes, hipMemcpyDeviceToDevice, c->stream));
     else return fail("unknown diagnostic kernel %d", which);
   }
@@ -1513,8 +1479,7 @@ int batch_resolved(const bflbm_batch* b) {
   for (const bflbm_ctx* c : b->ctx) noise = noise || c->dp.noise_on;
   FusedGrid F;
   (void)batch_fused_plan(b->G, (int)b->ctx.size(), noise ? 1 : 0, F);
-  const int ncu = g_fused_ncu > 0 ? g_fused_ncu : 256;
-  return (long long)F.total * (long long)b->ctx.size() < ncu ? 0 : 1;
+  return (long long)F.total * (long long)b->ctx.size() < device_cus() ? 0 : 1;
 }
 
 // Rewrite the device records when some replica changed since they were written: new parameters (bflbm_set_params on a

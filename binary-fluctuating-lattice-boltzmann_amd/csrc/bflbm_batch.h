@@ -60,7 +60,7 @@ __device__ __forceinline__ void collide_batch_body(const double* __restrict__ S,
 #include "bflbm_collide_body.inc"
 }
 template <bool NOISE>
-__global__ void __launch_bounds__(256, BFLBM_COLLIDE_WAVES) k_collide_batch(const BatchRec* __restrict__ recs, Geo G, int k) {
+__global__ void __launch_bounds__(256, COLLIDE_WAVES) k_collide_batch(const BatchRec* __restrict__ recs, Geo G, int k) {
   const BatchRecC R = batch_rec(recs, (int)blockIdx.z);
   const int cur = R->cur0 ^ (k & 1);
   collide_batch_body<NOISE>(R->S[cur], R->S[cur ^ 1], R->rho, R->phi, G, batch_params(R), R->idx0 + (uint32_t)k);
@@ -101,7 +101,7 @@ k_fused_batch(const BatchRec* __restrict__ recs, Geo G, FusedGrid F, int nrep, i
 }
 
 // the batch's tile shape and chunking: the single-lattice plan with the workgroups of all replicas counted
-static inline int batch_fused_threads(int mode) { return mode == 1 ? 256 : BFLBM_FUSED_TX * BFLBM_FUSED_TY; }
+static inline int batch_fused_threads(int mode) { return mode == 1 ? 256 : FUSED_TX * FUSED_TY; }
 static inline int batch_fused_plan(const Geo& G, int nrep, int mode, FusedGrid& F) {
   return fused_plan(G, 0, G.nzs, mode, 0, F, nrep, batch_fused_threads(mode));
 }
@@ -112,7 +112,7 @@ static inline hipError_t batch_fused_launch(const BatchRec* recs, const Geo& G, 
   const long long per_xcd = ((long long)nrep * F.total + 7) / 8;
   if (per_xcd * 8 > (long long)INT32_MAX) return hipErrorInvalidConfiguration;
   dim3 grid((unsigned)(per_xcd * 8)), block(batch_fused_threads(mode));
-  constexpr int TX0 = BFLBM_FUSED_TX, TY0 = BFLBM_FUSED_TY;
+  constexpr int TX0 = FUSED_TX, TY0 = FUSED_TY;
   if (mode == 1)      hipLaunchKernelGGL((k_fused_batch<32, 8, 1>), grid, block, 0, stream, recs, G, F, nrep, k);
   else if (TX == 32)  hipLaunchKernelGGL((k_fused_batch<32, (TX0 * TY0) / 32, 0>), grid, block, 0, stream, recs, G, F, nrep, k);
   else if (TX == 16)  hipLaunchKernelGGL((k_fused_batch<16, (TX0 * TY0) / 16, 0>), grid, block, 0, stream, recs, G, F, nrep, k);

@@ -58,7 +58,7 @@
     }
     d_populations(m, fs);
 #pragma unroll
-    for (int i = 0; i < Q; ++i) st_pop(Dp + (long long)i*G.vol, BFLBM_XSHIFT ? I.o[1][1 + BFLBM_SX(Vel::cx[i])] : o, fs[i]);
+    for (int i = 0; i < Q; ++i) st_pop(Dp + (long long)i*G.vol, o, fs[i]);
   }
   {
     double m[Q];
@@ -76,5 +76,5 @@
     }
     d_populations(m, gs);
 #pragma unroll
-    for (int i = 0; i < Q; ++i) st_pop(Dp + (long long)(i+Q)*G.vol, BFLBM_XSHIFT ? I.o[1][1 + BFLBM_SX(Vel::cx[i])] : o, gs[i]);
+    for (int i = 0; i < Q; ++i) st_pop(Dp + (long long)(i+Q)*G.vol, o, gs[i]);
   }

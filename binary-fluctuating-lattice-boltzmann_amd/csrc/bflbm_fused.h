@@ -80,60 +80,41 @@ k_fused(const double* __restrict__ S, double* __restrict__ D,
 #undef BFLBM_FUSED_MAP
 }
 
-#ifndef BFLBM_FUSED_TX
-#define BFLBM_FUSED_TX 64
-#endif
-#ifndef BFLBM_FUSED_TY
-#define BFLBM_FUSED_TY 8
-#endif
+constexpr int FUSED_TX = 64, FUSED_TY = 8;   // tile shape of the fused kernel (narrower lattices at zero noise: see fused_plan)
 
 static int g_fused_ncu = 0;     // compute units of the device (set at context creation)
-// Tile shape, chunking and workgroup order of one launch of the fused kernel over the storage planes [pa, pb); returns the
-// tile width (the height is 512 / width)
-// nrep > 1: a replica batch launches nrep copies of this plan (bflbm_batch.h); the chunking then counts all of their workgroups.
-// threads: workgroup size (tiles of at least 8 rows; the batch's noise kernel runs 256)
-static inline int fused_plan(const Geo& G, int pa, int pb, int mode, int pair_len, FusedGrid& F, int nrep = 1,
-                             int threads = BFLBM_FUSED_TX * BFLBM_FUSED_TY) {
-  // pair_len > 0: ONE launch over the two disjoint plane ranges [pa, pa+pair_len) and [pb-pair_len, pb)
-  // (the boundary plane pairs of a slab), one chunk each.
-  // Tile shape: 64 x 8 sites; lattices narrower than 64 in x get the same 512 sites as 32 x 16, 16 x 32 or 8 x 64
-  // (zero noise only; e.g. the reference's 8 x 256 x 64 flat-interface box would use 8 of 64 lanes of a 64-wide tile)
-  const int TX = std::min((mode != 0 || G.nx > 32) ? BFLBM_FUSED_TX : (G.nx > 16 ? 32 : (G.nx > 8 ? 16 : 8)), threads / 8);
-  const int TY = threads / TX;
-  F.ntx = (G.nx + TX - 1) / TX;
-  F.nty = (G.ny + TY - 1) / TY;
-  F.ncols = F.ntx * F.nty;
-  F.pa = pa; F.pb = pb;
-  const int np = pb - pa;
-  static const int want_env = [] { const char* e = getenv("BFLBM_FUSED_WG"); return e ? atoi(e) : 0; }();
-  // Chunking.  One workgroup is resident per CU, so the launch runs in rounds of `ncu` workgroups and costs
-  // about  rounds x (planes per chunk + 1)  plane marches (a chunk of L planes marches L+2, the two extra
-  // ones pull only).  Pick the chunk count that minimises this: 256^3 -> 128 columns x 2 chunks = one full
-  // round; 192^3 -> 72 columns x 7 chunks = 504 workgroups in 2 rounds of 30 planes instead of 288 in
-  // "1.1" rounds of 50.  Marches longer than 256 planes are avoided on a single slab (neighbouring
-  // workgroups drift apart and lose L2 sharing; measured on MI355X); a slab of a multi-GPU run is cut
-  // into >= 3 rounds of shorter workgroups so that the RCCL copy kernels of the overlapped exchange, which
-  // need a few CUs of their own, delay at most a short tail of the interior sweep.
-  // BFLBM_FUSED_WG overrides the target workgroup count (tuning only).
-  const int ncu = g_fused_ncu > 0 ? g_fused_ncu : 256;
-  // BFLBM_SLAB_ROUNDS: minimum number of rounds of the interior sweep of a slab (default 3; tuning knob for
-  // real multi-GPU runs: fewer rounds = less look-ahead overhead, more = shorter tail behind the RCCL kernels)
-  static const int min_slab_rounds = [] { const char* e = getenv("BFLBM_SLAB_ROUNDS"); return e && atoi(e) > 0 ? atoi(e) : 3; }();
-  const int maxchunks = std::max(1, np / 2);                     // small lattices: short chunks buy parallelism
-  int nchunks;
-  if (want_env > 0) {
-    nchunks = std::min(maxchunks, std::max(1, (want_env + F.ncols - 1) / F.ncols));
-  } else {
-    long long best = -1; nchunks = 1;
-    for (int k = 1; k <= maxchunks; ++k) {
-      const int lz = (np + k - 1) / k, chunks = (np + lz - 1) / lz;
-      if (chunks != k) continue;                                  // same partition as a smaller k
-      if (G.zwrap && lz > 256 && k < maxchunks) continue;
-      const long long total = (long long)F.ncols * chunks * nrep, rounds = (total + ncu - 1) / ncu;
-      if (!G.zwrap && rounds < min_slab_rounds && k < maxchunks) continue;
-      const long long cost = rounds * (lz + 1);
-      if (best < 0 || cost < best) { best = cost; nchunks = k; }
-    }
+static inline int device_cus() { return g_fused_ncu > 0 ? g_fused_ncu : 256; }
+
+// Chunking of a launch of np planes over F.ncols tile columns (both plane-marching kernels); fills lz, nchunks, cstride,
+// total and per_xcd.  min_chunk: the shortest chunk the kernel takes.  nrep > 1: a replica batch launches nrep copies of
+// the plan (bflbm_batch.h), so the search counts all of their workgroups.  pair_len > 0: ONE launch over the two disjoint
+// plane ranges [pa, pa+pair_len) and [pb-pair_len, pb) (the boundary plane pairs of a slab), one chunk each.
+//
+// One workgroup is resident per CU, so the launch runs in rounds of `ncu` workgroups and costs about
+// rounds x (planes per chunk + 1) plane marches (a chunk of L planes marches L+2, the two extra ones pull only).  Pick the
+// chunk count that minimises this: 256^3 -> 128 columns x 2 chunks = one full round; 192^3 -> 72 columns x 7 chunks = 504
+// workgroups in 2 rounds of 30 planes instead of 288 in "1.1" rounds of 50.  Marches longer than 256 planes are avoided on
+// a single slab (neighbouring workgroups drift apart and lose L2 sharing; measured on MI355X, and one 512-plane march per
+// column of the hand-over kernel was A/B-tested: -1 %); a slab of a multi-GPU run is cut into >= 3 rounds of shorter
+// workgroups so that the RCCL copy kernels of the overlapped exchange, which need a few CUs of their own, delay at most a
+// short tail of the interior sweep.  Round 4 scanned the hand-over kernel's chunk count at 256^3 ... 512^3 on two boxes
+// (profiles/r04_chunk_scan.txt): a model fitted on the first box ((rounds + tail) x (planes + 4): 448^3 +5 % with 7
+// chunks, 512^3 +5 % with 4) changed nothing on the second (every lattice within the +-2 % process-to-process scatter,
+// 512x512x128 2 % SLOWER with its choice), so the rule stays.
+static inline void plan_chunks(FusedGrid& F, int np, bool zwrap, int min_chunk, int nrep, int pair_len) {
+  constexpr int min_slab_rounds = 3;
+  const int ncu = device_cus();
+  const int maxchunks = std::max(1, np / min_chunk);             // small lattices: short chunks buy parallelism
+  long long best = -1;
+  int nchunks = 1;
+  for (int k = 1; k <= maxchunks; ++k) {
+    const int lz = (np + k - 1) / k, chunks = (np + lz - 1) / lz;
+    if (chunks != k) continue;                                    // same partition as a smaller k
+    if (zwrap && lz > 256 && k < maxchunks) continue;
+    const long long total = (long long)F.ncols * chunks * nrep, rounds = (total + ncu - 1) / ncu;
+    if (!zwrap && rounds < min_slab_rounds && k < maxchunks) continue;
+    const long long cost = rounds * (lz + 1);
+    if (best < 0 || cost < best) { best = cost; nchunks = k; }
   }
   F.lz = (np + nchunks - 1) / nchunks;
   F.nchunks = (np + F.lz - 1) / F.lz;
@@ -141,7 +122,23 @@ static inline int fused_plan(const Geo& G, int pa, int pb, int mode, int pair_le
   if (pair_len > 0 && np > 2 * pair_len) { F.lz = pair_len; F.nchunks = 2; F.cstride = np - pair_len; }
   F.total = F.ncols * F.nchunks;
   F.per_xcd = (F.total + 7) / 8;
-  { static const int sx_env = [] { const char* e = getenv("BFLBM_MAP_SX"); return e ? atoi(e) : 0; }(); F.sx = sx_env > 0 ? sx_env : std::min(F.ntx, 4); }   // strips of 4 tiles: +2 % at 512^3 (ntx = 8), identical at 256^3
+}
+
+// Tile shape, chunking and workgroup order of one launch of the fused kernel over the storage planes [pa, pb); returns the
+// tile width (the height is threads / width).  nrep, pair_len: see plan_chunks.
+// threads: workgroup size (tiles of at least 8 rows; the batch's noise kernel runs 256)
+static inline int fused_plan(const Geo& G, int pa, int pb, int mode, int pair_len, FusedGrid& F, int nrep = 1,
+                             int threads = FUSED_TX * FUSED_TY) {
+  // Tile shape: 64 x 8 sites; lattices narrower than 64 in x get the same 512 sites as 32 x 16, 16 x 32 or 8 x 64
+  // (zero noise only; e.g. the reference's 8 x 256 x 64 flat-interface box would use 8 of 64 lanes of a 64-wide tile)
+  const int TX = std::min((mode != 0 || G.nx > 32) ? FUSED_TX : (G.nx > 16 ? 32 : (G.nx > 8 ? 16 : 8)), threads / 8);
+  const int TY = threads / TX;
+  F.ntx = (G.nx + TX - 1) / TX;
+  F.nty = (G.ny + TY - 1) / TY;
+  F.ncols = F.ntx * F.nty;
+  F.pa = pa; F.pb = pb;
+  plan_chunks(F, pb - pa, G.zwrap, 2, nrep, pair_len);
+  F.sx = std::min(F.ntx, 4);      // strips of 4 tiles: +2 % at 512^3 (ntx = 8), identical at 256^3
   return TX;
 }
 
@@ -151,9 +148,9 @@ static inline hipError_t fused_launch(const double* S, double* D, const double* 
                                uint32_t noise_index, int mode, hipStream_t stream, int pair_len = 0) {
   FusedGrid F;
   const int TX = fused_plan(G, pa, pb, mode, pair_len, F);
-  const int TY = (BFLBM_FUSED_TX * BFLBM_FUSED_TY) / TX;
+  const int TY = (FUSED_TX * FUSED_TY) / TX;
   dim3 grid((unsigned)(F.per_xcd * 8)), block(TX * TY);
-  constexpr int TX0 = BFLBM_FUSED_TX, TY0 = BFLBM_FUSED_TY;
+  constexpr int TX0 = FUSED_TX, TY0 = FUSED_TY;
   if (mode == 2)      hipLaunchKernelGGL((k_fused<TX0, TY0, 2>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
   else if (mode == 1) hipLaunchKernelGGL((k_fused<TX0, TY0, 1>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
   else if (TX == 32)  hipLaunchKernelGGL((k_fused<32, (TX0 * TY0) / 32, 0>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);

@@ -33,13 +33,8 @@
   const unsigned xo[3] = { (unsigned)wrapx(x - 1) * 8u, (unsigned)x * 8u, (unsigned)wrapx(x + 1) * 8u };
   const unsigned yo[3] = { (unsigned)(wrapy(y - 1) * G.pitch) * 8u, (unsigned)(y * G.pitch) * 8u, (unsigned)(wrapy(y + 1) * G.pitch) * 8u };
   auto ld = [](const double* __restrict__ base, unsigned boff) { return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + boff); };
-#ifndef BFLBM_FUSED_NT_STORES
-#define BFLBM_FUSED_NT_STORES 0     // non-temporal population stores: +0.8 % at 256^3, -2.0 % at 512^3 in this kernel (profiles/r04_nt_hints.txt): off
-#endif
-  auto st = [](double* __restrict__ base, unsigned boff, double v) {
-    double* q = reinterpret_cast<double*>(reinterpret_cast<char*>(base) + boff);
-    if (BFLBM_FUSED_NT_STORES) __builtin_nontemporal_store(v, q); else *q = v;
-  };
+  // plain population stores (the non-temporal hint was +0.8 % at 256^3, -2.0 % at 512^3 in this kernel, profiles/r04_nt_hints.txt)
+  auto st = [](double* __restrict__ base, unsigned boff, double v) { *reinterpret_cast<double*>(reinterpret_cast<char*>(base) + boff) = v; };
   // ---- ring half-task of this thread: lanes 0..nper-1 of every wave; the lower half of the waves sums
   // fluid f, the upper half fluid g, so the fluid (and with it the load base) is wave-uniform
   const int nring = 2 * (aw + 2) + 2 * ah;
@@ -98,7 +93,7 @@
 #pragma unroll
       for (int i = 0; i < Q; ++i) {
         const double* __restrict__ b = pl[1 - Vel::cz[i]] + (long long)i * G.vol;
-        const unsigned o = oo[1 - Vel::cy[i]][1 + BFLBM_PX(Vel::cx[i])];
+        const unsigned o = oo[1 - Vel::cy[i]][1 - Vel::cx[i]];
         cf[i] = ld(b, o);
         cg[i] = ld(b + (long long)Q * G.vol, o);
       }
@@ -118,7 +113,7 @@
 #pragma unroll
       for (int i = 0; i < Q; ++i) {
         const double* __restrict__ b = pl[1 - Vel::cz[i]] + (long long)hfl * Q * G.vol + (long long)i * G.vol;
-        hv[i] = ld(b, ho[1 - Vel::cy[i]][1 + BFLBM_PX(Vel::cx[i])]);
+        hv[i] = ld(b, ho[1 - Vel::cy[i]][1 - Vel::cx[i]]);
       }
     } else {
 #pragma unroll
@@ -184,8 +179,6 @@
       double* __restrict__ Dp = D + (long long)pc * G.plane;
       unsigned o = yo[1] + xo[1];
       asm volatile("" : "+v"(o));
-      unsigned os3[3] = { yo[1] + xo[0], o, yo[1] + xo[2] };       // store slots of populations with c_x = -1, 0, +1 (BFLBM_XSHIFT)
-      if (BFLBM_XSHIFT) { asm volatile("" : "+v"(os3[0])); asm volatile("" : "+v"(os3[2])); }
       {
         SiteHydro Hy;
         SiteRecip R;
@@ -209,7 +202,7 @@
           double out[Q];
           d_populations(mf, out);
 #pragma unroll
-          for (int i = 0; i < Q; ++i) st(Dp + (long long)i * G.vol, os3[1 + BFLBM_SX(Vel::cx[i])], out[i]);
+          for (int i = 0; i < Q; ++i) st(Dp + (long long)i * G.vol, o, out[i]);
         }
         {
           if (MODE == 2) {
@@ -227,7 +220,7 @@
           double out[Q];
           d_populations(mg, out);
 #pragma unroll
-          for (int i = 0; i < Q; ++i) st(Dp + (long long)(i + Q) * G.vol, os3[1 + BFLBM_SX(Vel::cx[i])], out[i]);
+          for (int i = 0; i < Q; ++i) st(Dp + (long long)(i + Q) * G.vol, o, out[i]);
         }
       }
     }

@@ -46,35 +46,12 @@
 
 #include "bflbm_fused.h"
 
-// Requests of the next plane's f half (quiet kernel): one every BFLBM_HO_SPREAD_F VALU instructions of the relaxation of
-// fluid f instead of one burst of 19 before it; 0 = burst (see the comment at the call site)
-#ifndef BFLBM_HO_SPREAD_F
-#define BFLBM_HO_SPREAD_F 28
-#endif
-#ifndef BFLBM_HO_NT_STORES
-#define BFLBM_HO_NT_STORES 1
-#endif
-#ifndef BFLBM_HO_NT_LOADS
-#define BFLBM_HO_NT_LOADS 0
-#endif
-#ifndef BFLBM_HO_NT_FRAMES
-#define BFLBM_HO_NT_FRAMES 0     // experiment: the frame stores too
-#endif
-#ifndef BFLBM_HO_SPREAD_F1
-#define BFLBM_HO_SPREAD_F1 44     // noise kernel, round 4: with the 11-instruction normals one request every 44 VALU instructions is
-#endif                            // +2.3 % at 512^3 and +2.0 % at 256^3 (16 ... 32: -1 %, 56: 0, 68: +2.5 / +0.5 %); round 3's generator: every spacing lost
-
-
-// Diagnostic build (-DBFLBM_STAMP, tools/ho_stamps.py): shader-clock stamps at the phase boundaries of a march position,
-// written by lane 0 of every wave of ONE workgroup for 64 steady-state positions.  Not compiled into the product.
-#ifdef BFLBM_STAMP
-#define HO_NSTAMP 10
-#define HO_STAMP_POS 64
-__device__ unsigned long long g_ho_stamps[4 * HO_STAMP_POS * HO_NSTAMP];
-#define HO_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); ts[k] = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define HO_STAMP(k) do { } while (0)
-#endif
+// Requests of the next plane's f half in the steady state: one every HO_SPREAD_F VALU instructions of the relaxation of
+// fluid f instead of one burst of 19 before it (see the comment at the call site).  The noise kernel, round 4: with the
+// 11-instruction normals one request every 44 VALU instructions is +2.3 % at 512^3 and +2.0 % at 256^3 (16 ... 32: -1 %,
+// 56: 0, 68: +2.5 / +0.5 %); round 3's generator: every spacing lost.
+constexpr int HO_SPREAD_F = 28;      // quiet kernel
+constexpr int HO_SPREAD_F1 = 44;     // noise kernel
 
 template <int TY> struct HoLayout {
   static constexpr int TX = 64;
@@ -168,11 +145,7 @@ k_fused_ho(const double* __restrict__ S, double* __restrict__ D, Geo G, DevParam
   auto wrapx = [&](int v) { return v < 0 ? v + G.nx : (v >= G.nx ? v - G.nx : v); };
   auto wrapy = [&](int v) { return v < 0 ? v + G.ny : (v >= G.ny ? v - G.ny : v); };
   auto ld = [](const double* __restrict__ base, unsigned boff) { return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + boff); };
-  auto ldnt = [](const double* __restrict__ base, unsigned boff) { return __builtin_nontemporal_load(reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + boff)); };
-  auto st = [](double* __restrict__ base, unsigned boff, double v) {
-    double* q = reinterpret_cast<double*>(reinterpret_cast<char*>(base) + boff);
-    if (BFLBM_HO_NT_FRAMES) __builtin_nontemporal_store(v, q); else *q = v;
-  };
+  auto st = [](double* __restrict__ base, unsigned boff, double v) { *reinterpret_cast<double*>(reinterpret_cast<char*>(base) + boff) = v; };
 
   // active extent of this tile; idle lanes / rows of a ragged tile work on a duplicate of the last active site
   const int aw = RAG ? min(TX, G.nx - x0) : TX, ah = RAG ? min(TY, G.ny - y0) : TY;
@@ -296,12 +269,9 @@ k_fused_ho(const double* __restrict__ S, double* __restrict__ D, Geo G, DevParam
 #pragma unroll
       for (int i = 0; i < Q; ++i) {
         const double* __restrict__ b = pl[1 - Vel::cz[i]] + (long long)i * G.vol;
-        const unsigned o = oo[1 - Vel::cy[i]][1 + BFLBM_PX(Vel::cx[i])];
-        // BFLBM_HO_NT_LOADS: 1 = the populations that do not travel in x with the non-temporal hint (every one of their lines is read by
-        // exactly one tile, once; only the x-shifted row segments of the others share a line with the neighbouring tile), 2 = all of them
-        const bool nt = BFLBM_HO_NT_LOADS == 2 || (BFLBM_HO_NT_LOADS == 1 && Vel::cx[i] == 0);
-        if (which != 2) f[i] = nt ? ldnt(b, o) : ld(b, o);
-        if (which != 1) g[i] = nt ? ldnt(b + (long long)Q * G.vol, o) : ld(b + (long long)Q * G.vol, o);
+        const unsigned o = oo[1 - Vel::cy[i]][1 - Vel::cx[i]];
+        if (which != 2) f[i] = ld(b, o);
+        if (which != 1) g[i] = ld(b + (long long)Q * G.vol, o);
       }
     }
     if ((parts & 2) && which != 2 && Hg.use_frames && q >= fa && q <= fb && has_rtask) {
@@ -330,12 +300,8 @@ k_fused_ho(const double* __restrict__ S, double* __restrict__ D, Geo G, DevParam
   // vmcnt(0): the join with the paths that end in loads).
   auto position = [&](const int q, auto col_c, auto ldn_c) {
     constexpr bool do_collide = decltype(col_c)::value, load_next = decltype(ldn_c)::value;
-    // quiet kernel: the own loads of the f half are spread over the relaxation of f (below); the noise kernel keeps the burst
-    constexpr bool spread_f = do_collide && load_next && (MODE == 0 ? BFLBM_HO_SPREAD_F > 0 : BFLBM_HO_SPREAD_F1 > 0);
-#ifdef BFLBM_STAMP
-    unsigned long long ts[HO_NSTAMP] = {0};
-#endif
-    HO_STAMP(0);                                             // top of the position
+    // steady state: the own loads of the f half are spread over the relaxation of f (below)
+    constexpr bool spread_f = do_collide && load_next;
     const int slot = it & 3;
     const double* __restrict__ pl[3] = { S + (long long)wrapp(q - 1) * G.plane, S + (long long)wrapp(q) * G.plane,
                                          S + (long long)wrapp(q + 1) * G.plane };
@@ -378,7 +344,7 @@ k_fused_ho(const double* __restrict__ S, double* __restrict__ D, Geo G, DevParam
         double t[2][Q];
 #pragma unroll
         for (int i = 0; i < Q; ++i) {
-          unsigned o = hyo[1 - Vel::cy[i]] + hxo[1 + BFLBM_PX(Vel::cx[i])];
+          unsigned o = hyo[1 - Vel::cy[i]] + hxo[1 - Vel::cx[i]];
           asm volatile("" : "+v"(o));
           const double* __restrict__ b = pl[1 - Vel::cz[i]] + (long long)i * G.vol;
           t[0][i] = ld(b, o);
@@ -391,9 +357,7 @@ k_fused_ho(const double* __restrict__ S, double* __restrict__ D, Geo G, DevParam
         rp[slot][1][ry * LW + rx] = density(t[1]);
       }
     }
-    HO_STAMP(1);                                             // plane q arrived, densities summed
     __syncthreads();
-    HO_STAMP(2);                                             // barrier passed
     // frames of plane q-3: finished at the previous position, combined across rows now
     finish(q - 3, (it & 1) ^ 1);
     // 3. collide plane q-1
@@ -418,10 +382,8 @@ k_fused_ho(const double* __restrict__ S, double* __restrict__ D, Geo G, DevParam
     for (int i = 0; i < Q; ++i) gl[i][tid] = cg[i];
 #pragma unroll
     for (int i = 0; i < Q; ++i) fl[i][tid] = cf[i];
-    HO_STAMP(3);                                             // frames finished, held plane read as moments, new plane parked in LDS
     // the f half of the next plane: in flight while plane q-1 is collided
     if (load_next) pull_plane(q + 1, nf, ng, hvn, 1, spread_f ? 2 : 3);
-    HO_STAMP(4);                                             // f half of plane q+1 requested
     if (do_collide) {
       const int sl[3] = { (it - 2) & 3, (it - 1) & 3, it & 3 };
       const double r = rp[sl[1]][0][lown], ph = rp[sl[1]][1][lown];
@@ -444,8 +406,6 @@ k_fused_ho(const double* __restrict__ S, double* __restrict__ D, Geo G, DevParam
       double* __restrict__ Dp = D + (long long)pcw * G.plane;
       unsigned o = yo[1] + xo[1];
       asm volatile("" : "+v"(o));
-      unsigned os3[3] = { yo[1] + xo[0], o, yo[1] + xo[2] };       // store slots of populations with c_x = -1, 0, +1 (BFLBM_XSHIFT)
-      if (BFLBM_XSHIFT) { asm volatile("" : "+v"(os3[0])); asm volatile("" : "+v"(os3[2])); }
       SiteHydro Hy;
       SiteRecip R;
       d_site_recips(P, r, ph, R);
@@ -467,10 +427,7 @@ k_fused_ho(const double* __restrict__ S, double* __restrict__ D, Geo G, DevParam
         // population stores carry the non-temporal hint (round 4: +0.9 % at 512^3, +0.6 % at 256^3, +1.6 % with noise, runs agreeing to
         // 0.1 %: the written lines are not read again before the next step, the L2 keeps the neighbours' shared lines instead)
         auto put = [&](int i, double v) {
-          if (active) {
-            double* __restrict__ q = reinterpret_cast<double*>(reinterpret_cast<char*>(Dk + (long long)i * G.vol) + os3[1 + BFLBM_SX(Vel::cx[i])]);
-            if (BFLBM_HO_NT_STORES) __builtin_nontemporal_store(v, q); else *q = v;
-          }
+          if (active) __builtin_nontemporal_store(v, reinterpret_cast<double*>(reinterpret_cast<char*>(Dk + (long long)i * G.vol) + o));
         };
         // x shifts see zeros from the idle lanes of a narrow tile (they hold a duplicate of the last site)
         auto shr = [&](double v) { return ho_shr((RAG && !active_x) ? 0.0 : v); };
@@ -545,15 +502,15 @@ k_fused_ho(const double* __restrict__ S, double* __restrict__ D, Geo G, DevParam
           }
         }
       };
-      HO_STAMP(5);                                           // gradient, noise head, projection done
-      // Round 3 (tools/ho_stamps.py): a lone wave that issues its 19 requests as one burst stands at the issue for 2400 of
-      // the 18500 clocks of a position -- the burst is longer than the CU's request queue, and an in-order wave cannot
-      // compute while it waits for queue space.  In the quiet kernel the 19 own loads of the f half are therefore requested
-      // one every BFLBM_HO_SPREAD_F (28) VALU instructions of the relaxation of f; the order is pinned with
-      // sched_group_barrier (the compiler hoists independent loads to the top of the block otherwise).  512^3: 7817 ->
-      // 8484 and 8250 -> 8442 MLUPS on two boxes, 256^3 +2.5 %; spacings of 20 and 36 and all 38 loads spread were slower
-      // than the burst (NOTES.md section 3.1f).  The noise kernel: every spacing lost with round 3's generator; with round 4's
-      // (11 instructions per normal) one request every 44 instructions is +2 % at both sizes (profiles/r04_noise_generator_ab.txt).
+      // Round 3 (shader-clock stamps of the march phases): a lone wave that issues its 19 requests as one burst stands
+      // at the issue for 2400 of the 18500 clocks of a position -- the burst is longer than the CU's request queue, and
+      // an in-order wave cannot compute while it waits for queue space.  In the quiet kernel the 19 own loads of the f
+      // half are therefore requested one every HO_SPREAD_F (28) VALU instructions of the relaxation of f; the order is
+      // pinned with sched_group_barrier (the compiler hoists independent loads to the top of the block otherwise).
+      // 512^3: 7817 -> 8484 and 8250 -> 8442 MLUPS on two boxes, 256^3 +2.5 %; spacings of 20 and 36 and all 38 loads
+      // spread were slower than the burst (NOTES.md section 3.1f).  The noise kernel: every spacing lost with round 3's
+      // generator; with round 4's (11 instructions per normal) one request every 44 instructions is +2 % at both sizes
+      // (profiles/r04_noise_generator_ab.txt).
       if (spread_f) pull_plane(q + 1, nf, ng, hvn, 1, 1);
       if (MODE == 1) d_relax_generated(P, mf, r, v_b, Hy.uf, Hy.af, P.inv_tau_f_bar, fn3, NA.sr, ntab, rst, R.cs4);
       else           d_relax<false>(P, mf, r, v_b, Hy.uf, Hy.af, P.inv_tau_f_bar, zn, R.cs4);
@@ -561,24 +518,14 @@ k_fused_ho(const double* __restrict__ S, double* __restrict__ D, Geo G, DevParam
 #pragma unroll
         for (int s_ = 0; s_ < Q; ++s_) {
           __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                      // one vector-memory read,
-          __builtin_amdgcn_sched_group_barrier(0x002, MODE == 0 ? BFLBM_HO_SPREAD_F : BFLBM_HO_SPREAD_F1, 0);      // then this many VALU instructions
+          __builtin_amdgcn_sched_group_barrier(0x002, MODE == 0 ? HO_SPREAD_F : HO_SPREAD_F1, 0);      // then this many VALU instructions
         }
       }
-      HO_STAMP(6);                                           // fluid f relaxed
       finish_fluid(mf, 0);
       if (load_next) pull_plane(q + 1, nf, ng, hvn, 2);       // the g half of the next plane: spreads the requests over the march position (+2.9 % at 512^3)
-      HO_STAMP(7);                                           // f stored, frames produced, g half requested
       if (MODE == 1) d_relax_generated(P, mg, ph, v_b, Hy.ug, Hy.ag, P.inv_tau_g_bar, gn3, NA.sp, ntab, rst, R.cs4);
       else           d_relax<false>(P, mg, ph, v_b, Hy.ug, Hy.ag, P.inv_tau_g_bar, zn, R.cs4);
-      HO_STAMP(8);                                           // fluid g relaxed
       finish_fluid(mg, 1);
-      HO_STAMP(9);                                           // g stored
-#ifdef BFLBM_STAMP
-      if (blockIdx.x == (gridDim.x > 777u ? 777u : gridDim.x / 2u + 1u) && it >= 40 && it < 40 + HO_STAMP_POS && lane == 0) {
-#pragma unroll
-        for (int k = 0; k < HO_NSTAMP; ++k) g_ho_stamps[((it - 40) * 4 + ty) * HO_NSTAMP + k] = ts[k];
-      }
-#endif
     } else if (load_next) {
       // the first two positions of a chunk collide nothing: the g half goes now, and is waited for here (as in
       // the prologue: keeps vmcnt(0) out of the loop head)
@@ -599,72 +546,37 @@ k_fused_ho(const double* __restrict__ S, double* __restrict__ D, Geo G, DevParam
   finish(qb - 2, (it & 1) ^ 1);
 }
 
-#ifndef BFLBM_HO_TY
-#define BFLBM_HO_TY 4
-#endif
+constexpr int HO_TY = 4;   // tile height of the hand-over kernel (tiles are 64 x HO_TY)
 
 // lattices the hand-over kernel takes: at least one whole tile; a narrower last tile column / lower last tile row needs
 // two lanes / rows (a ring site owned by a tile ONE site wide or high also collects from the tile beyond it, which the
 // 3 x 3 lookup of the consumer does not reach, and its two edge roles must be different lanes / rows)
 static inline bool handover_ok(const Geo& G) {
-  constexpr int TY = BFLBM_HO_TY;
-  return G.nx >= 64 && G.nx % 64 != 1 && G.ny >= TY && G.ny % TY != 1;
+  return G.nx >= 64 && G.nx % 64 != 1 && G.ny >= HO_TY && G.ny % HO_TY != 1;
 }
-static inline bool handover_ragged(const Geo& G) { return G.nx % 64 != 0 || G.ny % BFLBM_HO_TY != 0; }
+static inline bool handover_ragged(const Geo& G) { return G.nx % 64 != 0 || G.ny % HO_TY != 0; }
 static inline size_t handover_frame_doubles(const Geo& G) {
-  constexpr int TY = BFLBM_HO_TY;
-  return (size_t)((G.nx + 63) / 64) * (size_t)((G.ny + TY - 1) / TY) * HoLayout<TY>::REC * (size_t)G.nzs;
+  return (size_t)((G.nx + 63) / 64) * (size_t)((G.ny + HO_TY - 1) / HO_TY) * HoLayout<HO_TY>::REC * (size_t)G.nzs;
 }
 
 struct HoSig { int pa = -1, pb = -1, lz = -1, nchunks = -1, cstride = -1; long long step = -1;
   bool same_geometry(const HoSig& o) const { return pa == o.pa && pb == o.pb && lz == o.lz && nchunks == o.nchunks && cstride == o.cstride; } };
 
-// Chunking and workgroup order of one launch over the storage planes [pa, pb) (pair_len > 0: the two boundary plane
-// pairs of a slab, one chunk each).  One workgroup is resident per CU, so a launch runs in rounds of `slots` workgroups
-// and costs about rounds x (planes per chunk + 1) march positions; the chunk count minimises that.  Round 4 scanned the
-// chunk count at 256^3 ... 512^3 on two boxes (profiles/r04_chunk_scan.txt): a model fitted on the first box
-// ((rounds + tail) x (planes + 4): 448^3 +5 % with 7 chunks, 512^3 +5 % with 4) changed nothing on the second (every
-// lattice within the +-2 % process-to-process scatter, 512x512x128 2 % SLOWER with its choice), so the rule stays.
+// Tiles, chunking and workgroup order of one launch over the storage planes [pa, pb) (pair_len: see plan_chunks)
 static inline void handover_plan(const Geo& G, int pa, int pb, int pair_len, FusedGrid& F) {
-  constexpr int TX = 64, TY = BFLBM_HO_TY;
+  constexpr int TX = 64, TY = HO_TY;
   F.ntx = (G.nx + TX - 1) / TX; F.nty = (G.ny + TY - 1) / TY;
   F.ncols = F.ntx * F.nty;
   F.pa = pa; F.pb = pb;
-  const int np = pb - pa;
-  static const int want_env = [] { const char* e = getenv("BFLBM_FUSED_WG"); return e ? atoi(e) : 0; }();
-  const int slots = g_fused_ncu > 0 ? g_fused_ncu : 256;        // one workgroup per CU
-  static const int min_slab_rounds = [] { const char* e = getenv("BFLBM_SLAB_ROUNDS"); return e && atoi(e) > 0 ? atoi(e) : 3; }();
-  F.row0 = 0;
-  const int maxchunks = std::max(1, np / 4);                     // a chunk shorter than 4 planes has no complete frame
-  int nchunks;
-  if (want_env > 0) {
-    nchunks = std::min(maxchunks, std::max(1, (want_env + F.ncols - 1) / F.ncols));
-  } else {
-    long long best = -1; nchunks = 1;
-    for (int k = 1; k <= maxchunks; ++k) {
-      const int lz = (np + k - 1) / k, chunks = (np + lz - 1) / lz;
-      if (chunks != k) continue;
-      if (G.zwrap && lz > 256 && k < maxchunks) continue;   // one 512-plane march per column was A/B-tested: -1 %
-      const long long total = (long long)F.ncols * chunks, rounds = (total + slots - 1) / slots;
-      if (!G.zwrap && rounds < min_slab_rounds && k < maxchunks) continue;
-      const long long cost = rounds * (lz + 1);
-      if (best < 0 || cost < best) { best = cost; nchunks = k; }
-    }
-  }
-  F.lz = (np + nchunks - 1) / nchunks;
-  F.nchunks = (np + F.lz - 1) / F.lz;
-  F.cstride = F.lz;
-  if (pair_len > 0 && np > 2 * pair_len) { F.lz = pair_len; F.nchunks = 2; F.cstride = np - pair_len; }
-  F.total = F.ncols * F.nchunks;
-  F.per_xcd = (F.total + 7) / 8;
-  { static const int sx_env = [] { const char* e = getenv("BFLBM_MAP_SX"); return e ? atoi(e) : 0; }(); F.sx = sx_env > 0 ? sx_env : F.ntx; }
+  plan_chunks(F, pb - pa, G.zwrap, 4, 1, pair_len);       // a chunk shorter than 4 planes has no complete frame
+  F.sx = F.ntx;
 }
 
 // fin/fout: frame buffers of the state read / written.  sig_in: what wrote fin (step == steps-1 required);
 // sig_out receives this launch.  returns the launch's error code
 static inline hipError_t handover_launch(const double* S, double* D, const double* fin, double* fout, const Geo& G, const DevParams& P,
                                   int pa, int pb, long long steps, const HoSig& sig_in, HoSig& sig_out, hipStream_t stream, int pair_len = 0, int mode = 0) {
-  constexpr int TX = 64, TY = BFLBM_HO_TY;
+  constexpr int TX = 64, TY = HO_TY;
   FusedGrid F;
   handover_plan(G, pa, pb, pair_len, F);
   sig_out.pa = pa; sig_out.pb = pb; sig_out.lz = F.lz; sig_out.nchunks = F.nchunks; sig_out.cstride = F.cstride; sig_out.step = steps;
@@ -674,8 +586,7 @@ static inline hipError_t handover_launch(const double* S, double* D, const doubl
   Hg.use_frames = (sig_in.step == steps - 1 && sig_in.same_geometry(sig_out)) ? 1 : 0;
   dim3 grid((unsigned)(F.per_xcd * 8)), block(TX * TY);
   const uint32_t nidx = (uint32_t)steps;
-  static const bool force_rag = [] { const char* e = getenv("BFLBM_FORCE_RAG"); return e && atoi(e) != 0; }();   // diagnostics: what the ragged-tile code costs on full tiles
-  const bool rag = handover_ragged(G) || force_rag;
+  const bool rag = handover_ragged(G);
   if (mode == 1) { if (rag) hipLaunchKernelGGL((k_fused_ho<TY, 1, true>), grid, block, 0, stream, S, D, G, P, F, Hg, nidx);
                    else     hipLaunchKernelGGL((k_fused_ho<TY, 1, false>), grid, block, 0, stream, S, D, G, P, F, Hg, nidx); }
   else           { if (rag) hipLaunchKernelGGL((k_fused_ho<TY, 0, true>), grid, block, 0, stream, S, D, G, P, F, Hg, nidx);

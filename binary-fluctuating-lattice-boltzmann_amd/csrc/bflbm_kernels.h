@@ -12,16 +12,6 @@
 
 #include "bflbm_site.h"
 
-// Layout of the x direction.  BFLBM_XSHIFT 1 ("half-streamed"): population i of logical site x is stored at x + c_ix
-// (periodic), i.e. it is streamed in x when it is STORED and in y,z when it is pulled: every pull reads x-aligned row
-// segments (the line of the neighbouring tile that an x-shifted segment touches was 9 % of the reads) and
-// every store of a population with c_ix != 0 is shifted by one element instead.  Pure data movement: the same doubles.
-#ifndef BFLBM_XSHIFT
-#define BFLBM_XSHIFT 0
-#endif
-#define BFLBM_PX(cx) (BFLBM_XSHIFT ? 0 : -(cx))      /* x displacement of the pull of a population with c_x = cx */
-#define BFLBM_SX(cx) (BFLBM_XSHIFT ? (cx) : 0)       /* x displacement of its store */
-
 struct Geo {
   int nx, ny, nzs;     // storage extent (nzs includes the halo planes)
   int zwrap;           // 1: plane neighbours wrap modulo nzs (single slab)
@@ -69,19 +59,16 @@ __device__ __forceinline__ long long nb_off(const SiteIdx& I, int dx, int dy, in
   return I.row[dz+1][dy+1] + xx;
 }
 
-#ifndef BFLBM_COLLIDE_NT_STORES
-#define BFLBM_COLLIDE_NT_STORES 0   // non-temporal population stores in k_collide: +3.7 % at 32^3, +1 ... -2 % elsewhere (profiles/r04_nt_hints.txt): off
-#endif
-__device__ __forceinline__ void st_pop(double* __restrict__ base, unsigned boff, double v) {   // population stores of k_collide
-  double* q = reinterpret_cast<double*>(reinterpret_cast<char*>(base) + boff);
-  if (BFLBM_COLLIDE_NT_STORES) __builtin_nontemporal_store(v, q); else *q = v;
+// population stores of k_collide: plain (the non-temporal hint was +3.7 % at 32^3, +1 ... -2 % elsewhere, profiles/r04_nt_hints.txt)
+__device__ __forceinline__ void st_pop(double* __restrict__ base, unsigned boff, double v) {
+  *reinterpret_cast<double*>(reinterpret_cast<char*>(base) + boff) = v;
 }
 // f_i(x) = S_i(x - c_i)
 __device__ __forceinline__ void pull_site(const double* __restrict__ S, const Geo& G, const SiteIdx& I,
                                           double (&fs)[Q], double (&gs)[Q]) {
 #pragma unroll
   for (int i = 0; i < Q; ++i) {
-    const long long o = nb_off(I, BFLBM_PX(Vel::cx[i]), -Vel::cy[i], -Vel::cz[i]);
+    const long long o = nb_off(I, -Vel::cx[i], -Vel::cy[i], -Vel::cz[i]);
     fs[i] = S[(long long)i*G.vol + o];
     gs[i] = S[(long long)(i+Q)*G.vol + o];
   }
@@ -157,7 +144,7 @@ __device__ __forceinline__ void pull_site(const double* __restrict__ S, const Ge
 #pragma unroll
   for (int i = 0; i < Q; ++i) {
     const double* __restrict__ b = S + (long long)i*G.vol + I.pl[1 - Vel::cz[i]];
-    const unsigned o = I.o[1 - Vel::cy[i]][1 + BFLBM_PX(Vel::cx[i])];
+    const unsigned o = I.o[1 - Vel::cy[i]][1 - Vel::cx[i]];
     fs[i] = ld_sb(b, o);
     gs[i] = ld_sb(b + (long long)Q*G.vol, o);
   }
@@ -219,11 +206,9 @@ __global__ void __launch_bounds__(256) k_density_streamed(const double* __restri
 }
 
 // ---- pass B: pull, project (hydrovars), draw noise, collide, store post-collision state
-#ifndef BFLBM_COLLIDE_WAVES
-#define BFLBM_COLLIDE_WAVES 2
-#endif
+constexpr int COLLIDE_WAVES = 2;   // waves per SIMD of the two-pass collide kernels
 template <bool NOISE, bool INJECT>
-__global__ void __launch_bounds__(256, BFLBM_COLLIDE_WAVES) k_collide(const double* __restrict__ S, double* __restrict__ D,
+__global__ void __launch_bounds__(256, COLLIDE_WAVES) k_collide(const double* __restrict__ S, double* __restrict__ D,
                                                  const double* __restrict__ rho, const double* __restrict__ phi,
                                                  const double* __restrict__ injf, const double* __restrict__ injg,
                                                  Geo G, DevParams P, int p0, uint32_t noise_index, RefState Rf) {
@@ -251,7 +236,7 @@ __global__ void __launch_bounds__(256) k_unstream(const double* __restrict__ N, 
   const long long o = I.row[1][1] + x;
 #pragma unroll
   for (int i = 0; i < Q; ++i) {
-    const long long src = nb_off(I, BFLBM_XSHIFT ? 0 : Vel::cx[i], Vel::cy[i], Vel::cz[i]);   // the slot of site x - c_x: N_i there + c_i
+    const long long src = nb_off(I, Vel::cx[i], Vel::cy[i], Vel::cz[i]);   // the slot of site x + c_i
     S[(long long)i*G.vol + o] = N[(long long)i*G.vol + src];
     S[(long long)(i+Q)*G.vol + o] = N[(long long)(i+Q)*G.vol + src];
   }
@@ -276,7 +261,7 @@ __global__ void __launch_bounds__(256) k_init(double* __restrict__ S, const doub
       const int pe = p + 1 + Vel::cz[i];
       if (mode == 1) r = rho_ext[pe];
       else {
-        const int xx = BFLBM_XSHIFT ? x : (Vel::cx[i] > 0 ? xp : (Vel::cx[i] < 0 ? xm : x));
+        const int xx = Vel::cx[i] > 0 ? xp : (Vel::cx[i] < 0 ? xm : x);
         const int yy = Vel::cy[i] > 0 ? yp : (Vel::cy[i] < 0 ? ym : y);
         r = rho_ext[(long long)pe*G.dplane + (long long)yy*G.nx + xx];
       }

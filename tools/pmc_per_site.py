@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Per-site counter table of tools/round4/r4_pmc_sizes.sh: one row per lattice, counters of the step's kernel (k_fused_ho) divided by
-the sites one launch updates.  FETCH_SIZE is doubled (gfx950 tallies 128-byte requests at 64 B: /opt/skills/guides/
-MI355X_MICROARCH.md, HBM section), both sizes are KiB.  usage: pmc_per_site.py gpurun_out/r4_pmc_sizes"""
+"""Per-site counter table of a counter run over several lattices (ROOT/<nx>x<ny>x<nz>/pmc_summary.txt): one row per
+lattice, counters of the step's kernel (k_fused_ho) divided by the sites one launch updates.  FETCH_SIZE is doubled (gfx950
+tallies 128-byte requests at 64 B), both sizes are KiB.
+usage: pmc_per_site.py ROOT"""
 import glob, json, os, re, sys
 root = sys.argv[1]
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
