@@ -31,10 +31,10 @@ int fail(const char* fmt, ...) {
 }
 
 // calls a replica view of a batch refuses (include/bflbm.h, "Replica batch")
-#define BFLBM_REFUSE_VIEW(c, call, instead)                                                   \
-  do {                                                                                        \
-    if ((c)->batch) return fail("%s: the context is a replica of a batch; %s", call, instead); \
-  } while (0)
+#define BFLBM_REFUSE_VIEW(c, call, instead) do { if ((c)->batch) return fail("%s: the context is a replica of a batch; %s", call, instead); } while (0)
+
+// calls that would change what the open step runs (include/bflbm.h, bflbm_step_boundary)
+#define BFLBM_REFUSE_OPEN_STEP(c, call) do { if ((c)->step_open()) return fail("%s inside an open step", call); } while (0)
 
 #define HIP_TRY(expr)                                                                         \
   do {                                                                                        \
@@ -98,7 +98,7 @@ struct bflbm_ctx {
   double* phi = nullptr;
   double* injf = nullptr;
   double* injg = nullptr;
-  bool inject = false;
+  bool inject = false;           // injg / injf feed the next step instead of generated noise
   double* partial = nullptr;
   size_t partial_n = 0;
   hipStream_t stream = nullptr;
@@ -109,7 +109,8 @@ struct bflbm_ctx {
   double* frames[2] = {nullptr, nullptr};   // schedule 3: tile-boundary density frames of S[0], S[1] (bflbm_handover.h)
   bool frames_unavailable = false;          // their allocation failed once: auto stays on the bit-exact schedules
   HoSig fsig[2][2];              // [state buffer][0 interior sweep, 1 boundary pairs]: the launch that wrote the frames
-  bool step_open = false;
+  int step_sch = -1;             // the schedule bflbm_step_boundary resolved for the open step; -1: no step is open
+  bool step_open() const { return step_sch >= 0; }
   double total_max = -1.;        // largest |rho + phi| of the state an upload made resident (< 0: analytic init, the parameters say it)
   float tune_ms[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // bflbm_tune_placement: step time of every candidate allocation tried, and which was kept
   int tune_n = 0, tune_kept = 0;
@@ -124,7 +125,8 @@ struct bflbm_ctx {
   double com[3] = {0., 0., 0.}; // global centre of mass (update_com) of the resident state
   bool com_valid = false;
   bflbm_batch* batch = nullptr; // non-null: a replica view owned by this batch (bflbm_batch_replica)
-  bool batch_dirty = false;     // its parameters changed since the batch last wrote its device record
+  bool record_stale = true;     // a view: its batch record (parameters, buffers, step counter) must be written again
+  // what describes the resident state, and what was derived from it, is reset by the transitions below (state_replaced ...)
 };
 
 namespace {
@@ -209,8 +211,10 @@ int launch_handover(bflbm_ctx* c, int pa, int pb, int pair_len = 0) {
   if (pb <= pa) return 0;
   if (ensure_frames(c)) return 1;
   const int kind = pair_len > 0 ? 1 : 0;
+  HoSig sig;
   const hipError_t e = handover_launch(c->S[c->cur], c->S[1 - c->cur], c->frames[c->cur], c->frames[1 - c->cur], c->G, c->dp, pa, pb,
-                                       c->steps, c->fsig[c->cur][kind], c->fsig[1 - c->cur][kind], c->stream, pair_len, c->dp.noise_on ? 1 : 0);
+                                       c->steps, c->fsig[c->cur][kind], sig, c->stream, pair_len, c->dp.noise_on ? 1 : 0);
+  c->fsig[1 - c->cur][kind] = (e == hipSuccess) ? sig : HoSig();     // frames are valid only where a launch wrote them
   return e != hipSuccess ? fail("hand-over launch failed: %s", hipGetErrorString(e)) : 0;
 }
 
@@ -300,6 +304,51 @@ int ensure_density(bflbm_ctx* c) {
   c->density_valid = true;
   return 0;
 }
+
+// The frames policy: allocates the frames the next step needs and returns the schedule it runs.  `auto` whose frames do
+// not fit remembers it and resolves to a bit-exact schedule; an explicit schedule 3 stays 3, and where `loud` (at the step,
+// before it is opened) reports the failure by returning -1: the caller may switch to an exact schedule and go on.
+int frames_for_next_step(bflbm_ctx* c, bool loud) {
+  const int sch = resolved_schedule(c);
+  const bool report = loud && c->schedule == 3;
+  if (sch != 3 || !ensure_frames(c, !report)) return sch;
+  return report ? -1 : resolved_schedule(c);
+}
+
+// ---- transitions of the resident state ----------------------------------------------------------------------------
+// A new state is resident: an analytic init, an upload, or none (ref_kind < 0: the zeroed buffers the placement probe
+// leaves).  The frames are allocated here rather than inside its first (possibly timed or overlapped) step.
+void state_replaced(bflbm_ctx* c, long long steps, int ref_kind, double total_max) {
+  c->steps = steps; c->total_max = total_max;
+  c->ref_kind = std::max(ref_kind, 0); c->ref_kind_step = ref_kind < 0 ? -1 : steps;
+  c->step_sch = -1;
+  c->density_valid = false; c->com_valid = false;
+  for (auto& b : c->fsig) for (auto& sg : b) sg = HoSig();     // the frames describe another state
+  c->record_stale = true;
+  (void)frames_for_next_step(c, false);
+}
+
+// The open step is complete.  A batch view's record stays valid: the kernels derive buffer and noise index from k.
+void state_advanced(bflbm_ctx* c) {
+  c->cur = 1 - c->cur; c->steps += 1;
+  c->step_sch = -1;
+  c->density_valid = false; c->com_valid = false;
+  c->inject = false;                             // injected noise feeds exactly one step
+}
+
+// The counter (the noise index of the next step) moves, the state stays; frames are keyed by the step that wrote them.
+void step_count_moved(bflbm_ctx* c, long long n) {
+  if (c->ref_kind_step == c->steps) c->ref_kind_step = n;
+  c->steps = n;
+  for (auto& b : c->fsig) for (auto& sg : b) sg = HoSig();
+  c->record_stale = true;
+}
+
+// Halo planes of the resident state were written (or, in the diagnostic timer, rho / phi themselves).
+void halos_written(bflbm_ctx* c) { c->density_valid = false; }
+
+// A boundary or interior sweep failed: the step closes with S[cur] intact (it may be retried); no frame of S[1-cur] is valid.
+int sweep_failed(bflbm_ctx* c) { c->step_sch = -1; for (auto& sg : c->fsig[1 - c->cur]) sg = HoSig(); return 1; }
 
 // One sweep of the resolved schedule sch (0 two-pass, 1 fused, 3 hand-over) over the storage planes [pa, pb).
 // pair_len > 0: only the boundary plane pairs [pa, pa+pair_len) and [pb-pair_len, pb) of a slab; the plane-marching
@@ -543,7 +592,7 @@ static int probe_ms(bflbm_ctx* c, float* ms) {
 int bflbm_tune_placement(bflbm_ctx* c, int max_candidates, float* ms_per_step, int* kept) {
   if (!c) return fail("null context");
   BFLBM_REFUSE_VIEW(c, "bflbm_tune_placement", "batches do no placement tuning (bflbm_batch_create)");
-  if (c->step_open) return fail("bflbm_tune_placement inside an open step");
+  BFLBM_REFUSE_OPEN_STEP(c, "bflbm_tune_placement");
   if (max_candidates < 1 || max_candidates > 8) return fail("max_candidates must be 1 ... 8");
   HIP_TRY(hipSetDevice(c->dom.device));
   const Geo& G = c->G;
@@ -555,9 +604,7 @@ int bflbm_tune_placement(bflbm_ctx* c, int max_candidates, float* ms_per_step, i
     const size_t bytes_now = (sdoubles + (size_t)(c->S[1] - c->S[0])) * sizeof(double);
     HIP_TRY(hipMemsetAsync(c->S[0], 0, bytes_now, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->cur = 0; c->steps = 0; c->density_valid = false; c->step_open = false; c->com_valid = false; c->total_max = -1.;
-    c->ref_kind = 0; c->ref_kind_step = -1;
-    for (auto& b : c->fsig) for (auto& sg : b) sg = HoSig();
+    c->cur = 0; state_replaced(c, 0, -1, -1.);
     return 0;
   };
   float best_ms = 0.f;
@@ -627,9 +674,10 @@ int bflbm_destroy(bflbm_ctx* c) {
 
 int bflbm_set_params(bflbm_ctx* c, const bflbm_params* p) {
   if (!c || !p) return fail("null argument");
+  BFLBM_REFUSE_OPEN_STEP(c, "bflbm_set_params");
   c->prm = *p;
   derive(c->prm, c->dp);
-  c->batch_dirty = true;                         // a replica view: the batch rewrites its record before the next step
+  c->record_stale = true;                        // a replica view: the batch rewrites its record before the next step
   return 0;
 }
 int bflbm_get_params(const bflbm_ctx* c, bflbm_params* p) {
@@ -663,27 +711,22 @@ int bflbm_resolved_schedule(const bflbm_ctx* c, int* schedule) {
 int bflbm_set_schedule(bflbm_ctx* c, int schedule) {
   if (!c) return fail("null context");
   BFLBM_REFUSE_VIEW(c, "bflbm_set_schedule", "use bflbm_batch_set_schedule");
+  BFLBM_REFUSE_OPEN_STEP(c, "bflbm_set_schedule");
   if (schedule < 0 || schedule > 3) return fail("unknown schedule %d", schedule);
   c->schedule = schedule;
   return 0;
 }
 
 // ---- initial conditions ---------------------------------------------------------------
-static int run_init(bflbm_ctx* c, int mode, const double* rho_ext_host, size_t n_ext, double rho_c, double phi_c, double rho_t) {
+// total_max: what `auto` keys its stability bound on, < 0 where rho + phi = rho_hi + rho_lo at every site
+static int run_init(bflbm_ctx* c, int mode, const double* rho_ext_host, size_t n_ext, double rho_c, double phi_c, double rho_t, double total_max) {
   HIP_TRY(hipSetDevice(c->dom.device));
   double* scratch = c->S[1 - c->cur];
   if (mode != 0) HIP_TRY(hipMemcpyAsync(scratch, rho_ext_host, n_ext * sizeof(double), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_init, plane_grid(c, c->G.nzs), dim3(256), 0, c->stream, c->S[c->cur], scratch, c->G, mode, rho_c, phi_c, rho_t, 0);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->steps = 0; c->density_valid = false; c->step_open = false; c->com_valid = false;
-  c->total_max = -1.;                              // rho + phi = rho_hi + rho_lo at every site
-  for (auto& b : c->fsig) for (auto& sg : b) sg = HoSig();     // the hand-over frames describe another state
-  // the frames of schedule 3 are allocated here, where a run starts, rather than inside its first (possibly timed or
-  // overlapped) step; a failure is remembered and `auto` stays bit-exact (an explicit schedule 3 reports it at the step)
-  if ((c->schedule == 2 || c->schedule == 3) && resolved_schedule(c) == 3) (void)ensure_frames(c, true);
-  c->ref_kind = (mode == 0) ? 2 : 1;             // thermal_noise gets the absolute COM (:623-625) or zero (:690, :739)
-  c->ref_kind_step = 0;
+  state_replaced(c, 0, (mode == 0) ? 2 : 1, total_max);   // thermal_noise gets the absolute COM (:623-625) or zero (:690, :739)
   return 0;
 }
 
@@ -698,11 +741,9 @@ static inline int ext_global_z(const bflbm_ctx* c, int pe) {
 int bflbm_init_mixture(bflbm_ctx* c) {
   if (!c) return fail("null context");
   const double C1 = 0.5, C2 = 0.5;               // LBM_binary.H:606-614
-  if (run_init(c, 0, nullptr, 0, 2. * C1, 2. * C2, 0.)) return 1;
   // rho = phi = 1 at every site whatever rho_hi / rho_lo say (:613-614): the total density `auto` keys its stability bound on is 2
   // (alpha0 = 4 on this state is NaN within 50 steps on the reference's CPU path, tests/test_oracle_pins.py)
-  c->total_max = 2. * C1 + 2. * C2;
-  return 0;
+  return run_init(c, 0, nullptr, 0, 2. * C1, 2. * C2, 0., 2. * C1 + 2. * C2);
 }
 
 int bflbm_init_stripe(bflbm_ctx* c, double frac) {
@@ -718,7 +759,7 @@ int bflbm_init_stripe(bflbm_ctx* c, double frac) {
     const double pos = z - nz / 2;
     tab[pe] = (P.rho_hi - P.rho_lo) * 0.5 * (std::tanh((pos - pos_lo) / std::sqrt(P.kappa)) + std::tanh((pos_hi - pos) / std::sqrt(P.kappa))) + P.rho_lo;
   }
-  return run_init(c, 1, tab.data(), tab.size(), 0., 0., rho_t);
+  return run_init(c, 1, tab.data(), tab.size(), 0., 0., rho_t, -1.);
 }
 
 int bflbm_init_droplet(bflbm_ctx* c, double r_frac) {
@@ -753,7 +794,7 @@ int bflbm_init_droplet(bflbm_ctx* c, double r_frac) {
     if (pb > pa) th.emplace_back(work, pa, pb);
   }
   for (auto& t : th) t.join();
-  return run_init(c, 2, fld.data(), fld.size(), 0., 0., rho_t);
+  return run_init(c, 2, fld.data(), fld.size(), 0., 0., rho_t, -1.);
 }
 
 // ---- upload / download ----------------------------------------------------------------
@@ -772,14 +813,12 @@ int bflbm_commit_upload(bflbm_ctx* c, int reset) {
   hipLaunchKernelGGL(k_unstream, plane_grid(c, c->nzl), dim3(256), 0, c->stream, c->S[1 - c->cur], c->S[c->cur], c->G, own_lo(c));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (reset) c->steps = 0;
-  c->density_valid = false; c->step_open = false; c->com_valid = false;
-  for (auto& b : c->fsig) for (auto& sg : b) sg = HoSig();
-  c->ref_kind = 0; c->ref_kind_step = c->steps;  // LBM_init: COM relative to com_ref (:651-654)
   // what `auto` keys its stability bound on from here on: the total density the upload made resident, not rho_hi/rho_lo
   // (handover_contract_params).  The own planes' densities need no halo (the upload buffer holds the streamed populations
   // of every own site), so the slab reduces its own maximum; a ring combines the slabs' (bflbm_ring_commit_upload).
-  {
+  // A NaN in the upload, or a failed reduction: never schedule 3.
+  double m = std::numeric_limits<double>::infinity();
+  const int rc = [&]() -> int {
     const int lo = own_lo(c);
     hipLaunchKernelGGL(k_density_streamed, plane_grid(c, c->nzl), dim3(256), 0, c->stream, c->S[1 - c->cur], c->rho, c->phi, c->G, lo);
     hipLaunchKernelGGL(k_total_absmax, plane_grid(c, c->nzl), dim3(256), 0, c->stream, c->rho, c->phi, c->partial, c->G, lo);
@@ -787,12 +826,13 @@ int bflbm_commit_upload(bflbm_ctx* c, int reset) {
     std::vector<double> h(c->partial_n);
     HIP_TRY(hipMemcpyAsync(h.data(), c->partial, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    double m = 0.;
-    for (double v : h) m = (v != v || m != m) ? (m + v) : std::max(m, v);
-    c->total_max = (m == m) ? m : std::numeric_limits<double>::infinity();     // NaN in the upload: never schedule 3
-  }
-  if ((c->schedule == 2 || c->schedule == 3) && resolved_schedule(c) == 3) (void)ensure_frames(c, true);   // as after the analytic inits
-  return 0;
+    double v_max = 0.;
+    for (double v : h) v_max = (v != v || v_max != v_max) ? (v_max + v) : std::max(v_max, v);
+    if (v_max == v_max) m = v_max;
+    return 0;
+  }();
+  state_replaced(c, reset ? 0 : c->steps, 0, m);   // LBM_init: COM relative to com_ref (:651-654)
+  return rc;
 }
 
 // the total-density bound of `auto` (see handover_contract_params): < 0 = from the parameters
@@ -803,13 +843,14 @@ int bflbm_state_total_max(const bflbm_ctx* c, double* total_max) {
 }
 int bflbm_set_state_total_max(bflbm_ctx* c, double total_max) {      // a driver that owns several slabs hands every slab the global maximum
   if (!c) return fail("null context");
+  BFLBM_REFUSE_OPEN_STEP(c, "bflbm_set_state_total_max");
   c->total_max = total_max;
   return 0;
 }
 
 int bflbm_download_fg(bflbm_ctx* c, double* f, double* g, const bflbm_fab* box) {
   if (!c || !f || !g) return fail("null argument");
-  if (c->step_open) return fail("download inside an open step");
+  if (c->step_open()) return fail("download inside an open step");
   HIP_TRY(hipSetDevice(c->dom.device));
   double* N = c->S[1 - c->cur];
   hipLaunchKernelGGL(k_pull, plane_grid(c, c->nzl), dim3(256), 0, c->stream, c->S[c->cur], N, c->G, own_lo(c));
@@ -824,43 +865,31 @@ static int prepare_ref(bflbm_ctx* c);
 int bflbm_step_boundary(bflbm_ctx* c) {
   if (!c) return fail("null context");
   BFLBM_REFUSE_VIEW(c, "bflbm_step_boundary", "use bflbm_batch_step");
-  if (c->step_open) return fail("step already open");
+  if (c->step_open()) return fail("step already open");
   HIP_TRY(hipSetDevice(c->dom.device));
   if (prepare_ref(c)) return 1;
-  if (c->schedule == 2 && resolved_schedule(c) == 3) (void)ensure_frames(c, true);   // auto: falls back when they do not fit
-  // an explicit schedule 3 whose frames cannot be allocated fails HERE, before the step is opened: nothing of the resident
-  // state has been touched and the caller may switch to an exact schedule and go on
-  if (c->schedule == 3 && resolved_schedule(c) == 3 && ensure_frames(c)) return 1;
-  c->step_open = true;
-  const int lo = own_lo(c), hi = own_hi(c);
+  const int sch = frames_for_next_step(c, true);
+  if (sch < 0) return 1;
+  c->step_sch = sch;                             // the step runs sch to its end: what could change it is refused until then
   if (c->G.zwrap) return 0;                      // single slab: everything is "interior"
-  const int rc = launch_sweep(c, resolved_schedule(c), lo, hi, 2);
-  if (rc) c->step_open = false;                  // a failed launch wrote nothing that the resident state S[cur] holds
-  return rc;
+  return launch_sweep(c, sch, own_lo(c), own_hi(c), 2) ? sweep_failed(c) : 0;
 }
 
 int bflbm_step_interior(bflbm_ctx* c) {
   if (!c) return fail("null context");
   BFLBM_REFUSE_VIEW(c, "bflbm_step_interior", "use bflbm_batch_step");
-  if (!c->step_open) return fail("bflbm_step_interior: call bflbm_step_boundary first");
+  if (!c->step_open()) return fail("bflbm_step_interior: call bflbm_step_boundary first");
   HIP_TRY(hipSetDevice(c->dom.device));
   const int lo = own_lo(c), hi = own_hi(c);
   const int a = c->G.zwrap ? lo : lo + 2, b = c->G.zwrap ? hi : hi - 2;
-  const int rc = launch_sweep(c, resolved_schedule(c), a, b);
-  if (rc) c->step_open = false;                  // as in bflbm_step_boundary: S[cur] is intact, the step may be retried
-  return rc;
+  return launch_sweep(c, c->step_sch, a, b) ? sweep_failed(c) : 0;
 }
 
 int bflbm_step_finish(bflbm_ctx* c) {
   if (!c) return fail("null context");
   BFLBM_REFUSE_VIEW(c, "bflbm_step_finish", "use bflbm_batch_step");
-  if (!c->step_open) return fail("no open step");
-  c->cur = 1 - c->cur;
-  c->steps += 1;
-  c->step_open = false;
-  c->density_valid = false;
-  c->com_valid = false;
-  if (c->inject) c->inject = false;              // injected noise feeds exactly one step
+  if (!c->step_open()) return fail("no open step");
+  state_advanced(c);
   return 0;
 }
 
@@ -869,11 +898,7 @@ int bflbm_step(bflbm_ctx* c, int nsteps) {
   BFLBM_REFUSE_VIEW(c, "bflbm_step", "use bflbm_batch_step");
   if (nsteps < 0) return fail("nsteps < 0");
   if (!c->G.zwrap && nsteps > 1) return fail("bflbm_step: nranks > 1 needs a halo exchange between steps; use nsteps == 1");
-  for (int s = 0; s < nsteps; ++s) {
-    if (bflbm_step_boundary(c)) return 1;
-    if (bflbm_step_interior(c)) return 1;
-    if (bflbm_step_finish(c)) return 1;
-  }
+  for (int s = 0; s < nsteps; ++s) if (bflbm_step_boundary(c) || bflbm_step_interior(c) || bflbm_step_finish(c)) return 1;
   return 0;
 }
 
@@ -889,10 +914,8 @@ int bflbm_step_count(const bflbm_ctx* c, long long* n) {
 int bflbm_set_step_count(bflbm_ctx* c, long long n) {
   if (!c) return fail("null context");
   if (n < 0) return fail("bflbm_set_step_count: negative step count");
-  if (c->step_open) return fail("bflbm_set_step_count inside an open step");
-  if (c->ref_kind_step == c->steps) c->ref_kind_step = n;
-  c->steps = n;
-  for (auto& b : c->fsig) for (auto& sg : b) sg = HoSig();     // frames are keyed by the step that wrote them
+  BFLBM_REFUSE_OPEN_STEP(c, "bflbm_set_step_count");
+  step_count_moved(c, n);
   return 0;
 }
 
@@ -926,7 +949,7 @@ int bflbm_halo_unpack(bflbm_ctx* c, int kind, int side, const void* buf) {
   HaloTable T; halo_table(c, kind, side, false, T);
   hipLaunchKernelGGL(k_halo_unpack, plane_grid(c, 2 * Q), dim3(256), 0, c->stream, halo_buffer(c, kind), (const double*)buf, c->G, T);
   HIP_TRY(hipGetLastError());
-  if (kind == BFLBM_HALO_STATE) c->density_valid = false;
+  if (kind == BFLBM_HALO_STATE) halos_written(c);
   return 0;
 }
 
@@ -943,13 +966,15 @@ int bflbm_halo_planes(bflbm_ctx* c, int kind, int side, int pack, void** planes,
   for (int e = 0; e < 2 * Q; ++e) planes[e] = base + (size_t)T.comp[e] * (size_t)c->G.vol + (size_t)T.plane[e] * (size_t)c->G.plane;
   *plane_bytes = (size_t)c->G.plane * sizeof(double);
   *count = 2 * Q;
-  if (!pack && kind == BFLBM_HALO_STATE) c->density_valid = false;    // the caller is about to overwrite halo planes of the resident state
+  if (!pack && kind == BFLBM_HALO_STATE) halos_written(c);    // the caller is about to overwrite halo planes of the resident state
   return 0;
 }
 
 // ---- observables -----------------------------------------------------------------------
-static int observe(bflbm_ctx* c, int what, int ncomp_out, double* dst, double* dst2, int ncomp_host, const bflbm_fab* box) {
-  if (c->step_open) return fail("observables requested inside an open step");
+// Materialises an observable of the resident state densely ([comp][z][y][x] over the own planes) in the scratch buffer
+// S[1-cur]: what 0 hydrovsbar, 1 noise, 2 hydrovs; ncomp_out components.  `asker` names the caller in the refusal.
+static int observe_launch(bflbm_ctx* c, int what, int ncomp_out, const char* asker) {
+  if (c->step_open()) return fail("%s requested inside an open step", asker);
   HIP_TRY(hipSetDevice(c->dom.device));
   if (what == 2 && ensure_density(c)) return 1;
   if (what != 0 && prepare_ref(c)) return 1;
@@ -962,6 +987,12 @@ static int observe(bflbm_ctx* c, int what, int ncomp_out, double* dst, double* d
   if (what == 1) hipLaunchKernelGGL((k_observe<1>), g, b, 0, c->stream, c->S[c->cur], c->rho, c->phi, c->injf, c->injg, out, c->G, c->dp, own_lo(c), idx, ncomp_out, inj, Rf);
   if (what == 2) hipLaunchKernelGGL((k_observe<2>), g, b, 0, c->stream, c->S[c->cur], c->rho, c->phi, c->injf, c->injg, out, c->G, c->dp, own_lo(c), idx, ncomp_out, inj, Rf);
   HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+static int observe(bflbm_ctx* c, int what, int ncomp_out, double* dst, double* dst2, int ncomp_host, const bflbm_fab* box) {
+  if (observe_launch(c, what, ncomp_out, "observables")) return 1;
+  double* out = c->S[1 - c->cur];
   const long long ovol = (long long)c->nzl * c->G.dplane;
   if (what == 1) {
     if (dst && copy_fab(c, dst, box, Q, out, ovol, 0, false, false, true)) return 1;
@@ -990,6 +1021,7 @@ int bflbm_get_noise(bflbm_ctx* c, double* fn, double* gn, const bflbm_fab* box) 
 int bflbm_inject_noise(bflbm_ctx* c, const double* fn, const double* gn, const bflbm_fab* box) {
   if (!c) return fail("null context");
   BFLBM_REFUSE_VIEW(c, "bflbm_inject_noise", "batches draw generated noise only (set kBT with bflbm_set_params, step with bflbm_batch_step)");
+  BFLBM_REFUSE_OPEN_STEP(c, "bflbm_inject_noise");
   if (!fn || !gn) { c->inject = false; return 0; }
   HIP_TRY(hipSetDevice(c->dom.device));
   const size_t nb = (size_t)Q * c->nzl * (size_t)c->G.dplane * sizeof(double);
@@ -1002,7 +1034,7 @@ int bflbm_inject_noise(bflbm_ctx* c, const double* fn, const double* gn, const b
 }
 
 static int reduce5(bflbm_ctx* c, double out[5]) {
-  if (c->step_open) return fail("reduction requested inside an open step");
+  if (c->step_open()) return fail("reduction requested inside an open step");
   HIP_TRY(hipSetDevice(c->dom.device));
   if (ensure_density(c)) return 1;
   hipLaunchKernelGGL(k_reduce, plane_grid(c, c->nzl), dim3(256), 0, c->stream, c->rho, c->phi, c->partial, c->G, own_lo(c));
@@ -1051,6 +1083,7 @@ static int prepare_ref(bflbm_ctx* c) {
 int bflbm_set_ref_state(bflbm_ctx* c, const double* rho_eq, const double* phi_eq, const double* rhot_eq, const bflbm_fab* box) {
   if (!c || !rho_eq || !phi_eq || !rhot_eq) return fail("null argument");
   BFLBM_REFUSE_VIEW(c, "bflbm_set_ref_state", "bflbm_batch_step has no reference-state noise (run such a lattice as a lone context)");
+  BFLBM_REFUSE_OPEN_STEP(c, "bflbm_set_ref_state");
   if (check_fab(box)) return 1;
   HIP_TRY(hipSetDevice(c->dom.device));
   const size_t nb = (size_t)c->G.dplane * c->G.nz * sizeof(double);
@@ -1066,6 +1099,7 @@ int bflbm_set_ref_state(bflbm_ctx* c, const double* rho_eq, const double* phi_eq
 int bflbm_enable_ref_state(bflbm_ctx* c, int on, const double com_ref[3]) {
   if (!c) return fail("null context");
   BFLBM_REFUSE_VIEW(c, "bflbm_enable_ref_state", "bflbm_batch_step has no reference-state noise (run such a lattice as a lone context)");
+  BFLBM_REFUSE_OPEN_STEP(c, "bflbm_enable_ref_state");
   if (on && (!c->ref[0] || !com_ref)) return fail("bflbm_enable_ref_state: upload the reference state first (bflbm_set_ref_state) and give com_ref");
   c->ref_on = on != 0;
   if (on) for (int d = 0; d < 3; ++d) c->com_ref[d] = com_ref[d];
@@ -1080,7 +1114,7 @@ int bflbm_ref_state_active(const bflbm_ctx* c, int* active) {
 
 int bflbm_set_com(bflbm_ctx* c, const double com[3]) {
   if (!c || !com) return fail("null argument");
-  if (c->step_open) return fail("bflbm_set_com inside an open step");
+  BFLBM_REFUSE_OPEN_STEP(c, "bflbm_set_com");
   for (int d = 0; d < 3; ++d) if (!std::isfinite(com[d])) return fail("bflbm_set_com: centre of mass is not finite");
   for (int d = 0; d < 3; ++d) c->com[d] = com[d];
   c->com_valid = true;
@@ -1118,7 +1152,7 @@ int bflbm_rng_site_normals(uint64_t seed, uint64_t site, uint32_t noise_index, d
 
 int bflbm_debug_time_kernel(bflbm_ctx* c, int which, int reps, float* ms) {
   if (!c || !ms || reps < 1) return fail("bad argument");
-  if (c->step_open) return fail("diagnostics inside an open step");
+  if (c->step_open()) return fail("diagnostics inside an open step");
   HIP_TRY(hipSetDevice(c->dom.device));
   const size_t sbytes = (size_t)2 * Q * c->G.vol * sizeof(double);
   for (int r = -1; r < reps; ++r) {
@@ -1134,7 +1168,7 @@ int bflbm_debug_time_kernel(bflbm_ctx* c, int which, int reps, float* ms) {
   float t = 0.f;
   HIP_TRY(hipEventElapsedTime(&t, c->ev0, c->ev1));
   *ms = t / reps;
-  c->density_valid = false;
+  halos_written(c);
   return 0;
 }
 
@@ -1223,7 +1257,7 @@ static int ring_copy(bflbm_ring* r, int kind) {
       }
     }
     HIP_TRY(hipEventRecord(r->unpacked[k], r->comm[k]));
-    if (kind == BFLBM_HALO_STATE) c->density_valid = false;
+    if (kind == BFLBM_HALO_STATE) halos_written(c);
   }
   return 0;
 }
@@ -1346,11 +1380,9 @@ int bflbm_ring_commit_upload(bflbm_ring* r, int reset) {
   if (!r) return fail("null ring");
   if (ring_exchange(r, BFLBM_HALO_UPLOAD) || ring_join(r)) return 1;
   for (bflbm_ctx* c : r->ctx) if (bflbm_commit_upload(c, reset)) return 1;
-  {                                                         // every slab resolves `auto` on the whole lattice's total density
-    double m = 0.;
-    for (bflbm_ctx* c : r->ctx) m = std::max(m, c->total_max);
-    for (bflbm_ctx* c : r->ctx) c->total_max = m;
-  }
+  double m = 0.;                                            // every slab resolves `auto` on the whole lattice's total density
+  for (bflbm_ctx* c : r->ctx) m = std::max(m, c->total_max);
+  for (bflbm_ctx* c : r->ctx) if (bflbm_set_state_total_max(c, m)) return 1;
   if (ring_exchange(r, BFLBM_HALO_STATE) || ring_join(r)) return 1;
   return bflbm_ring_sync(r);
 }
@@ -1387,8 +1419,7 @@ int bflbm_ring_com_sums(bflbm_ring* r, double sums[4]);
 // reference-state noise: the slabs need the GLOBAL centre of mass of the resident state
 static int ring_prepare_ref(bflbm_ring* r) {
   bflbm_ctx* c0 = r->ctx[0];
-  if (!ref_active(c0) || c0->com_valid) return 0;
-  if (c0->steps == c0->ref_kind_step && c0->ref_kind == 1) return 0;
+  if (!ref_active(c0) || c0->com_valid || (c0->steps == c0->ref_kind_step && c0->ref_kind == 1)) return 0;
   double s[4];
   if (bflbm_ring_com_sums(r, s)) return 1;
   const double com[3] = { s[1] / s[0], s[2] / s[0], s[3] / s[0] };
@@ -1455,14 +1486,12 @@ int bflbm_ring_sync(bflbm_ring* r) {
 // ---- replica batch (include/bflbm.h, "Replica batch"; kernels in bflbm_batch.h) -----------------------------------------
 struct bflbm_batch {
   std::vector<bflbm_ctx*> ctx;          // the replica views
-  std::vector<long long> steps0;        // per replica: step counter when its record was written
   hipStream_t stream = nullptr;         // every replica's stream
   int device = 0;
   Geo G;                                // the replicas' common geometry
   int schedule = 2;                     // 0 two-pass, 1 fused, 2 auto
   BatchRec* d_rec = nullptr;            // per-replica records read by the kernels
   BatchRec* h_rec = nullptr;            // pinned host copy of what was uploaded
-  bool table_valid = false;
   long long k = 0;                      // batch steps since the records were written
 };
 
@@ -1482,31 +1511,26 @@ int batch_resolved(const bflbm_batch* b) {
   return (long long)F.total * (long long)b->ctx.size() < device_cus() ? 0 : 1;
 }
 
-// Rewrite the device records when some replica changed since they were written: new parameters (bflbm_set_params on a
-// view), a step counter or resident buffer that no longer follows from the batch steps since (an init, an upload,
-// bflbm_set_step_count).  Unchanged replicas cost one comparison per step.
+// Rewrite the device records when some replica's record is stale (a new view, new parameters, an init or upload,
+// bflbm_set_step_count: the record_stale transitions) or k outgrows the kernels' 32-bit arithmetic.  Unchanged replicas
+// cost one flag per step.
 int batch_sync_table(bflbm_batch* b) {
-  bool stale = !b->table_valid || b->k >= (1LL << 30);
-  for (size_t r = 0; r < b->ctx.size() && !stale; ++r) {
-    const bflbm_ctx* c = b->ctx[r];
-    if (c->batch_dirty || c->steps != b->steps0[r] + b->k || c->cur != (b->h_rec[r].cur0 ^ (int)(b->k & 1))) stale = true;
-  }
+  bool stale = b->k >= (1LL << 30);
+  for (const bflbm_ctx* c : b->ctx) stale = stale || c->record_stale;
   if (!stale) return 0;
   HIP_TRY(hipStreamSynchronize(b->stream));      // the previous records may still be in flight to the device
   for (size_t r = 0; r < b->ctx.size(); ++r) {
-    bflbm_ctx* c = b->ctx[r];
+    const bflbm_ctx* c = b->ctx[r];
     BatchRec& R = b->h_rec[r];
     R.P = c->dp;
     R.S[0] = c->S[0]; R.S[1] = c->S[1];
     R.rho = c->rho; R.phi = c->phi;
     R.idx0 = (uint32_t)c->steps;
     R.cur0 = c->cur;
-    b->steps0[r] = c->steps;
-    c->batch_dirty = false;
   }
   HIP_TRY(hipMemcpyAsync(b->d_rec, b->h_rec, b->ctx.size() * sizeof(BatchRec), hipMemcpyHostToDevice, b->stream));
+  for (bflbm_ctx* c : b->ctx) c->record_stale = false;
   b->k = 0;
-  b->table_valid = true;
   return 0;
 }
 
@@ -1550,7 +1574,6 @@ int bflbm_batch_create(const bflbm_params* p, int nreplicas, const int n[3], int
     b->ctx.push_back(c);
   }
   b->G = b->ctx[0]->G;
-  b->steps0.assign(nreplicas, 0);
   e = hipMalloc((void**)&b->d_rec, (size_t)nreplicas * sizeof(BatchRec));
   if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_rec, (size_t)nreplicas * sizeof(BatchRec), hipHostMallocDefault);
   if (e != hipSuccess) { bflbm_batch_destroy(b); return fail("bflbm_batch_create: %s", hipGetErrorString(e)); }
@@ -1606,7 +1629,7 @@ int bflbm_batch_step(bflbm_batch* b, int nsteps) {
   if (!quiet.empty() && !noisy.empty())
     return fail("bflbm_batch_step: replicas %s have kBT == 0 and replicas %s kBT != 0; a batch steps all replicas with noise or none",
                 replica_list(quiet).c_str(), replica_list(noisy).c_str());
-  for (const bflbm_ctx* c : b->ctx) if (c->step_open) return fail("bflbm_batch_step: a replica has an open step");
+  for (const bflbm_ctx* c : b->ctx) if (c->step_open()) return fail("bflbm_batch_step: a replica has an open step");
   if (nsteps == 0) return 0;
   HIP_TRY(hipSetDevice(b->device));
   const int sch = batch_resolved(b);
@@ -1618,12 +1641,7 @@ int bflbm_batch_step(bflbm_batch* b, int nsteps) {
                                   : batch_two_pass_launch(b->d_rec, b->G, nrep, noise, (int)b->k, b->stream);
     if (e != hipSuccess) return fail("bflbm_batch_step: launch failed: %s", hipGetErrorString(e));
     b->k += 1;
-    for (bflbm_ctx* c : b->ctx) {
-      c->cur = 1 - c->cur;
-      c->steps += 1;
-      c->density_valid = false;
-      c->com_valid = false;
-    }
+    for (bflbm_ctx* c : b->ctx) state_advanced(c);
   }
   return 0;
 }

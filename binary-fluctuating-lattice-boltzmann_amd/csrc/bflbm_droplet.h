@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(256) k_sum_partials(const double* __restrict__
 // the decomposition: a ring gives the same doubles as the single context.
 template <int NV, class Launch>
 int reduce_blocks(bflbm_ctx* c, double (&out)[NV], Launch launch) {
-  if (c->step_open) return fail("reduction requested inside an open step");
+  if (c->step_open()) return fail("reduction requested inside an open step");
   HIP_TRY(hipSetDevice(c->dom.device));
   if (ensure_density(c)) return 1;
   const dim3 g = plane_grid(c, c->nzl);
@@ -360,7 +360,7 @@ __global__ void __launch_bounds__(256) k_minmax_partials(const double* __restric
 int rho_range(const std::vector<bflbm_ctx*>& ctx, double& lo, double& hi) {
   lo = 1e300; hi = -1e300;
   for (bflbm_ctx* c : ctx) {
-    if (c->step_open) return fail("reduction requested inside an open step");
+    if (c->step_open()) return fail("reduction requested inside an open step");
     HIP_TRY(hipSetDevice(c->dom.device));
     if (ensure_density(c)) return 1;
     const dim3 g = plane_grid(c, c->nzl);

@@ -573,17 +573,19 @@ static inline void handover_plan(const Geo& G, int pa, int pb, int pair_len, Fus
 }
 
 // fin/fout: frame buffers of the state read / written.  sig_in: what wrote fin (step == steps-1 required);
-// sig_out receives this launch.  returns the launch's error code
+// sig_out: the signature of this launch's plan, which describes fout once the launch has succeeded.  returns the
+// launch's error code
 static inline hipError_t handover_launch(const double* S, double* D, const double* fin, double* fout, const Geo& G, const DevParams& P,
                                   int pa, int pb, long long steps, const HoSig& sig_in, HoSig& sig_out, hipStream_t stream, int pair_len = 0, int mode = 0) {
   constexpr int TX = 64, TY = HO_TY;
   FusedGrid F;
   handover_plan(G, pa, pb, pair_len, F);
-  sig_out.pa = pa; sig_out.pb = pb; sig_out.lz = F.lz; sig_out.nchunks = F.nchunks; sig_out.cstride = F.cstride; sig_out.step = steps;
+  HoSig sig;
+  sig.pa = pa; sig.pb = pb; sig.lz = F.lz; sig.nchunks = F.nchunks; sig.cstride = F.cstride; sig.step = steps;
   HoGrid Hg;
   Hg.fin = fin; Hg.fout = fout;
   Hg.fplane = (long long)F.ncols * HoLayout<TY>::REC;
-  Hg.use_frames = (sig_in.step == steps - 1 && sig_in.same_geometry(sig_out)) ? 1 : 0;
+  Hg.use_frames = (sig_in.step == steps - 1 && sig_in.same_geometry(sig)) ? 1 : 0;
   dim3 grid((unsigned)(F.per_xcd * 8)), block(TX * TY);
   const uint32_t nidx = (uint32_t)steps;
   const bool rag = handover_ragged(G);
@@ -591,6 +593,7 @@ static inline hipError_t handover_launch(const double* S, double* D, const doubl
                    else     hipLaunchKernelGGL((k_fused_ho<TY, 1, false>), grid, block, 0, stream, S, D, G, P, F, Hg, nidx); }
   else           { if (rag) hipLaunchKernelGGL((k_fused_ho<TY, 0, true>), grid, block, 0, stream, S, D, G, P, F, Hg, nidx);
                    else     hipLaunchKernelGGL((k_fused_ho<TY, 0, false>), grid, block, 0, stream, S, D, G, P, F, Hg, nidx); }
+  sig_out = sig;
   return hipGetLastError();
 }
 

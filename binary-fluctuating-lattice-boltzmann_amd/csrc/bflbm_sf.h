@@ -171,21 +171,11 @@ int bflbm_sf_reset(bflbm_sf* s) {
 int bflbm_sf_accumulate(bflbm_sf* s, int lb_hydrovars, int reset) {
   if (!s) return fail("null argument");
   bflbm_ctx* c = s->c;
-  if (c->step_open) return fail("structure factor requested inside an open step");
   if (lb_hydrovars && s->nvar_fields > BFLBM_NHYDROBAR) return fail("bflbm_sf_accumulate: pair variables outside hydrovsbar");
+  if (observe_launch(c, lb_hydrovars ? 0 : 2, lb_hydrovars ? BFLBM_NHYDROBAR : s->nvar_fields, "structure factor")) return 1;
   if (reset && bflbm_sf_reset(s)) return 1;
-  HIP_TRY(hipSetDevice(c->dom.device));
   g_fft.set_stream(s->plan, c->stream);              // the context's stream may have been replaced (bflbm_set_stream) since the plan was made
-  if (!lb_hydrovars && ensure_density(c)) return 1;
-  if (!lb_hydrovars && prepare_ref(c)) return 1;
-  const RefState Rf = ref_state(c);
   double* fields = c->S[1 - c->cur];                 // dense [comp][z][y][x]
-  dim3 g = plane_grid(c, c->nzl), b(256);
-  const uint32_t idx = (uint32_t)c->steps;
-  const int inj = c->inject ? 1 : 0;
-  if (lb_hydrovars) hipLaunchKernelGGL((k_observe<0>), g, b, 0, c->stream, c->S[c->cur], c->rho, c->phi, c->injf, c->injg, fields, c->G, c->dp, own_lo(c), idx, BFLBM_NHYDROBAR, inj, Rf);
-  else              hipLaunchKernelGGL((k_observe<2>), g, b, 0, c->stream, c->S[c->cur], c->rho, c->phi, c->injf, c->injg, fields, c->G, c->dp, own_lo(c), idx, s->nvar_fields, inj, Rf);
-  HIP_TRY(hipGetLastError());
   const long long n = (long long)c->nzl * c->G.dplane;
   for (size_t v = 0; v < s->vars.size(); ++v)
     if (g_fft.exec_d2z(s->plan, fields + (long long)s->vars[v] * n, (hipfftDoubleComplex*)(s->hat + (long long)v * s->nk)) != HIPFFT_SUCCESS)
@@ -209,7 +199,7 @@ int bflbm_sf_get(bflbm_sf* s, int what, int zero_avg, double* dst) {
   if (!s || !dst) return fail("null argument");
   if (what < 0 || what > 2) return fail("bflbm_sf_get: what must be 0, 1 or 2");
   bflbm_ctx* c = s->c;
-  if (c->step_open) return fail("structure factor requested inside an open step");
+  if (c->step_open()) return fail("structure factor requested inside an open step");
   HIP_TRY(hipSetDevice(c->dom.device));
   const long long n = (long long)c->nzl * c->G.dplane;
   double* out = c->S[1 - c->cur];                    // 38 component volumes of scratch >= 32 pairs

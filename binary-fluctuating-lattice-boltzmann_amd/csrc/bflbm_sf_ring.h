@@ -154,24 +154,15 @@ int bflbm_ring_sf_accumulate(bflbm_ring_sf* s, int lb_hydrovars, int reset) {
   const int n = (int)r->ctx.size();
   if (lb_hydrovars && s->nvar_fields > BFLBM_NHYDROBAR) return fail("bflbm_ring_sf_accumulate: pair variables outside hydrovsbar");
   if (reset && bflbm_ring_sf_reset(s)) return 1;
-  if (!lb_hydrovars && ring_prepare_ref(r)) return 1;
+  if (!lb_hydrovars && ring_prepare_ref(r)) return 1;     // the global centre of mass: the slabs' own prepare_ref is then a no-op
   const Geo& G0 = r->ctx[0]->G;
   const int ny = G0.ny, nz = G0.nz, nxc = s->nxc;
   const size_t nv = s->vars.size();
   // 1. observe + 2-D transforms of the own planes
   for (int k = 0; k < n; ++k) {
     bflbm_ctx* c = r->ctx[k];
-    if (c->step_open) return fail("structure factor requested inside an open step");
-    HIP_TRY(hipSetDevice(c->dom.device));
-    if (!lb_hydrovars && ensure_density(c)) return 1;
-    const RefState Rf = ref_state(c);
+    if (observe_launch(c, lb_hydrovars ? 0 : 2, lb_hydrovars ? BFLBM_NHYDROBAR : s->nvar_fields, "structure factor")) return 1;
     double* fields = c->S[1 - c->cur];
-    dim3 g = plane_grid(c, c->nzl), b(256);
-    const uint32_t idx = (uint32_t)c->steps;
-    const int inj = c->inject ? 1 : 0;
-    if (lb_hydrovars) hipLaunchKernelGGL((k_observe<0>), g, b, 0, c->stream, c->S[c->cur], c->rho, c->phi, c->injf, c->injg, fields, c->G, c->dp, own_lo(c), idx, BFLBM_NHYDROBAR, inj, Rf);
-    else              hipLaunchKernelGGL((k_observe<2>), g, b, 0, c->stream, c->S[c->cur], c->rho, c->phi, c->injf, c->injg, fields, c->G, c->dp, own_lo(c), idx, s->nvar_fields, inj, Rf);
-    HIP_TRY(hipGetLastError());
     g_fft.set_stream(s->slab[k].plan2d, c->stream);
     const long long nloc = (long long)c->nzl * c->G.dplane;
     for (size_t v = 0; v < nv; ++v)

@@ -344,6 +344,11 @@ class LocalSlabRing:
         self.exchange(_lib.HALO_UPLOAD)
         for e in self.engines:
             e.commit_upload(True)
+        if hasattr(self.engines[0], "set_state_total_max"):
+            # every slab resolves `auto` on the whole lattice's total density, as in SlabLattice.LBM_init
+            m = max(e.state_total_max for e in self.engines)
+            for e in self.engines:
+                e.set_state_total_max(m)
         self.exchange(_lib.HALO_STATE)
 
     def _gather(self, getter, ncomp):

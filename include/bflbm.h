@@ -163,7 +163,12 @@ int bflbm_set_step_count(bflbm_ctx* c, long long steps_done);
  *   bflbm_step_interior  -> all other planes (overlaps the exchange)
  *   wait; bflbm_halo_unpack(BFLBM_HALO_NEXT, side, buf)
  *   bflbm_step_finish    -> swap A/B buffers, advance the step counter
- * With nranks == 1 these also work (halo calls are then not needed). */
+ * With nranks == 1 these also work (halo calls are then not needed).
+ * The step is open from bflbm_step_boundary to bflbm_step_finish and runs the schedule bflbm_step_boundary resolved with the
+ * parameters it had then: inside it bflbm_set_params, bflbm_set_schedule, bflbm_inject_noise, bflbm_set_state_total_max,
+ * bflbm_set_ref_state, bflbm_enable_ref_state, bflbm_set_com, bflbm_set_step_count, bflbm_tune_placement, downloads,
+ * observables and reductions are refused ("... inside an open step").  A failed bflbm_step_boundary or
+ * bflbm_step_interior closes the step with the resident state intact: it may be retried, on another schedule too. */
 int bflbm_step_boundary(bflbm_ctx* c);
 int bflbm_step_interior(bflbm_ctx* c);
 int bflbm_step_finish(bflbm_ctx* c);

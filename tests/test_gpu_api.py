@@ -71,6 +71,61 @@ def test_error_conventions(pkg):
     slab.close()
 
 
+def test_an_open_step_pins_what_it_runs(pkg, ob):
+    """bflbm_step_boundary resolves the schedule and the step runs it with the parameters it started with: the calls that
+    could change either are refused until bflbm_step_finish, and the step then completes as if they had not been made."""
+    n = (16, 16, 16)
+    lbm = pkg.BinaryLBM(*n, schedule="fused")
+    ref = ob.OracleLattice(*n)
+    lbm.LBM_init_stripe(0.5)
+    ref.init_stripe(0.5)
+    lbm.step_boundary()
+    noise = np.zeros((19,) + n)
+    eq = np.ones(n)
+    for call in (lambda: lbm.set_params(alpha0=1.0, kBT=1e-5), lambda: lbm.set_schedule("two_pass"),
+                 lambda: lbm.inject_noise(noise, noise), lambda: lbm.inject_noise(None, None),
+                 lambda: lbm.set_state_total_max(100.0), lambda: lbm.set_ref_state(eq, eq, 2 * eq, (8., 8., 8.)),
+                 lambda: lbm.disable_ref_state()):
+        with pytest.raises(pkg.BflbmError, match="inside an open step"):
+            call()
+    lbm.step_interior()
+    lbm.step_finish()
+    ref.timestep()
+    f, g = lbm.populations()
+    assert np.array_equal(f, ref.f) and np.array_equal(g, ref.g)
+    assert lbm.resolved_schedule() == "fused" and lbm.state_total_max < 0 and not lbm.ref_state_active
+    lbm.close()
+
+
+@pytest.mark.parametrize("between", ["fused_step", "set_steps_done"])
+def test_handover_frames_are_not_reused_across_an_exact_step_or_a_moved_counter(pkg, between):
+    """Frames describe the state of the hand-over step that wrote them.  After an exact step, or after the step counter was
+    set, the next hand-over step has none and pulls every ring: it equals one fused step from the same state, bit for bit."""
+    n = (128, 16, 32)
+    lbm = pkg.BinaryLBM(*n, schedule="handover")
+    assert lbm.resolved_schedule() == "handover"
+    lbm.LBM_init_droplet(0.2)
+    lbm.LBM_timestep(3)
+    if between == "fused_step":
+        lbm.set_schedule("fused")
+        lbm.LBM_timestep(1)
+        lbm.set_schedule("handover")
+    else:
+        lbm.set_steps_done(lbm.steps_done)
+    f0, g0 = lbm.populations()
+    steps = lbm.steps_done
+    lbm.LBM_timestep(1)
+    other = pkg.BinaryLBM(*n, schedule="fused")
+    other.LBM_init(f0, g0)
+    other.set_steps_done(steps)
+    other.LBM_timestep(1)
+    f, g = lbm.populations()
+    fo, go = other.populations()
+    assert np.array_equal(f, fo) and np.array_equal(g, go)
+    lbm.close()
+    other.close()
+
+
 def test_partial_box_download_only_touches_its_cells(pkg, ob):
     """A FAB covering only part of the lattice (and sticking out of it) gets only its overlap."""
     n = (8, 8, 8)

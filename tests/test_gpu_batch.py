@@ -202,6 +202,35 @@ def test_batch_replicas_are_independent(pkg):
             lone.close()
 
 
+def test_batch_records_follow_a_reinit_and_an_upload_that_keeps_the_counter(pkg):
+    """A replica's device record is rewritten because a call marked it stale, not because its step counter or buffer no
+    longer follow from the batch steps: right after the step that wrote the records, re-initialise one replica and upload
+    into another with commit_upload(False) (same counter, same buffer).  With noise, the counter is the noise index."""
+    n = (32, 32, 32)
+    params, inits = [dict(p, kBT=1e-5) for p in PARAMS[:3]], INITS[:3]
+    with pkg.BatchLBM(n, params=params, schedule="two_pass") as b:
+        for rep, init in zip(b.replicas, inits):
+            _init(rep, n, init)
+        lones = _lones(pkg, n, params, inits, "two_pass")
+        b.LBM_timestep(1)
+        for lone in lones:
+            lone.LBM_timestep(1)
+        f1, g1 = _random_state(n, 5)
+        for lat in (b.replicas[0], lones[0]):
+            lat.LBM_init_droplet(0.35)
+        for lat in (b.replicas[1], lones[1]):
+            lat.upload(f1, g1)
+            lat.commit_upload(False)
+        b.LBM_timestep(4)
+        for lone in lones:
+            lone.LBM_timestep(4)
+        assert [rep.steps_done for rep in b.replicas] == [lone.steps_done for lone in lones] == [4, 5, 5]
+        for r, (rep, lone) in enumerate(zip(b.replicas, lones)):
+            _assert_same(rep, lone, f"replica {r} after a re-init / an upload right after the records were written")
+        for lone in lones:
+            lone.close()
+
+
 def test_batch_refusals(pkg):
     n = (32, 32, 32)
     lib = pkg._lib.load()

@@ -80,6 +80,22 @@ def test_slab_ring_upload_path(pkg, ob):
     ring.close()
 
 
+def test_slab_ring_upload_hands_every_slab_the_lattice_maximum(pkg):
+    """LocalSlabRing.LBM_init: every slab resolves `auto` on the largest |rho + phi| of the whole upload, not of its own
+    planes (as SlabLattice.LBM_init and bflbm_ring_commit_upload do)."""
+    n = (64, 8, 32)
+    w = np.array([1 / 3] + [1 / 18] * 6 + [1 / 36] * 12)[:, None, None, None]
+    scale = np.ones((1, n[2], 1, 1))
+    scale[:, 16:] = 2.0                              # slab 1: total density 3, slab 0: 1.5
+    f0 = np.ascontiguousarray(np.broadcast_to(w * scale, (19, n[2], n[1], n[0])))
+    g0 = 0.5 * f0
+    ring = pkg.LocalSlabRing(*n, 2)
+    ring.LBM_init(f0, g0)
+    tm = [e.state_total_max for e in ring.engines]
+    assert tm[0] == tm[1] and abs(tm[0] - 3.0) < 1e-12, tm
+    ring.close()
+
+
 def test_distributed_driver_world_size_one(pkg, ob):
     """SlabLattice over torch.distributed with one rank on the GPU (stream sharing with torch)."""
     import os
