@@ -1635,10 +1635,12 @@ int bflbm_batch_step(bflbm_batch* b, int nsteps) {
   const int sch = batch_resolved(b);
   const bool noise = !noisy.empty();
   const int nrep = (int)b->ctx.size();
+  bool unit = !noise;                          // the unit-rate kernels: zero noise and every replica at tau = 1/2
+  for (const bflbm_ctx* c : b->ctx) unit = unit && unit_rates(c->dp);
   for (int s = 0; s < nsteps; ++s) {
     if (batch_sync_table(b)) return 1;
-    const hipError_t e = sch == 1 ? batch_fused_launch(b->d_rec, b->G, nrep, noise ? 1 : 0, (int)b->k, b->stream)
-                                  : batch_two_pass_launch(b->d_rec, b->G, nrep, noise, (int)b->k, b->stream);
+    const hipError_t e = sch == 1 ? batch_fused_launch(b->d_rec, b->G, nrep, noise ? 1 : 0, unit, (int)b->k, b->stream)
+                                  : batch_two_pass_launch(b->d_rec, b->G, nrep, noise, unit, (int)b->k, b->stream);
     if (e != hipSuccess) return fail("bflbm_batch_step: launch failed: %s", hipGetErrorString(e));
     b->k += 1;
     for (bflbm_ctx* c : b->ctx) state_advanced(c);

@@ -46,7 +46,7 @@ __global__ void __launch_bounds__(256) k_density_batch(const BatchRec* __restric
 }
 
 // pass B, grid (plane blocks, nz, B): k_collide without injected noise and reference state
-template <bool NOISE>
+template <bool NOISE, bool UNIT>
 __device__ __forceinline__ void collide_batch_body(const double* __restrict__ S, double* __restrict__ D,
                                                    const double* __restrict__ rho, const double* __restrict__ phi,
                                                    const Geo& G, const DevParams& P, uint32_t noise_index) {
@@ -63,7 +63,14 @@ template <bool NOISE>
 __global__ void __launch_bounds__(256, COLLIDE_WAVES) k_collide_batch(const BatchRec* __restrict__ recs, Geo G, int k) {
   const BatchRecC R = batch_rec(recs, (int)blockIdx.z);
   const int cur = R->cur0 ^ (k & 1);
-  collide_batch_body<NOISE>(R->S[cur], R->S[cur ^ 1], R->rho, R->phi, G, batch_params(R), R->idx0 + (uint32_t)k);
+  collide_batch_body<NOISE, false>(R->S[cur], R->S[cur ^ 1], R->rho, R->phi, G, batch_params(R), R->idx0 + (uint32_t)k);
+}
+
+// zero noise with every replica at unit relaxation rates (unit_rates): d_relax_with's unit-rate form
+__global__ void __launch_bounds__(256, COLLIDE_WAVES) k_collide_batch_unit(const BatchRec* __restrict__ recs, Geo G, int k) {
+  const BatchRecC R = batch_rec(recs, (int)blockIdx.z);
+  const int cur = R->cur0 ^ (k & 1);
+  collide_batch_body<false, true>(R->S[cur], R->S[cur ^ 1], R->rho, R->phi, G, batch_params(R), R->idx0 + (uint32_t)k);
 }
 
 // one-pass schedule: nrep * F.total workgroups.  Workgroups b and b+8 share an XCD (round-robin dispatch); the work list
@@ -79,7 +86,7 @@ __device__ __forceinline__ bool batch_map(const FusedGrid& F, int nrep, int b, i
   return true;
 }
 
-template <int TX, int TY, int MODE>
+template <int TX, int TY, int MODE, bool UNIT>
 __device__ __forceinline__ void fused_batch_body(const double* __restrict__ S, double* __restrict__ D,
                                                  const Geo& G, const DevParams& P, const FusedGrid& F, uint32_t noise_index, int w) {
   const double* __restrict__ injf = nullptr;
@@ -97,7 +104,18 @@ k_fused_batch(const BatchRec* __restrict__ recs, Geo G, FusedGrid F, int nrep, i
   if (!batch_map(F, nrep, (int)blockIdx.x, r, w)) return;   // whole workgroup leaves together
   const BatchRecC R = batch_rec(recs, r);
   const int cur = R->cur0 ^ (k & 1);
-  fused_batch_body<TX, TY, MODE>(R->S[cur], R->S[cur ^ 1], G, batch_params(R), F, R->idx0 + (uint32_t)k, w);
+  fused_batch_body<TX, TY, MODE, false>(R->S[cur], R->S[cur ^ 1], G, batch_params(R), F, R->idx0 + (uint32_t)k, w);
+}
+
+// zero noise with every replica at unit relaxation rates (unit_rates): d_relax_with's unit-rate form
+template <int TX, int TY>
+__global__ void __launch_bounds__(TX*TY, 2)
+k_fused_batch_unit(const BatchRec* __restrict__ recs, Geo G, FusedGrid F, int nrep, int k) {
+  int r, w;
+  if (!batch_map(F, nrep, (int)blockIdx.x, r, w)) return;   // whole workgroup leaves together
+  const BatchRecC R = batch_rec(recs, r);
+  const int cur = R->cur0 ^ (k & 1);
+  fused_batch_body<TX, TY, 0, true>(R->S[cur], R->S[cur ^ 1], G, batch_params(R), F, R->idx0 + (uint32_t)k, w);
 }
 
 // the batch's tile shape and chunking: the single-lattice plan with the workgroups of all replicas counted
@@ -106,7 +124,8 @@ static inline int batch_fused_plan(const Geo& G, int nrep, int mode, FusedGrid& 
   return fused_plan(G, 0, G.nzs, mode, 0, F, nrep, batch_fused_threads(mode));
 }
 
-static inline hipError_t batch_fused_launch(const BatchRec* recs, const Geo& G, int nrep, int mode, int k, hipStream_t stream) {
+// unit: the caller found zero noise and unit_rates() in every replica
+static inline hipError_t batch_fused_launch(const BatchRec* recs, const Geo& G, int nrep, int mode, bool unit, int k, hipStream_t stream) {
   FusedGrid F;
   const int TX = batch_fused_plan(G, nrep, mode, F);
   const long long per_xcd = ((long long)nrep * F.total + 7) / 8;
@@ -114,6 +133,12 @@ static inline hipError_t batch_fused_launch(const BatchRec* recs, const Geo& G, 
   dim3 grid((unsigned)(per_xcd * 8)), block(batch_fused_threads(mode));
   constexpr int TX0 = FUSED_TX, TY0 = FUSED_TY;
   if (mode == 1)      hipLaunchKernelGGL((k_fused_batch<32, 8, 1>), grid, block, 0, stream, recs, G, F, nrep, k);
+  else if (unit) {
+    if (TX == 32)      hipLaunchKernelGGL((k_fused_batch_unit<32, (TX0 * TY0) / 32>), grid, block, 0, stream, recs, G, F, nrep, k);
+    else if (TX == 16) hipLaunchKernelGGL((k_fused_batch_unit<16, (TX0 * TY0) / 16>), grid, block, 0, stream, recs, G, F, nrep, k);
+    else if (TX == 8)  hipLaunchKernelGGL((k_fused_batch_unit<8, (TX0 * TY0) / 8>), grid, block, 0, stream, recs, G, F, nrep, k);
+    else               hipLaunchKernelGGL((k_fused_batch_unit<TX0, TY0>), grid, block, 0, stream, recs, G, F, nrep, k);
+  }
   else if (TX == 32)  hipLaunchKernelGGL((k_fused_batch<32, (TX0 * TY0) / 32, 0>), grid, block, 0, stream, recs, G, F, nrep, k);
   else if (TX == 16)  hipLaunchKernelGGL((k_fused_batch<16, (TX0 * TY0) / 16, 0>), grid, block, 0, stream, recs, G, F, nrep, k);
   else if (TX == 8)   hipLaunchKernelGGL((k_fused_batch<8, (TX0 * TY0) / 8, 0>), grid, block, 0, stream, recs, G, F, nrep, k);
@@ -121,10 +146,11 @@ static inline hipError_t batch_fused_launch(const BatchRec* recs, const Geo& G, 
   return hipGetLastError();
 }
 
-static inline hipError_t batch_two_pass_launch(const BatchRec* recs, const Geo& G, int nrep, bool noise, int k, hipStream_t stream) {
+static inline hipError_t batch_two_pass_launch(const BatchRec* recs, const Geo& G, int nrep, bool noise, bool unit, int k, hipStream_t stream) {
   const dim3 grid((unsigned)((G.plane + 255) / 256), (unsigned)G.nzs, (unsigned)nrep), block(256);
   hipLaunchKernelGGL(k_density_batch, grid, block, 0, stream, recs, G, k);
   if (noise) hipLaunchKernelGGL((k_collide_batch<true>), grid, block, 0, stream, recs, G, k);
+  else if (unit) hipLaunchKernelGGL(k_collide_batch_unit, grid, block, 0, stream, recs, G, k);
   else       hipLaunchKernelGGL((k_collide_batch<false>), grid, block, 0, stream, recs, G, k);
   return hipGetLastError();
 }

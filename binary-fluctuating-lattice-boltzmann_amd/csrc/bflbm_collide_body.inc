@@ -1,7 +1,8 @@
 // bflbm_collide_body.inc -- the body of pass B of the two-pass schedule (pull, project, draw noise, collide, store),
 // included verbatim by k_collide (bflbm_kernels.h) and by the replica-batch kernel (bflbm_batch.h), so that both
 // compile the same source and the single-lattice kernel's instructions stay exactly what they were.
-// In scope: template flags NOISE, INJECT; S, D, rho, phi, injf, injg, G, P, p0, noise_index, Rf.
+// In scope: NOISE, INJECT, UNIT (compile-time; UNIT: both relaxation rates are 1.0, see d_relax_with); S, D, rho, phi, injf,
+// injg, G, P, p0, noise_index, Rf.
   __shared__ double ntab[(NOISE && !INJECT) ? BFLBM_NORMAL_TABLE_N : 4];
   if (NOISE && !INJECT) d_load_normal_table(ntab, true);
   BFLBM_SITE_FROM_BLOCK_XCD();
@@ -54,7 +55,7 @@
       d_relax_generated(P, m, r, v_b, Hy.uf, Hy.af, P.inv_tau_f_bar, fn3, NA.sr, ntab, rst, R.cs4);
     } else {
       const double zn[Q] = {0.};
-      d_relax<false>(P, m, r, v_b, Hy.uf, Hy.af, P.inv_tau_f_bar, zn, R.cs4);
+      d_relax<false, UNIT>(P, m, r, v_b, Hy.uf, Hy.af, P.inv_tau_f_bar, zn, R.cs4);
     }
     d_populations(m, fs);
 #pragma unroll
@@ -72,7 +73,7 @@
       d_relax_generated(P, m, ph, v_b, Hy.ug, Hy.ag, P.inv_tau_g_bar, gn3, NA.sp, ntab, rst, R.cs4);
     } else {
       const double zn[Q] = {0.};
-      d_relax<false>(P, m, ph, v_b, Hy.ug, Hy.ag, P.inv_tau_g_bar, zn, R.cs4);
+      d_relax<false, UNIT>(P, m, ph, v_b, Hy.ug, Hy.ag, P.inv_tau_g_bar, zn, R.cs4);
     }
     d_populations(m, gs);
 #pragma unroll

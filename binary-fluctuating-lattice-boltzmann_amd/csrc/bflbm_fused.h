@@ -75,6 +75,20 @@ __global__ void __launch_bounds__(TX*TY, 2)
 k_fused(const double* __restrict__ S, double* __restrict__ D,
         const double* __restrict__ injf, const double* __restrict__ injg,
         Geo G, DevParams P, FusedGrid F, uint32_t noise_index) {
+  constexpr bool UNIT = false;
+#define BFLBM_FUSED_MAP(col, chunk) fused_map(F, (int)blockIdx.x, col, chunk)
+#include "bflbm_fused_body.inc"
+#undef BFLBM_FUSED_MAP
+}
+// zero noise at unit relaxation rates (unit_rates(P)): the same source with d_relax_with's unit-rate form, under its own
+// name so that k_fused's symbols and code stay what they were
+template <int TX, int TY>
+__global__ void __launch_bounds__(TX*TY, 2)
+k_fused_unit(const double* __restrict__ S, double* __restrict__ D,
+             const double* __restrict__ injf, const double* __restrict__ injg,
+             Geo G, DevParams P, FusedGrid F, uint32_t noise_index) {
+  constexpr int MODE = 0;
+  constexpr bool UNIT = true;
 #define BFLBM_FUSED_MAP(col, chunk) fused_map(F, (int)blockIdx.x, col, chunk)
 #include "bflbm_fused_body.inc"
 #undef BFLBM_FUSED_MAP
@@ -153,6 +167,12 @@ static inline hipError_t fused_launch(const double* S, double* D, const double* 
   constexpr int TX0 = FUSED_TX, TY0 = FUSED_TY;
   if (mode == 2)      hipLaunchKernelGGL((k_fused<TX0, TY0, 2>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
   else if (mode == 1) hipLaunchKernelGGL((k_fused<TX0, TY0, 1>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
+  else if (unit_rates(P)) {
+    if (TX == 32)      hipLaunchKernelGGL((k_fused_unit<32, (TX0 * TY0) / 32>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
+    else if (TX == 16) hipLaunchKernelGGL((k_fused_unit<16, (TX0 * TY0) / 16>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
+    else if (TX == 8)  hipLaunchKernelGGL((k_fused_unit<8, (TX0 * TY0) / 8>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
+    else               hipLaunchKernelGGL((k_fused_unit<TX0, TY0>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
+  }
   else if (TX == 32)  hipLaunchKernelGGL((k_fused<32, (TX0 * TY0) / 32, 0>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
   else if (TX == 16)  hipLaunchKernelGGL((k_fused<16, (TX0 * TY0) / 16, 0>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
   else if (TX == 8)   hipLaunchKernelGGL((k_fused<8, (TX0 * TY0) / 8, 0>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);

@@ -1,7 +1,8 @@
 // bflbm_fused_body.inc -- the body of the fused plane-marching kernel (schedule 1), included verbatim by k_fused
 // (bflbm_fused.h) and by the replica-batch kernel (bflbm_batch.h), so that both compile the same source and the
 // single-lattice kernel's instructions stay exactly what they were.
-// In scope: template parameters TX, TY, MODE; S, D, injf, injg, G, P, F, noise_index; the macro
+// In scope: TX, TY, MODE, UNIT (compile-time; UNIT: both relaxation rates are 1.0, see d_relax_with); S, D, injf, injg, G, P,
+// F, noise_index; the macro
 // BFLBM_FUSED_MAP(col, chunk), which sets this workgroup's tile column and chunk and is false when it has none.
   static_assert((TX * TY) % 64 == 0, "whole waves");
   constexpr int LW = TX + 2;                     // LDS row length
@@ -197,7 +198,7 @@
             d_relax_generated(P, mf, r, v_b, Hy.uf, Hy.af, P.inv_tau_f_bar, n3, sqrt(fabs(r)), ntab, rst, R.cs4);
           } else {
             const double zn[Q] = {0.};
-            d_relax<false>(P, mf, r, v_b, Hy.uf, Hy.af, P.inv_tau_f_bar, zn, R.cs4);
+            d_relax<false, UNIT>(P, mf, r, v_b, Hy.uf, Hy.af, P.inv_tau_f_bar, zn, R.cs4);
           }
           double out[Q];
           d_populations(mf, out);
@@ -215,7 +216,7 @@
             d_relax_generated(P, mg, ph, v_b, Hy.ug, Hy.ag, P.inv_tau_g_bar, n3, sqrt(fabs(ph)), ntab, rst, R.cs4);
           } else {
             const double zn[Q] = {0.};
-            d_relax<false>(P, mg, ph, v_b, Hy.ug, Hy.ag, P.inv_tau_g_bar, zn, R.cs4);
+            d_relax<false, UNIT>(P, mg, ph, v_b, Hy.ug, Hy.ag, P.inv_tau_g_bar, zn, R.cs4);
           }
           double out[Q];
           d_populations(mg, out);

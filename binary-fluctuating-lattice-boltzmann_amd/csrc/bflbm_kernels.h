@@ -212,8 +212,12 @@ __global__ void __launch_bounds__(256, COLLIDE_WAVES) k_collide(const double* __
                                                  const double* __restrict__ rho, const double* __restrict__ phi,
                                                  const double* __restrict__ injf, const double* __restrict__ injg,
                                                  Geo G, DevParams P, int p0, uint32_t noise_index, RefState Rf) {
+  constexpr bool UNIT = false;
 #include "bflbm_collide_body.inc"
 }
+// There is no unit-rate form of this kernel (d_relax_with's UNIT; k_fused_unit, k_fused_ho_unit): compiled with the flag its
+// register allocation spills 4 SGPRs where this one spills none, and the two-pass schedule is the small-lattice and noise path.
+// The batch's pass B has one (k_collide_batch_unit: 6 SGPR spills with and without the flag).  Same doubles either way.
 
 // ---- natural (post-stream) populations of the slab's own planes: N_i(x) = S_i(x - c_i)
 __global__ void __launch_bounds__(256) k_pull(const double* __restrict__ S, double* __restrict__ N, Geo G, int p0) {

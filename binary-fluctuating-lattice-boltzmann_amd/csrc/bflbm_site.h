@@ -40,6 +40,9 @@ struct DevParams {
   uint32_t seed_lo, seed_hi;
   int noise_on;                 // kBT != 0
 };
+// Both relaxation rates are exactly 1.0 (tau_f == tau_g == 1/2, the header default).  A quiet launch with such
+// parameters takes the kernels compiled with UNIT (d_relax_with); every other tau takes the generic ones.
+static inline bool unit_rates(const DevParams& P) { return P.inv_tau_f_bar == 1.0 && P.inv_tau_g_bar == 1.0; }
 
 // RN(x/3) and RN(x/9) with one multiply and two FMAs instead of the ~10-instruction IEEE
 // division sequence.  Exactness (for normal x, no under/overflow): write x = X*2^e with X a
@@ -408,31 +411,44 @@ __device__ __forceinline__ void d_force_moments(const DevParams& P, double rho, 
 // velocity v_b (equilibrium), its own real velocity u and acceleration a (force moments).
 // The noise of mode k is asked from `noise(k)` in mode order right where it is added (a generated stream never
 // exists as an array of 19 doubles); NOISE=false drops the terms (they are exactly +-0 when kBT == 0).
-template <bool NOISE, typename NoiseFn>
+//
+// UNIT: the caller knows that inv_tau_bar == 1.0 (tau = 1/2, the header default: derive() gives
+// 1./(tau*(1. + 0.5/tau)) == 1.0 exactly) and that there is no noise.  Then, for every finite m[k],
+//   k >= 10:  m + (1.0*(0. - m) + 0.) = m + (-m) = +0.0    (x + (-x) is +0.0 in round-to-nearest, for x = +-0 as well)
+//   k <  10:  1.0*(mEq - m) is (mEq - m) bit for bit
+// so the ghost modes are written as the literal +0.0 WITHOUT reading m[k], and the multiplication is dropped.  Nothing
+// else is rewritten: with m[10..18] a literal zero the compiler removes the ghost rows of d_moments and the terms of
+// d_population_terms that IEEE arithmetic lets it remove (x - 0.0, c*0.0 with c a finite constant, x + (-0.0)), and
+// keeps every x + 0.0 whose x may be -0.0, so the stored populations are the generic code's bits by construction.
+// (Non-finite m is outside the contract: inf + (-inf) is NaN in the generic form and 0 here)
+// The flag exists for the quiet kernels only; the noise paths relax the ghost modes as m + (-m + n), which is not n.
+template <bool NOISE, bool UNIT = false, typename NoiseFn>
 __device__ __forceinline__ void d_relax_with(const DevParams& P, double (&m)[Q], double rho_k, const double (&v_b)[3],
                                              const double (&u)[3], const double (&a)[3], double inv_tau_bar,
                                              NoiseFn noise, double ycs4) {
+  static_assert(!(NOISE && UNIT), "the unit-rate form is defined at zero noise only");
   double mEq[10], mPhi[10];
   d_equilibrium(P, rho_k, v_b, mEq, ycs4);
   d_force_moments(P, rho_k, u, a, mPhi, ycs4);
 #pragma unroll
   for (int k = 0; k < 10; ++k) {
-    double R = inv_tau_bar*(mEq[k] - m[k]) + mPhi[k];
+    double R = (UNIT ? (mEq[k] - m[k]) : inv_tau_bar*(mEq[k] - m[k])) + mPhi[k];
     if (NOISE) R = R + noise(k);
     m[k] = m[k] + R;
   }
 #pragma unroll
   for (int k = 10; k < Q; ++k) {
+    if (UNIT) { m[k] = 0.; continue; }
     double R = inv_tau_bar*(0. - m[k]) + 0.;
     if (NOISE) R = R + noise(k);
     m[k] = m[k] + R;
   }
 }
-template <bool NOISE>
+template <bool NOISE, bool UNIT = false>
 __device__ __forceinline__ void d_relax(const DevParams& P, double (&m)[Q], double rho_k, const double (&v_b)[3],
                                         const double (&u)[3], const double (&a)[3], double inv_tau_bar,
                                         const double (&noise)[Q], double ycs4) {
-  d_relax_with<NOISE>(P, m, rho_k, v_b, u, a, inv_tau_bar, [&](int k) { return noise[k]; }, ycs4);
+  d_relax_with<NOISE, UNIT>(P, m, rho_k, v_b, u, a, inv_tau_bar, [&](int k) { return noise[k]; }, ycs4);
 }
 // relaxation of one fluid with the generated stream: n3 = its momentum-mode noise (fn3 or -fn3), s = A.sr / A.sp.
 // The fluid's 15 normals are drawn first (their 15 table look-ups are in flight together) and scaled where they are added.
@@ -456,8 +472,9 @@ __device__ __forceinline__ void d_barycentric(double rho, double phi, const Site
 }
 
 // collide (LBM_binary.H:451-516): fs,gs are replaced by the post-collision populations.
-// NOISE=false drops the noise terms (they are exactly +-0 when kBT == 0).
-template <bool NOISE>
+// NOISE=false drops the noise terms (they are exactly +-0 when kBT == 0); UNIT: see d_relax_with.  (No kernel calls
+// d_collide any more -- they relax the two fluids apart, around their stores -- so neither form of it is instantiated.)
+template <bool NOISE, bool UNIT = false>
 __device__ __forceinline__ void d_collide(const DevParams& P, double (&fs)[Q], double (&gs)[Q],
                                           double rho, double phi, const SiteHydro& H,
                                           const double (&fn)[Q], const double (&gn)[Q], const SiteRecip& R) {
@@ -466,13 +483,13 @@ __device__ __forceinline__ void d_collide(const DevParams& P, double (&fs)[Q], d
   {
     double m[Q];
     d_moments(fs, m);
-    d_relax<NOISE>(P, m, rho, v_b, H.uf, H.af, P.inv_tau_f_bar, fn, R.cs4);
+    d_relax<NOISE, UNIT>(P, m, rho, v_b, H.uf, H.af, P.inv_tau_f_bar, fn, R.cs4);
     d_populations(m, fs);
   }
   {
     double m[Q];
     d_moments(gs, m);
-    d_relax<NOISE>(P, m, phi, v_b, H.ug, H.ag, P.inv_tau_g_bar, gn, R.cs4);
+    d_relax<NOISE, UNIT>(P, m, phi, v_b, H.ug, H.ag, P.inv_tau_g_bar, gn, R.cs4);
     d_populations(m, gs);
   }
 }
