@@ -62,6 +62,12 @@ constexpr int HO_SPREAD_F1 = 44;     // noise kernel
 // processes each): 28 +3.3 / +1.8 %, 33 +2.7 / +1.4 % against the generic ragged kernel, so that instantiation keeps 28.
 constexpr int HO_SPREAD_FU = 33;       // full tiles
 constexpr int HO_SPREAD_FU_RAG = 28;   // ragged tiles
+// Outputs of fluid g that the full-tile unit-rate kernel stores one march position later (see the stores in front of the barrier in
+// bflbm_handover_body.inc).  The last four that finish_fluid forms (11..14, the yz diagonals) are stored at once: they are
+// younger than the last request of the g half, so the waits at the loop head stay vmcnt(4) and above and cover loads only
+// (with none kept the head ended in vmcnt(0) on the row's frame store).  512^3, MLUPS against the parent's 8745-8773 on the
+// same box: kept 1: 8935, 2: 9019-9030, 3: 9054, 4: 9037, 6: 8998, 9: 8953.
+constexpr bool ho_g_deferred(int i) { return i < 11 || i > 14; }
 
 template <int TY> struct HoLayout {
   static constexpr int TX = 64;

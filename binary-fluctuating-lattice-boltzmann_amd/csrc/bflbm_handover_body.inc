@@ -173,6 +173,10 @@
     }
   };
   double nf[Q], ng[Q], hvn[2][4];                            // the plane in flight
+  // Deferred g stores (full-tile unit-rate kernel): in the steady state the outputs of fluid g wait in registers and are stored
+  // by the NEXT position, as one run in front of its barrier; see the comment at the stores
+  constexpr bool DEFER_G = UNIT && MODE == 0 && !RAG;
+  double dg[Q];                                              // outputs of fluid g of the previous position that are not stored yet
   pull_plane(qa - 1, nf, ng, hvn);
   // The first plane is waited for here, outside the loop: the wait at the loop head is then computed from the
   // back edge alone, where the stores of the previous position are younger than every load it needs, and no
@@ -185,8 +189,10 @@
   // instances, so that the steady-state loop has a single path of memory operations: the compiler's wait at the
   // loop head is then the one the back edge needs -- the loads, not the 19 stores issued after them (it was
   // vmcnt(0): the join with the paths that end in loads).
-  auto position = [&](const int q, auto col_c, auto ldn_c) {
+  // pend_c: the previous position left its g outputs in dg; keep_c: this position leaves its own there (DEFER_G only)
+  auto position = [&](const int q, auto col_c, auto ldn_c, auto pend_c, auto keep_c) {
     constexpr bool do_collide = decltype(col_c)::value, load_next = decltype(ldn_c)::value;
+    constexpr bool pending = decltype(pend_c)::value, keep = decltype(keep_c)::value;
     // steady state: the own loads of the f half are spread over the relaxation of f (below)
     constexpr bool spread_f = do_collide && load_next;
     const int slot = it & 3;
@@ -242,6 +248,22 @@
         __builtin_amdgcn_sched_barrier(0);
         rp[slot][0][ry * LW + rx] = density(t[0]);
         rp[slot][1][ry * LW + rx] = density(t[1]);
+      }
+    }
+    // The deferred outputs of fluid g of plane q-2 go out here: the loads of plane q have all arrived (the density sums above
+    // consumed them), the wave issues nothing else until the f half is requested behind the barrier, and the request queue is
+    // empty.  In the tail of the previous position the same stores stood between 130 VALU instructions behind the burst of g
+    // requests.  512^3, interleaved processes, five each: 8660 -> 8896 MLUPS (+2.7 %; +3.4 % on the box of the scan), 256^3
+    // +2.2 %; the same stores behind the barrier -3.5 %, over the hold swap +0.2 ... +0.7 %, at the top of the position +1.6 %
+    // (NOTES.md section 3.1g, profiles/request_placement_ab.txt).
+    if (pending) {
+      double* __restrict__ Dq = D + (long long)wrapp(q - 2) * G.plane + (long long)Q * G.vol;
+      unsigned oq = yo[1] + xo[1];
+#pragma unroll
+      for (int i = 0; i < Q; ++i) {
+        if (!ho_g_deferred(i)) continue;
+        asm volatile("" : "+v"(oq));                           // keeps the store in its place among the memory operations around it
+        __builtin_nontemporal_store(dg[i], reinterpret_cast<double*>(reinterpret_cast<char*>(Dq + (long long)i * G.vol) + oq));
       }
     }
     __syncthreads();
@@ -307,13 +329,14 @@
       // sorts the 19 outputs of one fluid by destination and advances the z pipelines (see the header comment)
       // moments -> populations from the same terms as d_populations; a group of three populations that share a
       // destination (dy,dz) is stored and folded into its x bucket right after it is formed
-      auto finish_fluid = [&](const double (&mom)[Q], const int k) {
+      auto finish_fluid = [&](const double (&mom)[Q], const int k, auto later_c) {
         PopTerms T;
         d_population_terms(mom, T);
         double* __restrict__ Dk = Dp + (long long)(k * Q) * G.vol;
         // population stores carry the non-temporal hint (round 4: +0.9 % at 512^3, +0.6 % at 256^3, +1.6 % with noise, runs agreeing to
         // 0.1 %: the written lines are not read again before the next step, the L2 keeps the neighbours' shared lines instead)
         auto put = [&](int i, double v) {
+          if (decltype(later_c)::value && ho_g_deferred(i)) { dg[i] = v; return; }     // stored by the next position
           if (active) __builtin_nontemporal_store(v, reinterpret_cast<double*>(reinterpret_cast<char*>(Dk + (long long)i * G.vol) + o));
         };
         // x shifts see zeros from the idle lanes of a narrow tile (they hold a duplicate of the last site)
@@ -408,11 +431,11 @@
           __builtin_amdgcn_sched_group_barrier(0x002, MODE == 1 ? HO_SPREAD_F1 : (UNIT ? (RAG ? HO_SPREAD_FU_RAG : HO_SPREAD_FU) : HO_SPREAD_F), 0);      // then this many VALU instructions
         }
       }
-      finish_fluid(mf, 0);
+      finish_fluid(mf, 0, std::false_type{});
       if (load_next) pull_plane(q + 1, nf, ng, hvn, 2);       // the g half of the next plane: spreads the requests over the march position (+2.9 % at 512^3)
       if (MODE == 1) d_relax_generated(P, mg, ph, v_b, Hy.ug, Hy.ag, P.inv_tau_g_bar, gn3, NA.sp, ntab, rst, R.cs4);
       else           d_relax<false, UNIT>(P, mg, ph, v_b, Hy.ug, Hy.ag, P.inv_tau_g_bar, zn, R.cs4);
-      finish_fluid(mg, 1);
+      finish_fluid(mg, 1, std::bool_constant<keep>{});
     } else if (load_next) {
       // the first two positions of a chunk collide nothing: the g half goes now, and is waited for here (as in
       // the prologue: keeps vmcnt(0) out of the loop head)
@@ -420,12 +443,25 @@
       __builtin_amdgcn_s_waitcnt(0x0F70);
     }
   };
-  using std::bool_constant;
+  using T_ = std::true_type; using F_ = std::false_type;
   {
     int q = qa - 1;                                          // qb >= qa + 1: both leading positions request a plane
-    for (int k = 0; k < 2; ++k, ++q, ++it) position(q, bool_constant<false>{}, bool_constant<true>{});
-    for (; q < qb; ++q, ++it) position(q, bool_constant<true>{}, bool_constant<true>{});
-    position(qb, bool_constant<true>{}, bool_constant<false>{});
+    for (int k = 0; k < 2; ++k, ++q, ++it) position(q, F_{}, T_{}, F_{}, F_{});
+    if constexpr (DEFER_G) {
+      // the first steady-state position finds nothing pending (its own instance, so that the loop keeps a single path of
+      // memory operations); the last position of the chunk stores what the loop left and its own outputs at once
+      if (q < qb) {
+        position(q, T_{}, T_{}, F_{}, T_{});
+        ++q; ++it;
+        for (; q < qb; ++q, ++it) position(q, T_{}, T_{}, T_{}, T_{});
+        position(qb, T_{}, F_{}, T_{}, F_{});
+      } else {
+        position(qb, T_{}, F_{}, F_{}, F_{});
+      }
+    } else {
+      for (; q < qb; ++q, ++it) position(q, T_{}, T_{}, F_{}, F_{});
+      position(qb, T_{}, F_{}, F_{}, F_{});
+    }
     ++it;
   }
   // the last complete plane (qb-2) was finished at the last position; combine it across rows
