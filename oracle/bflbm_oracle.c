@@ -12,19 +12,19 @@
  * this library, and only as the checker / reported baseline.  The product path
  * (binary-fluctuating-lattice-boltzmann_amd/csrc) never links or calls it.
  *
- * PINNING: the reference cannot be compiled in this image (it needs AMReX, an
- * external library that is absent; writing stand-in headers is not allowed), and
- * it ships no golden vectors.  The oracle is pinned by outputs of the reference
+ * PINNING: by the reference's own compiled code -- oracle/ref_harness compiles LBM_d3q19.H and LBM_binary.H
+ * unmodified against a small stand-in for the AMReX names they use (g++ -O2 -ffp-contract=off, no -march);
+ * tests/test_reference_pins.py holds every function of this file to that build's output, from committed fixtures
+ * (tests/golden/reference_*.npz) and live where oracle/_ref/ is built, tau != 1/2 and both noise branches included
+ * (DESIGN.md section 4).  Beyond that the oracle is pinned by outputs of the reference
  * that its authors recorded in the notebooks under /root/reference: Flat_Interface.ipynb
  * cell 4 (interface height 47.86628666 at 8x256x64, frame 2000), Surface_Tension.ipynb cells
  * 13-19 (36 densities with 16 digits, force integrals, fitted radii and both Laplace-law surface
  * tensions of nine 32^3 droplets at frame 20000) and Droplet_Fluctuation.ipynb cell 5 (centre of
  * mass after 20000 steps) -- tests/test_oracle_pins.py, tests/test_gpu_notebook_surface_tension.py,
  * tests/test_gpu_fullsize.py -- and by algebraic identities of the D3Q19 basis.  All of those runs
- * used tau = 1/2 (full relaxation); for tau != 1/2 see DESIGN.md section 4 (parity unpinned by any
- * recorded reference number; invariant tests instead).  The three numbers of SURVEY.md section 8c
- * (8^3 stripe, 10 steps) are kept as a regression check only: they came from a survey-time build of the
- * reference headers against stand-in AMReX types and pin nothing by themselves.
+ * used tau = 1/2 (full relaxation).  The three numbers of SURVEY.md section 8c (8^3 stripe, 10 steps) are
+ * what oracle/_ref/ref_main prints for that case.
  * The Gaussian random stream (amrex::RandomNormal) is an un-vendored dependency:
  * noise parity with the reference is statistical only ("parity unpinned" at the
  * RNG boundary); this file defines the project's own counter-based stream.
@@ -333,7 +333,8 @@ static void thermal_noise_impl(const orc_params* p, int nx, int ny, int nz, int 
      * a = 4..18.  The reference interleaves f,g draws (:124-127), which is immaterial for an i.i.d. stream.
      * Amplitudes (:117, :125-126): sqrt(c kBT |rho phi/rhot|) and sqrt(c kBT/cs2 b[a] |rho|), the latter
      * evaluated as sqrt(c kBT/cs2 b[a]) * sqrt(|rho|) -- within 2 ulp of it (tests/test_oracle_pins.py) with 3 instead of 31 square
-     * roots per site; project-defined like the stream (the generated noise is pinned statistically only). */
+     * roots per site.  With the same normals in the reference's call order the field is within 6.5 ulp of the one
+     * the reference's compiled thermal_noise writes (measured 3; tests/test_reference_pins.py). */
     fn[IDX(nx,ny,nz,0,x,y,z)] = 0.;
     gn[IDX(nx,ny,nz,0,x,y,z)] = 0.;
     for (int a = 1; a <= 3; a++) {
@@ -518,6 +519,42 @@ static void phi_moments(const orc_params* p, double rho, const double u[3], cons
   mEq[8] = modifactor*cs4*(AD[1][2] + AD[2][1]);
   mEq[9] = modifactor*cs4*(AD[0][2] + AD[2][0]);
   for (int k = 10; k < Q; ++k) mEq[k] = 0.;
+}
+
+/* The site functions above by themselves, for tests/test_reference_pins.py (unit fixtures of the reference's own
+ * compiled code).  fields = {rho, phi}; field_index selects one, as in the reference's signatures. */
+void orc_equilibrium_moments(const orc_params* p, const double* fields, int field_index, const double* u, double* mEq) {
+  equilibrium_moments(p, fields[field_index], u, mEq);
+}
+void orc_phi_moments(const orc_params* p, const double* fields, int field_index, const double* u, const double* a, double* mEq) {
+  phi_moments(p, fields[field_index], u, a, mEq);
+}
+/* gradient of component icomp of a periodic field at every site -> out[3][z][y][x] */
+void orc_gradient_field(const orc_params* p, int nx, int ny, int nz, const double* field, int icomp, double* out) {
+  for (int z = 0; z < nz; ++z) for (int y = 0; y < ny; ++y) for (int x = 0; x < nx; ++x) {
+    double g[3];
+    gradient(p, nx,ny,nz, x,y,z, field, icomp, g);
+    for (int d = 0; d < 3; ++d) out[IDX(nx,ny,nz,d,x,y,z)] = g[d];
+  }
+}
+/* grad_laplacian_2nd, LBM_binary.H:170-194.  The step does not use it (see orc_hydrovars); restated for the unit
+ * fixtures only.  Neighbours of neighbours: the index is wrapped after each of the two offsets. */
+void orc_grad_laplacian_2nd_field(const orc_params* p, int nx, int ny, int nz, const double* field, int icomp, double* out) {
+  for (int z = 0; z < nz; ++z) for (int y = 0; y < ny; ++y) for (int x = 0; x < nx; ++x) {
+    double g[3] = {0.0, 0.0, 0.0};
+    for (int dir = 0; dir < 3; dir++) {
+      for (int i = 0; i < Q; i++) {
+        for (int j = 0; j < Q; j++) {
+          int xc = wrap(x + C[j][0], nx), yc = wrap(y + C[j][1], ny), zc = wrap(z + C[j][2], nz);
+          int xp = wrap(xc + C[i][0], nx), yp = wrap(yc + C[i][1], ny), zp = wrap(zc + C[i][2], nz);
+          double nb = field[IDX(nx,ny,nz,icomp,xp,yp,zp)];
+          double ce = field[IDX(nx,ny,nz,icomp,xc,yc,zc)];
+          g[dir] += 2.*W[i]*W[j]/p->cs4*(nb - ce)*C[j][dir];
+        }
+      }
+    }
+    for (int d = 0; d < 3; ++d) out[IDX(nx,ny,nz,d,x,y,z)] = g[d];
+  }
 }
 
 /* collide, LBM_binary.H:451-516 -- in place on f,g at every site */

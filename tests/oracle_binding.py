@@ -60,6 +60,58 @@ def populations(m):
     return f
 
 
+def equilibrium_moments(fields, field_index, u, params=None):
+    p = params if params is not None else default_params()
+    fields, u = (np.ascontiguousarray(x, dtype=np.float64) for x in (fields, u))
+    m = np.empty(Q)
+    lib().orc_equilibrium_moments(ctypes.byref(p), _p(fields), int(field_index), _p(u), _p(m))
+    return m
+
+
+def phi_moments(fields, field_index, u, a, params=None):
+    p = params if params is not None else default_params()
+    fields, u, a = (np.ascontiguousarray(x, dtype=np.float64) for x in (fields, u, a))
+    m = np.empty(Q)
+    lib().orc_phi_moments(ctypes.byref(p), _p(fields), int(field_index), _p(u), _p(a), _p(m))
+    return m
+
+
+def _field_operator(name, field, params):
+    p = params if params is not None else default_params()
+    field = np.ascontiguousarray(field, dtype=np.float64)
+    nz, ny, nx = field.shape
+    out = np.empty((3, nz, ny, nx))
+    getattr(lib(), name)(ctypes.byref(p), nx, ny, nz, _p(field), 0, _p(out))
+    return out
+
+
+def gradient(field, params=None):
+    """gradient (LBM_binary.H:134-150) of a periodic scalar field (nz, ny, nx) at every site -> (3, nz, ny, nx)."""
+    return _field_operator("orc_gradient_field", field, params)
+
+
+def grad_laplacian_2nd(field, params=None):
+    return _field_operator("orc_grad_laplacian_2nd_field", field, params)
+
+
+def thermal_noise(n, params, rho, phi, noise_index=0, ref=None, rel=(0.0, 0.0, 0.0)):
+    """The oracle's generated noise on given densities; ref = (rho_eq, phi_eq, rhot_eq): the USE_REF_STATE branch with
+    pos_com_relative = rel.  -> fn, gn (19, nz, ny, nx)."""
+    nx, ny, nz = n
+    fn = np.zeros((Q, nz, ny, nx))
+    gn = np.zeros((Q, nz, ny, nx))
+    if ref is None:
+        hbar = np.zeros((15, nz, ny, nx))
+        hbar[0], hbar[1] = rho, phi
+        lib().orc_thermal_noise(ctypes.byref(params), nx, ny, nz, _p(hbar), ctypes.c_uint32(noise_index), _p(fn), _p(gn))
+    else:
+        r = [np.ascontiguousarray(a, dtype=np.float64) for a in ref]
+        rel = np.ascontiguousarray(rel, dtype=np.float64)
+        lib().orc_thermal_noise_ref_slab(ctypes.byref(params), nx, ny, nz, 0, nz, _p(r[0]), _p(r[1]), _p(r[2]), _p(rel),
+                                         ctypes.c_uint32(noise_index), _p(fn), _p(gn))
+    return fn, gn
+
+
 def lattice_tables():
     c = np.empty((Q, 3), dtype=np.int32)
     w = np.empty(Q)
@@ -160,6 +212,14 @@ class OracleLattice:
                            _p(self.f), _p(self.g), _p(self._ft), _p(self._gt),
                            _p(self.hbar), _p(self.fn), _p(self.gn), _p(self.h))
         self.steps += 1
+
+    def set_noise(self, fn, gn):
+        """Replace the current noise moments and make hydrovs consistent with them (LBM_hydrovars reads modes 1..3)."""
+        nx, ny, nz = self.n
+        self.fn[...] = fn
+        self.gn[...] = gn
+        lib().orc_hydrovars(ctypes.byref(self.p), nx, ny, nz, _p(self.f), _p(self.g), _p(self.hbar),
+                            _p(self.fn), _p(self.gn), _p(self.h))
 
     def timestep_injected(self, fn, gn, fn_next=None, gn_next=None):
         """Collide with the given noise moments, stream, then refresh with fn_next/gn_next
