@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("BFLBM_LIB", os.path.join(_HERE, "csrc", "libbflbm.so"
 NVEL = 19
 NHYDRO = 22
 NHYDROBAR = 9
+TRACE_NREC = 12
 HALO_STATE, HALO_NEXT, HALO_UPLOAD = 0, 1, 2
 
 
@@ -111,6 +112,13 @@ SIGNATURES = {
     "bflbm_batch_resolved_schedule": (ctypes.c_int, [_vp, _P(ctypes.c_int)]),
     "bflbm_batch_step": (ctypes.c_int, [_vp, ctypes.c_int]),
     "bflbm_batch_sync": (ctypes.c_int, [_vp]),
+    "bflbm_trace_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, _P(_vp)]),
+    "bflbm_batch_trace_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, _P(_vp)]),
+    "bflbm_trace_destroy": (ctypes.c_int, [_vp]),
+    "bflbm_trace_sample": (ctypes.c_int, [_vp]),
+    "bflbm_trace_reset": (ctypes.c_int, [_vp]),
+    "bflbm_trace_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
+    "bflbm_trace_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp]),
     "bflbm_set_ref_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(Fab)]),
     "bflbm_enable_ref_state": (ctypes.c_int, [_vp, ctypes.c_int, _dp]),
     "bflbm_ref_state_active": (ctypes.c_int, [_vp, _P(ctypes.c_int)]),

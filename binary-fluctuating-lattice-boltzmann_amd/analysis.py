@@ -74,6 +74,20 @@ def principal_axes(rho_xyz, radius):
     return axes, ev, vec
 
 
+def msd(r, max_lag):
+    """Mean squared displacement of trajectories r[..., T, 3] (e.g. Trace.com() with the time axis moved next to last):
+    msd[..., k] = mean over t of |r[t + k] - r[t]|^2 over all frame pairs of lag k = 0 ... max_lag (msd[..., 0] = 0)."""
+    r = np.asarray(r, dtype=np.float64)
+    nt = r.shape[-2]
+    if not 0 <= max_lag < nt:
+        raise ValueError(f"msd: max_lag {max_lag} needs more than {nt} frames")
+    out = np.zeros(r.shape[:-2] + (max_lag + 1,))
+    for k in range(1, max_lag + 1):
+        d = r[..., k:, :] - r[..., :nt - k, :]
+        out[..., k] = (d * d).sum(axis=-1).mean(axis=-1)
+    return out
+
+
 # ---- the same observables from the device-reduced raw moments (BinaryLBM.droplet_moments) ----------------
 # m[0:10] = sum rho {1, x, y, z, xx, xy, xz, yy, yz, zz} in cell indices, m[10:20] trapezoid-weighted.
 

@@ -125,11 +125,19 @@ struct bflbm_ctx {
   double com[3] = {0., 0., 0.}; // global centre of mass (update_com) of the resident state
   bool com_valid = false;
   bflbm_batch* batch = nullptr; // non-null: a replica view owned by this batch (bflbm_batch_replica)
+  bflbm_trace* trace = nullptr; // the trace attached to this lone context (bflbm_trace.h); it outlives the context detached
   bool record_stale = true;     // a view: its batch record (parameters, buffers, step counter) must be written again
   // what describes the resident state, and what was derived from it, is reset by the transitions below (state_replaced ...)
 };
 
 namespace {
+
+// the owner's side of an ensemble trace (bflbm_trace.h): would the samples of `nsteps` more steps overflow it; one step
+// was taken through the owner (samples when due); the owner goes away
+bool trace_overflows(const bflbm_trace* t, long long nsteps);
+int trace_after_step(bflbm_trace* t);
+void trace_detach(bflbm_trace* t);
+#define BFLBM_REFUSE_TRACE_FULL(t, call, nsteps) do { if ((t) && trace_overflows(t, nsteps)) return fail("%s: trace full: the samples of %lld more step(s) do not fit (read it and bflbm_trace_reset, or create a larger one)", call, (long long)(nsteps)); } while (0)
 
 dim3 plane_grid(const bflbm_ctx* c, int nplanes) {
   return dim3((unsigned)((c->G.plane + 255) / 256), (unsigned)nplanes, 1);
@@ -656,6 +664,7 @@ int bflbm_destroy(bflbm_ctx* c) {
   if (!c) return 0;
   BFLBM_REFUSE_VIEW(c, "bflbm_destroy", "the batch owns it: use bflbm_batch_destroy");
   hipSetDevice(c->dom.device);
+  if (c->trace) trace_detach(c->trace);
   if (c->stream && c->own_stream) hipStreamSynchronize(c->stream);
   if (c->S[0]) hipFree(c->S[0]);                 // S[1] lives in the same allocation
   if (c->frames[0]) hipFree(c->frames[0]);
@@ -866,6 +875,7 @@ int bflbm_step_boundary(bflbm_ctx* c) {
   if (!c) return fail("null context");
   BFLBM_REFUSE_VIEW(c, "bflbm_step_boundary", "use bflbm_batch_step");
   if (c->step_open()) return fail("step already open");
+  BFLBM_REFUSE_TRACE_FULL(c->trace, "bflbm_step_boundary", 1);
   HIP_TRY(hipSetDevice(c->dom.device));
   if (prepare_ref(c)) return 1;
   const int sch = frames_for_next_step(c, true);
@@ -890,7 +900,7 @@ int bflbm_step_finish(bflbm_ctx* c) {
   BFLBM_REFUSE_VIEW(c, "bflbm_step_finish", "use bflbm_batch_step");
   if (!c->step_open()) return fail("no open step");
   state_advanced(c);
-  return 0;
+  return c->trace ? trace_after_step(c->trace) : 0;
 }
 
 int bflbm_step(bflbm_ctx* c, int nsteps) {
@@ -898,6 +908,7 @@ int bflbm_step(bflbm_ctx* c, int nsteps) {
   BFLBM_REFUSE_VIEW(c, "bflbm_step", "use bflbm_batch_step");
   if (nsteps < 0) return fail("nsteps < 0");
   if (!c->G.zwrap && nsteps > 1) return fail("bflbm_step: nranks > 1 needs a halo exchange between steps; use nsteps == 1");
+  BFLBM_REFUSE_TRACE_FULL(c->trace, "bflbm_step", nsteps);
   for (int s = 0; s < nsteps; ++s) if (bflbm_step_boundary(c) || bflbm_step_interior(c) || bflbm_step_finish(c)) return 1;
   return 0;
 }
@@ -1493,6 +1504,7 @@ struct bflbm_batch {
   BatchRec* d_rec = nullptr;            // per-replica records read by the kernels
   BatchRec* h_rec = nullptr;            // pinned host copy of what was uploaded
   long long k = 0;                      // batch steps since the records were written
+  bflbm_trace* trace = nullptr;         // the trace attached to this batch (bflbm_trace.h)
 };
 
 namespace {
@@ -1586,6 +1598,7 @@ int bflbm_batch_destroy(bflbm_batch* b) {
   if (!b) return 0;
   hipSetDevice(b->device);
   if (b->stream) hipStreamSynchronize(b->stream);
+  if (b->trace) trace_detach(b->trace);
   for (bflbm_ctx* c : b->ctx) { c->batch = nullptr; bflbm_destroy(c); }
   if (b->d_rec) hipFree(b->d_rec);
   if (b->h_rec) hipHostFree(b->h_rec);
@@ -1630,6 +1643,7 @@ int bflbm_batch_step(bflbm_batch* b, int nsteps) {
     return fail("bflbm_batch_step: replicas %s have kBT == 0 and replicas %s kBT != 0; a batch steps all replicas with noise or none",
                 replica_list(quiet).c_str(), replica_list(noisy).c_str());
   for (const bflbm_ctx* c : b->ctx) if (c->step_open()) return fail("bflbm_batch_step: a replica has an open step");
+  BFLBM_REFUSE_TRACE_FULL(b->trace, "bflbm_batch_step", nsteps);
   if (nsteps == 0) return 0;
   HIP_TRY(hipSetDevice(b->device));
   const int sch = batch_resolved(b);
@@ -1644,6 +1658,7 @@ int bflbm_batch_step(bflbm_batch* b, int nsteps) {
     if (e != hipSuccess) return fail("bflbm_batch_step: launch failed: %s", hipGetErrorString(e));
     b->k += 1;
     for (bflbm_ctx* c : b->ctx) state_advanced(c);
+    if (b->trace && trace_after_step(b->trace)) return 1;
   }
   return 0;
 }
@@ -1660,3 +1675,4 @@ int bflbm_batch_sync(bflbm_batch* b) {
 #include "bflbm_sf.h"
 #include "bflbm_sf_ring.h"
 #include "bflbm_droplet.h"
+#include "bflbm_trace.h"

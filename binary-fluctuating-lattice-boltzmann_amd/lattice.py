@@ -104,6 +104,65 @@ class _DropletMixin:
         return tuple(res)
 
 
+class Trace:
+    """Droplet moments of every replica recorded on the device every `every` steps through the owner (a lone
+    single-slab BinaryLBM or a BatchLBM) and read once: include/bflbm.h, "Ensemble traces".  Made by owner.trace()."""
+
+    def __init__(self, owner, create, every, capacity, threshold):
+        self.lib, self.owner = owner.lib, owner
+        h = ctypes.c_void_p()
+        thr = -np.inf if threshold is None else float(threshold)
+        check(getattr(self.lib, create)(owner._h, int(every), int(capacity), thr, ctypes.byref(h)))
+        self._h = h
+        if not hasattr(owner, "_dependents"):
+            owner._dependents = []
+        owner._dependents.append(self)               # closed before the owner it reads
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.bflbm_trace_destroy(self._h)
+            self._h = None
+            deps = getattr(self.owner, "_dependents", [])
+            if self in deps:
+                deps.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sample(self):
+        """Record the resident state now (e.g. frame 0); the every-counter does not move."""
+        check(self.lib.bflbm_trace_sample(self._h))
+
+    def reset(self):
+        """Forget the samples and restart the every-counter."""
+        check(self.lib.bflbm_trace_reset(self._h))
+
+    def _count(self):
+        n, b = ctypes.c_longlong(), ctypes.c_int()
+        check(self.lib.bflbm_trace_count(self._h, ctypes.byref(n), ctypes.byref(b)))
+        return n.value, b.value
+
+    @property
+    def count(self):
+        return self._count()[0]
+
+    def read(self):
+        """(steps[count, B] int64, rec[count, B, 12]); synchronises the owner's stream."""
+        n, b = self._count()
+        steps = np.empty((n, b), dtype=np.int64)
+        rec = np.empty((n, b, _lib.TRACE_NREC))
+        check(self.lib.bflbm_trace_read(self._h, 0, n, _ptr(rec), _ptr(steps)))
+        return steps, rec
+
+    def com(self):
+        """Centre of mass [count, B, 3] in cell indices of the cells above the threshold."""
+        rec = self.read()[1]
+        return rec[..., 1:4] / rec[..., 0:1]
+
+
 # kernel schedules of include/bflbm.h (bflbm_set_schedule): "fused" = plane march with the ring densities pulled
 # (bit-exact), "handover" = plane march with the ring densities handed over from the previous step (tolerance)
 SCHEDULES = {"two_pass": 0, "fused": 1, "fused_exact": 1, "auto": 2, "handover": 3}
@@ -319,6 +378,10 @@ class BinaryLBM(_DropletMixin):
         check(self.lib.bflbm_inject_noise(self._h, _ptr(fn), _ptr(gn), ctypes.byref(fab)))
 
     # -- reductions -------------------------------------------------------------------------
+    def trace(self, every, capacity, threshold=None):
+        """Record the droplet moments of the cells with rho > threshold (None: every cell) after every `every`-th step."""
+        return Trace(self, "bflbm_trace_create", every, capacity, threshold)
+
     def com_sums(self):
         s = (ctypes.c_double * 4)()
         check(self.lib.bflbm_com_sums(self._h, s))
@@ -615,6 +678,8 @@ class BatchLBM:
 
     def close(self):
         if getattr(self, "_h", None):
+            for d in list(getattr(self, "_dependents", [])):      # the batch's trace
+                d.close()
             for s in self.replicas:
                 for d in list(getattr(s, "_dependents", [])):
                     d.close()
@@ -650,6 +715,11 @@ class BatchLBM:
 
     def sync(self):
         check(self.lib.bflbm_batch_sync(self._h))
+
+    def trace(self, every, capacity, threshold=None):
+        """Record every replica's droplet moments (cells with rho > threshold; None: every cell) after every `every`-th
+        batch step."""
+        return Trace(self, "bflbm_batch_trace_create", every, capacity, threshold)
 
     # -- stacked getters: a leading replica axis ------------------------------------------------
     def populations(self):

@@ -264,6 +264,52 @@ int bflbm_batch_resolved_schedule(const bflbm_batch* b, int* schedule);
 int bflbm_batch_step(bflbm_batch* b, int nsteps);
 int bflbm_batch_sync(bflbm_batch* b);
 
+/* ---- Ensemble traces: droplet moments of every replica recorded on the device, read once at the end (the notebooks
+ * observe their ensembles every step: nine 32^3 droplets in Surface_Tension.ipynb, a 64^3 droplet's centre of mass 3201
+ * times in Droplet_Fluctuation.ipynb, whose estimator where(rho > 0.06, rho, 0) is threshold = 0.06).
+ * A trace is attached to one lone single-slab context or one replica batch.  After every `every`-th step taken through
+ * its owner it enqueues, on the owner's stream and without a host synchronisation, a reduction of the resident state of
+ * every replica into the next slot of a device buffer of `capacity` samples.
+ *  - record: BFLBM_TRACE_NREC = 12 doubles per replica and sample; rho is the f-density of the resident state at the
+ *    cell (the double bflbm_get_hydrovsbar component 0 holds), x, y, z are cell indices:
+ *      [0..9]  sum over the cells with rho > threshold of rho * {1, x, y, z, xx, xy, xz, yy, yz, zz}
+ *              (the order of bflbm_droplet_moments)
+ *      [10]    sum of rho over all cells
+ *      [11]    number of cells with rho > threshold, as a double
+ *    threshold = -INFINITY takes every cell; a NaN threshold is refused.
+ *  - order: the sums are added in the order of bflbm_droplet_moments: blocks of 256 consecutive sites of the padded
+ *    plane by a binary tree, per plane every thread a 256-strided subsequence of the block sums and the same tree, then
+ *    the planes 0 ... nz-1 in sequence.  With threshold = -INFINITY entries 0..9 equal bflbm_droplet_moments[0..9] of the
+ *    same state bit for bit, entry 10 equals entry 0 and entry 11 is nx ny nz.  A record does not depend on the number
+ *    of replicas, on the schedule, or on whether the lattice is a replica or a lone context.
+ *  - sampling rule: the trace counts the steps taken through its owner (bflbm_step and the split-step calls, sampled
+ *    inside bflbm_step_finish; bflbm_batch_step, sampled after each step's launches) since its creation or reset, and
+ *    samples after a step when that count is a multiple of `every`.  bflbm_trace_sample records the resident state now
+ *    (e.g. frame 0) without moving the count; bflbm_trace_reset forgets the samples and restarts the count.  Every sample
+ *    is labelled on the host with each replica's step counter, so bflbm_set_step_count on one view shifts only that
+ *    replica's labels.  A trace only reads the resident state: it works with every schedule and every kind of noise,
+ *    follows bflbm_set_stream and changes nothing its owner computes or keeps.
+ *  - capacity: bflbm_step, bflbm_batch_step and bflbm_step_boundary first work out how many samples the call would add;
+ *    if they do not fit, the call is refused before any launch ("trace full"), state and step counters untouched.
+ *    bflbm_trace_sample on a full trace is refused the same way.
+ *  - refused at creation (non-zero return, nothing allocated): null arguments, every < 1, capacity < 1, a NaN threshold,
+ *    a context with nranks > 1, a replica view (use bflbm_batch_trace_create), an owner that already has a trace, an
+ *    open step.  An open step also refuses bflbm_trace_sample, _reset and _read.
+ *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_trace_read, _count and
+ *    _destroy still work, bflbm_trace_sample fails.
+ *  - bflbm_trace_read synchronises the owner's stream; no other call of this group does. */
+typedef struct bflbm_trace bflbm_trace;
+#define BFLBM_TRACE_NREC 12
+int bflbm_trace_create(bflbm_ctx* c, int every, long long capacity, double threshold, bflbm_trace** out);
+int bflbm_batch_trace_create(bflbm_batch* b, int every, long long capacity, double threshold, bflbm_trace** out);
+int bflbm_trace_destroy(bflbm_trace* t);
+int bflbm_trace_sample(bflbm_trace* t);                 /* record the resident state now (e.g. frame 0) */
+int bflbm_trace_reset(bflbm_trace* t);                  /* forget the samples, restart the every-counter */
+int bflbm_trace_count(const bflbm_trace* t, long long* nsamples, int* nreplicas);
+int bflbm_trace_read(bflbm_trace* t, long long first, long long count,
+                     double* rec   /* [count][nreplicas][12] */,
+                     long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
+
 /* Materialise the per-step fields the reference keeps in MultiFabs, for the state
  * after the last completed step:
  *   hydrovsbar comps 0..8  (LBM_hydrovars_density, LBM_binary.H:315-354)
