@@ -11,7 +11,8 @@ from .slab import SlabLattice, LocalSlabRing, slab_bounds
 from . import plotfile
 from . import analysis
 from . import structfact
+from .structfact import BatchStructFact
 from . import run_job
 
-__all__ = ["RingLBM", "BatchLBM", "Trace", "SlabLattice", "LocalSlabRing", "slab_bounds", "BinaryLBM", "default_params", "make_fab", "rng_site_normals", "BflbmError",
+__all__ = ["RingLBM", "BatchLBM", "Trace", "BatchStructFact", "SlabLattice", "LocalSlabRing", "slab_bounds", "BinaryLBM", "default_params", "make_fab", "rng_site_normals", "BflbmError",
            "Params", "Domain", "Fab", "NVEL", "NHYDRO", "NHYDROBAR"]

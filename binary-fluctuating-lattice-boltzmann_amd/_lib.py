@@ -119,6 +119,14 @@ SIGNATURES = {
     "bflbm_trace_reset": (ctypes.c_int, [_vp]),
     "bflbm_trace_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
     "bflbm_trace_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp]),
+    "bflbm_batch_sf_create": (ctypes.c_int, [_vp, ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), _dp, ctypes.c_int, ctypes.c_int, _P(_vp)]),
+    "bflbm_batch_sf_destroy": (ctypes.c_int, [_vp]),
+    "bflbm_batch_sf_reset": (ctypes.c_int, [_vp]),
+    "bflbm_batch_sf_accumulate": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "bflbm_batch_sf_nsamples": (ctypes.c_int, [_vp, _P(ctypes.c_longlong)]),
+    "bflbm_batch_sf_get": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "bflbm_batch_get_hydrovs": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "bflbm_batch_get_hydrovsbar": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "bflbm_set_ref_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(Fab)]),
     "bflbm_enable_ref_state": (ctypes.c_int, [_vp, ctypes.c_int, _dp]),
     "bflbm_ref_state_active": (ctypes.c_int, [_vp, _P(ctypes.c_int)]),

@@ -305,11 +305,14 @@ inline int resolved_schedule(const bflbm_ctx* c) {
 inline int own_lo(const bflbm_ctx* c) { return c->G.H; }
 inline int own_hi(const bflbm_ctx* c) { return c->G.H + c->nzl; }
 
+// A density pass over the resident state was enqueued: rho / phi hold its densities (undone by the transitions below).
+void density_computed(bflbm_ctx* c) { c->density_valid = true; }
+
 int ensure_density(bflbm_ctx* c) {
   if (c->density_valid) return 0;
   const int ext = c->G.zwrap ? 0 : 1;
   if (launch_density(c, own_lo(c) - ext, own_hi(c) + ext)) return 1;
-  c->density_valid = true;
+  density_computed(c);
   return 0;
 }
 
@@ -1505,9 +1508,18 @@ struct bflbm_batch {
   BatchRec* h_rec = nullptr;            // pinned host copy of what was uploaded
   long long k = 0;                      // batch steps since the records were written
   bflbm_trace* trace = nullptr;         // the trace attached to this batch (bflbm_trace.h)
+  std::vector<bflbm_batch_sf*> sfs;     // the structure-factor accumulators living on this batch (bflbm_batch_sf.h)
+  double* d_obs = nullptr;              // dense [B][ncomp][nz][ny][nx] of bflbm_batch_get_hydrovs / _hydrovsbar, allocated at first use
+  size_t obs_doubles = 0;
 };
 
 namespace {
+
+// the batch's side of its structure-factor accumulators (bflbm_batch_sf.h): one step was taken through the batch (a frame
+// when due); the batch goes away; the getters' dense buffer
+int batch_sf_after_step(bflbm_batch_sf* s);
+void batch_sf_detach(bflbm_batch_sf* s);
+void batch_obs_free(bflbm_batch* b);
 
 // `auto` of a batch: the rule of exact_quiet_schedule over the whole batch -- the one-pass kernel once the fused
 // workgroups of all replicas fill the compute units, the two-pass schedule otherwise.  Unlike a lone lattice, a batch
@@ -1599,6 +1611,8 @@ int bflbm_batch_destroy(bflbm_batch* b) {
   hipSetDevice(b->device);
   if (b->stream) hipStreamSynchronize(b->stream);
   if (b->trace) trace_detach(b->trace);
+  while (!b->sfs.empty()) batch_sf_detach(b->sfs.back());
+  batch_obs_free(b);
   for (bflbm_ctx* c : b->ctx) { c->batch = nullptr; bflbm_destroy(c); }
   if (b->d_rec) hipFree(b->d_rec);
   if (b->h_rec) hipHostFree(b->h_rec);
@@ -1659,6 +1673,7 @@ int bflbm_batch_step(bflbm_batch* b, int nsteps) {
     b->k += 1;
     for (bflbm_ctx* c : b->ctx) state_advanced(c);
     if (b->trace && trace_after_step(b->trace)) return 1;
+    for (bflbm_batch_sf* s : b->sfs) if (batch_sf_after_step(s)) return 1;
   }
   return 0;
 }
@@ -1676,3 +1691,4 @@ int bflbm_batch_sync(bflbm_batch* b) {
 #include "bflbm_sf_ring.h"
 #include "bflbm_droplet.h"
 #include "bflbm_trace.h"
+#include "bflbm_batch_sf.h"

@@ -21,6 +21,7 @@ namespace {
 struct FftApi {
   void* handle = nullptr;
   hipfftResult (*plan3d)(hipfftHandle*, int, int, int, hipfftType) = nullptr;
+  hipfftResult (*plan_many)(hipfftHandle*, int, int*, int*, int, int, int*, int, int, hipfftType, int) = nullptr;
   hipfftResult (*set_stream)(hipfftHandle, hipStream_t) = nullptr;
   hipfftResult (*exec_d2z)(hipfftHandle, hipfftDoubleReal*, hipfftDoubleComplex*) = nullptr;
   hipfftResult (*destroy)(hipfftHandle) = nullptr;
@@ -38,10 +39,11 @@ int load_fft() {
   }
   if (!g_fft.handle) return fail("hipFFT is not available: %s", dlerror());
   g_fft.plan3d = (decltype(g_fft.plan3d))dlsym(g_fft.handle, "hipfftPlan3d");
+  g_fft.plan_many = (decltype(g_fft.plan_many))dlsym(g_fft.handle, "hipfftPlanMany");
   g_fft.set_stream = (decltype(g_fft.set_stream))dlsym(g_fft.handle, "hipfftSetStream");
   g_fft.exec_d2z = (decltype(g_fft.exec_d2z))dlsym(g_fft.handle, "hipfftExecD2Z");
   g_fft.destroy = (decltype(g_fft.destroy))dlsym(g_fft.handle, "hipfftDestroy");
-  if (!g_fft.plan3d || !g_fft.set_stream || !g_fft.exec_d2z || !g_fft.destroy) {
+  if (!g_fft.plan3d || !g_fft.plan_many || !g_fft.set_stream || !g_fft.exec_d2z || !g_fft.destroy) {
     g_fft.plan3d = nullptr;
     return fail("hipFFT: missing symbols in the loaded library");
   }

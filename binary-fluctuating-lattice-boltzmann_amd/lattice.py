@@ -678,8 +678,8 @@ class BatchLBM:
 
     def close(self):
         if getattr(self, "_h", None):
-            for d in list(getattr(self, "_dependents", [])):      # the batch's trace
-                d.close()
+            for d in list(getattr(self, "_dependents", [])):      # the batch's trace: closed; its structure-factor
+                getattr(d, "_owner_closing", d.close)()           # accumulators: detached by the library, still readable
             for s in self.replicas:
                 for d in list(getattr(s, "_dependents", [])):
                     d.close()
@@ -721,6 +721,11 @@ class BatchLBM:
         batch step."""
         return Trace(self, "bflbm_batch_trace_create", every, capacity, threshold)
 
+    def structfact(self, var_names, **kw):
+        """One structure-factor accumulator for the whole batch (structfact.BatchStructFact; every=k attaches it)."""
+        from .structfact import BatchStructFact
+        return BatchStructFact(self, var_names, **kw)
+
     # -- stacked getters: a leading replica axis ------------------------------------------------
     def populations(self):
         f = np.empty((len(self.replicas), NVEL, self.n[2], self.n[1], self.n[0]))
@@ -730,15 +735,15 @@ class BatchLBM:
         return f, g
 
     def LBM_hydrovars(self, ncomp=NHYDRO):
-        out = np.empty((len(self.replicas), ncomp, self.n[2], self.n[1], self.n[0]))
-        for r, s in enumerate(self.replicas):
-            s.LBM_hydrovars(out[r], ncomp=ncomp)
+        """hydrovs of every replica with one launch and one copy (bflbm_batch_get_hydrovs)."""
+        out = np.empty((len(self.replicas), int(ncomp), self.n[2], self.n[1], self.n[0]))
+        check(self.lib.bflbm_batch_get_hydrovs(self._h, _ptr(out), int(ncomp)))
         return out
 
-    def LBM_hydrovars_density(self):
-        out = np.empty((len(self.replicas), NHYDROBAR, self.n[2], self.n[1], self.n[0]))
-        for r, s in enumerate(self.replicas):
-            s.LBM_hydrovars_density(out[r])
+    def LBM_hydrovars_density(self, ncomp=NHYDROBAR):
+        """hydrovsbar of every replica with one launch and one copy (bflbm_batch_get_hydrovsbar)."""
+        out = np.empty((len(self.replicas), int(ncomp), self.n[2], self.n[1], self.n[0]))
+        check(self.lib.bflbm_batch_get_hydrovsbar(self._h, _ptr(out), int(ncomp)))
         return out
 
 

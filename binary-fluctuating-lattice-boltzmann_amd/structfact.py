@@ -133,3 +133,90 @@ class DeviceStructFact(StructFact):
 
     def magnitude(self, zero_avg=1):
         return self._get(0, zero_avg)
+
+
+class BatchStructFact(StructFact):
+    """One accumulator for all replicas of a BatchLBM (bflbm_batch_sf_*, csrc/bflbm_batch_sf.h): a frame is one
+    observation launch over the batch, one batched hipFFT and one accumulation launch on the batch's stream.  It keeps
+    every replica's spectra and the ensemble mean.  every >= 1 attaches it: batch.LBM_timestep then takes a frame after
+    every `every`-th step through the batch (counted since creation or reset()); fort_structure() takes one now."""
+
+    def __init__(self, batch, var_names, pair_a=PAIR_A, pair_b=PAIR_B, var_scaling=None, lb_hydrovars=False, every=0):
+        import ctypes
+        from . import _lib
+        super().__init__(var_names, pair_a, pair_b, var_scaling)
+        self.batch, self.lb, self.every = batch, bool(lb_hydrovars), int(every)
+        self._ct, self._check, self._libh = ctypes, _lib.check, batch.lib
+        self.n, self.nreplicas = tuple(batch.n), len(batch)
+        n = len(self.pairs)
+        a = (ctypes.c_int * n)(*[p[0] for p in self.pairs])
+        b = (ctypes.c_int * n)(*[p[1] for p in self.pairs])
+        sc = (ctypes.c_double * n)(*[float(v) for v in self.scale])
+        h = ctypes.c_void_p()
+        _lib.check(batch.lib.bflbm_batch_sf_create(batch._h, n, a, b, sc, int(self.lb), self.every, ctypes.byref(h)))
+        self._h = h
+        if not hasattr(batch, "_dependents"):
+            batch._dependents = []
+        batch._dependents.append(self)           # closed before the batch it reads
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._libh.bflbm_batch_sf_destroy(self._h)
+            self._h = None
+            deps = getattr(self.batch, "_dependents", [])
+            if self in deps:
+                deps.remove(self)
+
+    def _owner_closing(self):
+        """BatchLBM.close(): bflbm_batch_destroy detaches the accumulator; its spectra stay readable until close()."""
+        deps = getattr(self.batch, "_dependents", [])
+        if self in deps:
+            deps.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def nsamples(self):
+        """Frames accumulated, read from the library so that attached frames count."""
+        n = self._ct.c_longlong()
+        self._check(self._libh.bflbm_batch_sf_nsamples(self._h, self._ct.byref(n)))
+        return n.value
+
+    @nsamples.setter
+    def nsamples(self, value):                   # StructFact.__init__ assigns 0; the library keeps the count
+        pass
+
+    def reset(self):
+        if getattr(self, "_h", None):
+            self._check(self._libh.bflbm_batch_sf_reset(self._h))
+
+    def fort_structure(self, fields=None, reset=0):
+        """FortStructure on the resident state of every replica (`fields` is ignored: nothing is downloaded)."""
+        self._check(self._libh.bflbm_batch_sf_accumulate(self._h, int(bool(reset))))
+
+    def _get(self, what, zero_avg, replica=None):
+        nx, ny, nz = self.n
+        out = np.empty((len(self.pairs), nz, ny, nx))
+        r = -1 if replica is None else int(replica)
+        if r < 0 and replica is not None:
+            raise ValueError("replica: None (the ensemble mean) or an index >= 0")
+        self._check(self._libh.bflbm_batch_sf_get(self._h, r, what, int(bool(zero_avg)), out.ctypes.data_as(self._ct.c_void_p)))
+        return out
+
+    def mean(self, zero_avg=1, replica=None):
+        """Mean spectrum over the frames: of the ensemble (replica=None) or of one replica."""
+        return self._get(1, zero_avg, replica) + 1j * self._get(2, zero_avg, replica)
+
+    def means(self, zero_avg=1):
+        """Every replica's mean spectrum, stacked [B, npairs, nz, ny, nx]."""
+        return np.stack([self.mean(zero_avg, r) for r in range(self.nreplicas)])
+
+    def magnitude(self, zero_avg=1, replica=None):
+        return self._get(0, zero_avg, replica)
+
+    def _parts(self, zero_avg):                  # write_plotfile: the ensemble mean
+        return self._get(0, zero_avg), self._get(1, zero_avg), self._get(2, zero_avg)

@@ -310,6 +310,52 @@ int bflbm_trace_read(bflbm_trace* t, long long first, long long count,
                      double* rec   /* [count][nreplicas][12] */,
                      long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
 
+/* ---- Ensemble structure factors: S(k) of every replica of a batch in one batched pass (the reference's live job
+ * accumulates structure factors every out_SF_step steps, main_run_job.cpp:299-310, :342-349; Mixture.ipynb reads them).
+ * One accumulator serves the whole batch.  A frame enqueues, on the batch's stream and without a host synchronisation,
+ * one observation launch over all replicas (only the variables that occur in a pair, densely), one batched hipFFT D2Z
+ * (hipfftPlanMany, batch = B x distinct variables) and one accumulation launch; with one bflbm_sf per replica view the
+ * same frame is B observation launches, B x distinct variables transforms and B accumulation launches.
+ *  - pairs, scale, what, zero_avg, normalisation and output layout (dst[npairs][nz][ny][nx], k = 0 at cell n/2) are
+ *    those of bflbm_sf_*.  lb_hydrovars (0: var_a / var_b index hydrovs, != 0: hydrovsbar) is fixed at creation.
+ *  - spectra: the accumulator keeps one running sum per replica.  bflbm_batch_sf_get with replica r in 0..B-1 returns
+ *    that replica's mean over the frames; replica -1 returns the ensemble mean: per (pair, k) the B per-replica sums
+ *    are added in the replica order 0 ... B-1 and multiplied by 1 / (B nsamples), so the result does not depend on launch
+ *    geometry.  what = 0 of the ensemble is the magnitude of that complex mean, not a mean of magnitudes.
+ *  - sampling rule: every = 0: frames are taken only by bflbm_batch_sf_accumulate.  every >= 1: the accumulator is
+ *    attached; it counts the steps taken through bflbm_batch_step since its creation or reset and bflbm_batch_step enqueues
+ *    a frame after each step at which that count is a multiple of `every` (the trace's rule; after the trace's sample).
+ *    bflbm_batch_sf_accumulate is allowed on an attached accumulator and does not move the count, with reset != 0 too
+ *    (FortStructure's reset: the running sums and nsamples start again with this frame).  bflbm_batch_sf_reset zeroes the
+ *    sums, sets nsamples = 0 and restarts the count.  nsamples counts the frames whose launches were all accepted.
+ *  - what is touched on the replicas: the dense fields, the spectra, the running sums and the download buffer belong to
+ *    the accumulator; no replica's state or scratch buffer is written.  Only when hydrovs is observed and some replica's
+ *    rho / phi arrays are not the densities of its resident state, one density launch over the batch rewrites them for
+ *    every replica (a valid replica gets the same doubles again) and marks them valid, as the per-context observables
+ *    do.  hydrovsbar needs no densities.  A frame changes nothing the batch computes.
+ *  - a batch may hold several accumulators (e.g. one on hydrovs, one on hydrovsbar).
+ *  - lifetime: destroying the batch first detaches its accumulators (what is enqueued completes); after that
+ *    bflbm_batch_sf_get, _nsamples, _reset and _destroy still work and bflbm_batch_sf_accumulate fails.
+ *  - refused (non-zero return, a message naming the call, before any device is touched, nothing allocated): null
+ *    arguments, npairs outside 1..32, a variable index outside hydrovs (with lb_hydrovars: outside hydrovsbar),
+ *    every < 0; in bflbm_batch_sf_get a replica outside -1..B-1 or what outside 0..2.  A failed allocation or plan
+ *    frees what was allocated and reports the sizes; a failed launch reports the HIP error.
+ *  - bflbm_batch_sf_get, the two getters below and bflbm_batch_sf_destroy synchronise the batch's stream; no other call
+ *    of this group does.
+ * bflbm_batch_get_hydrovs / _hydrovsbar: the first ncomp components (1..22, 1..9) of every replica, dst[B][ncomp][nz][ny][nx],
+ * with one observation launch, one copy and one synchronisation; the doubles of bflbm_get_hydrovs / _hydrovsbar on the
+ * views.  They use a dense buffer owned by the batch, allocated at first use. */
+typedef struct bflbm_batch_sf bflbm_batch_sf;
+int bflbm_batch_sf_create(bflbm_batch* b, int npairs, const int* var_a, const int* var_b, const double* scale,
+                          int lb_hydrovars, int every, bflbm_batch_sf** out);
+int bflbm_batch_sf_destroy(bflbm_batch_sf* s);
+int bflbm_batch_sf_reset(bflbm_batch_sf* s);                 /* zero the accumulators, nsamples = 0, restart the every-count */
+int bflbm_batch_sf_accumulate(bflbm_batch_sf* s, int reset); /* FortStructure(fields, reset) on the resident state of every replica, now */
+int bflbm_batch_sf_nsamples(const bflbm_batch_sf* s, long long* n);
+int bflbm_batch_sf_get(bflbm_batch_sf* s, int replica, int what, int zero_avg, double* dst);  /* replica -1: ensemble mean */
+int bflbm_batch_get_hydrovs(bflbm_batch* b, double* dst, int ncomp);     /* dst[B][ncomp][nz][ny][nx] */
+int bflbm_batch_get_hydrovsbar(bflbm_batch* b, double* dst, int ncomp);
+
 /* Materialise the per-step fields the reference keeps in MultiFabs, for the state
  * after the last completed step:
  *   hydrovsbar comps 0..8  (LBM_hydrovars_density, LBM_binary.H:315-354)
