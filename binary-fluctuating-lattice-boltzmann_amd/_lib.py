@@ -119,6 +119,14 @@ SIGNATURES = {
     "bflbm_trace_reset": (ctypes.c_int, [_vp]),
     "bflbm_trace_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
     "bflbm_trace_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp]),
+    "bflbm_iface_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_batch_iface_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_iface_destroy": (ctypes.c_int, [_vp]),
+    "bflbm_iface_sample": (ctypes.c_int, [_vp]),
+    "bflbm_iface_reset": (ctypes.c_int, [_vp]),
+    "bflbm_iface_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
+    "bflbm_iface_geometry": (ctypes.c_int, [_vp, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int)]),
+    "bflbm_iface_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp]),
     "bflbm_batch_sf_create": (ctypes.c_int, [_vp, ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), _dp, ctypes.c_int, ctypes.c_int, _P(_vp)]),
     "bflbm_batch_sf_destroy": (ctypes.c_int, [_vp]),
     "bflbm_batch_sf_reset": (ctypes.c_int, [_vp]),

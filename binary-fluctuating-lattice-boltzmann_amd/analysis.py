@@ -88,6 +88,43 @@ def msd(r, max_lag):
     return out
 
 
+def interface_heights(field_zyx, level, window=None):
+    """The numpy restatement of the interface trace (include/bflbm.h, "Interface traces", is the definition): for every
+    column of field_zyx[nz, ny, nx] the height of the first rising (d(z-1) < level <= d(z)) and of the first falling
+    (d(z-1) >= level > d(z)) pair of the window [z_lo, z_hi) (default: all planes), scanned upward without a wrap,
+    h = (z-1) + (level - d(z-1)) / (d(z) - d(z-1)).  Returns [2, ny, nx] (0 rising, 1 falling), NaN without a crossing."""
+    d = np.asarray(field_zyx, dtype=np.float64)
+    if d.ndim != 3:
+        raise ValueError(f"interface_heights: a field [nz, ny, nx], got shape {d.shape}")
+    z_lo, z_hi = (0, d.shape[0]) if window is None else (int(window[0]), int(window[1]))
+    if not (0 <= z_lo and z_hi <= d.shape[0] and z_hi - z_lo >= 2):
+        raise ValueError(f"interface_heights: window [{z_lo}, {z_hi}) of {d.shape[0]} planes")
+    level = np.float64(level)
+    a, b = d[z_lo:z_hi - 1], d[z_lo + 1:z_hi]                # d(z-1), d(z) of the pairs z = z_lo+1 ... z_hi-1
+    out = np.full((2,) + d.shape[1:], np.nan)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for k, hit in enumerate(((a < level) & (level <= b), (a >= level) & (level > b))):   # a NaN compares false
+            first = np.argmax(hit, axis=0)[None]             # the first pair that crosses (0 where none does)
+            lo, hi = np.take_along_axis(a, first, axis=0)[0], np.take_along_axis(b, first, axis=0)[0]
+            h = (z_lo + first[0]).astype(np.float64) + (level - lo) / (hi - lo)
+            out[k] = np.where(hit.any(axis=0), h, np.nan)
+    return out
+
+
+def capillary_spectrum(h, axes=(-1,)):
+    """<|h_q|^2> of a height series h[T, ...] (Flat_Interface.ipynb cell 9, for one or both in-plane axes): the time mean
+    of every column is removed, numpy's unnormalised DFT is taken over `axes`, and |h_q|^2 is averaged over T.
+    Returns (spectrum of shape h.shape[1:], tuple of the wave numbers q = 2 pi fftfreq(n) of every axis in `axes`)."""
+    h = np.asarray(h, dtype=np.float64)
+    if h.ndim < 2:
+        raise ValueError("capillary_spectrum: h[T, ...] with at least one in-plane axis")
+    axes = tuple(a if a >= 0 else h.ndim + a for a in axes)
+    if any(not 1 <= a < h.ndim for a in axes) or len(set(axes)) != len(axes):
+        raise ValueError(f"capillary_spectrum: axes {axes} of an array with {h.ndim} dimensions (axis 0 is time)")
+    hq = np.fft.fftn(h - h.mean(axis=0), axes=axes)
+    return (np.abs(hq) ** 2).mean(axis=0), tuple(2 * np.pi * np.fft.fftfreq(h.shape[a]) for a in axes)
+
+
 # ---- the same observables from the device-reduced raw moments (BinaryLBM.droplet_moments) ----------------
 # m[0:10] = sum rho {1, x, y, z, xx, xy, xz, yy, yz, zz} in cell indices, m[10:20] trapezoid-weighted.
 

@@ -126,6 +126,7 @@ struct bflbm_ctx {
   bool com_valid = false;
   bflbm_batch* batch = nullptr; // non-null: a replica view owned by this batch (bflbm_batch_replica)
   bflbm_trace* trace = nullptr; // the trace attached to this lone context (bflbm_trace.h); it outlives the context detached
+  std::vector<bflbm_iface*> ifaces;   // the interface traces attached to this lone context (bflbm_iface.h), in creation order
   bool record_stale = true;     // a view: its batch record (parameters, buffers, step counter) must be written again
   // what describes the resident state, and what was derived from it, is reset by the transitions below (state_replaced ...)
 };
@@ -137,7 +138,12 @@ namespace {
 bool trace_overflows(const bflbm_trace* t, long long nsteps);
 int trace_after_step(bflbm_trace* t);
 void trace_detach(bflbm_trace* t);
+// the same three for the interface traces (bflbm_iface.h); an owner may carry several, served in creation order
+bool iface_overflows(const bflbm_iface* t, long long nsteps);
+int iface_after_step(bflbm_iface* t);
+void iface_detach(bflbm_iface* t);
 #define BFLBM_REFUSE_TRACE_FULL(t, call, nsteps) do { if ((t) && trace_overflows(t, nsteps)) return fail("%s: trace full: the samples of %lld more step(s) do not fit (read it and bflbm_trace_reset, or create a larger one)", call, (long long)(nsteps)); } while (0)
+#define BFLBM_REFUSE_IFACE_FULL(list, call, nsteps) do { for (const bflbm_iface* t_ : (list)) if (iface_overflows(t_, nsteps)) return fail("%s: interface trace full: the samples of %lld more step(s) do not fit (read it and bflbm_iface_reset, or create a larger one)", call, (long long)(nsteps)); } while (0)
 
 dim3 plane_grid(const bflbm_ctx* c, int nplanes) {
   return dim3((unsigned)((c->G.plane + 255) / 256), (unsigned)nplanes, 1);
@@ -668,6 +674,7 @@ int bflbm_destroy(bflbm_ctx* c) {
   BFLBM_REFUSE_VIEW(c, "bflbm_destroy", "the batch owns it: use bflbm_batch_destroy");
   hipSetDevice(c->dom.device);
   if (c->trace) trace_detach(c->trace);
+  while (!c->ifaces.empty()) iface_detach(c->ifaces.back());
   if (c->stream && c->own_stream) hipStreamSynchronize(c->stream);
   if (c->S[0]) hipFree(c->S[0]);                 // S[1] lives in the same allocation
   if (c->frames[0]) hipFree(c->frames[0]);
@@ -879,6 +886,7 @@ int bflbm_step_boundary(bflbm_ctx* c) {
   BFLBM_REFUSE_VIEW(c, "bflbm_step_boundary", "use bflbm_batch_step");
   if (c->step_open()) return fail("step already open");
   BFLBM_REFUSE_TRACE_FULL(c->trace, "bflbm_step_boundary", 1);
+  BFLBM_REFUSE_IFACE_FULL(c->ifaces, "bflbm_step_boundary", 1);
   HIP_TRY(hipSetDevice(c->dom.device));
   if (prepare_ref(c)) return 1;
   const int sch = frames_for_next_step(c, true);
@@ -903,7 +911,9 @@ int bflbm_step_finish(bflbm_ctx* c) {
   BFLBM_REFUSE_VIEW(c, "bflbm_step_finish", "use bflbm_batch_step");
   if (!c->step_open()) return fail("no open step");
   state_advanced(c);
-  return c->trace ? trace_after_step(c->trace) : 0;
+  if (c->trace && trace_after_step(c->trace)) return 1;
+  for (bflbm_iface* t : c->ifaces) if (iface_after_step(t)) return 1;
+  return 0;
 }
 
 int bflbm_step(bflbm_ctx* c, int nsteps) {
@@ -912,6 +922,7 @@ int bflbm_step(bflbm_ctx* c, int nsteps) {
   if (nsteps < 0) return fail("nsteps < 0");
   if (!c->G.zwrap && nsteps > 1) return fail("bflbm_step: nranks > 1 needs a halo exchange between steps; use nsteps == 1");
   BFLBM_REFUSE_TRACE_FULL(c->trace, "bflbm_step", nsteps);
+  BFLBM_REFUSE_IFACE_FULL(c->ifaces, "bflbm_step", nsteps);
   for (int s = 0; s < nsteps; ++s) if (bflbm_step_boundary(c) || bflbm_step_interior(c) || bflbm_step_finish(c)) return 1;
   return 0;
 }
@@ -1508,6 +1519,7 @@ struct bflbm_batch {
   BatchRec* h_rec = nullptr;            // pinned host copy of what was uploaded
   long long k = 0;                      // batch steps since the records were written
   bflbm_trace* trace = nullptr;         // the trace attached to this batch (bflbm_trace.h)
+  std::vector<bflbm_iface*> ifaces;     // the interface traces attached to this batch (bflbm_iface.h), in creation order
   std::vector<bflbm_batch_sf*> sfs;     // the structure-factor accumulators living on this batch (bflbm_batch_sf.h)
   double* d_obs = nullptr;              // dense [B][ncomp][nz][ny][nx] of bflbm_batch_get_hydrovs / _hydrovsbar, allocated at first use
   size_t obs_doubles = 0;
@@ -1611,6 +1623,7 @@ int bflbm_batch_destroy(bflbm_batch* b) {
   hipSetDevice(b->device);
   if (b->stream) hipStreamSynchronize(b->stream);
   if (b->trace) trace_detach(b->trace);
+  while (!b->ifaces.empty()) iface_detach(b->ifaces.back());
   while (!b->sfs.empty()) batch_sf_detach(b->sfs.back());
   batch_obs_free(b);
   for (bflbm_ctx* c : b->ctx) { c->batch = nullptr; bflbm_destroy(c); }
@@ -1658,6 +1671,7 @@ int bflbm_batch_step(bflbm_batch* b, int nsteps) {
                 replica_list(quiet).c_str(), replica_list(noisy).c_str());
   for (const bflbm_ctx* c : b->ctx) if (c->step_open()) return fail("bflbm_batch_step: a replica has an open step");
   BFLBM_REFUSE_TRACE_FULL(b->trace, "bflbm_batch_step", nsteps);
+  BFLBM_REFUSE_IFACE_FULL(b->ifaces, "bflbm_batch_step", nsteps);
   if (nsteps == 0) return 0;
   HIP_TRY(hipSetDevice(b->device));
   const int sch = batch_resolved(b);
@@ -1673,6 +1687,7 @@ int bflbm_batch_step(bflbm_batch* b, int nsteps) {
     b->k += 1;
     for (bflbm_ctx* c : b->ctx) state_advanced(c);
     if (b->trace && trace_after_step(b->trace)) return 1;
+    for (bflbm_iface* t : b->ifaces) if (iface_after_step(t)) return 1;
     for (bflbm_batch_sf* s : b->sfs) if (batch_sf_after_step(s)) return 1;
   }
   return 0;
@@ -1691,4 +1706,5 @@ int bflbm_batch_sync(bflbm_batch* b) {
 #include "bflbm_sf_ring.h"
 #include "bflbm_droplet.h"
 #include "bflbm_trace.h"
+#include "bflbm_iface.h"
 #include "bflbm_batch_sf.h"

@@ -163,6 +163,84 @@ class Trace:
         return rec[..., 1:4] / rec[..., 0:1]
 
 
+IFACE_FIELDS = {"rho": 0, "phi": 1}
+
+
+class InterfaceTrace:
+    """Contour heights of every column of every replica recorded on the device every `every` steps through the owner (a
+    lone single-slab BinaryLBM or a BatchLBM) and read once: include/bflbm.h, "Interface traces".  Made by
+    owner.interface_trace(); an owner may carry several."""
+
+    def __init__(self, owner, create, level, field, window, every, capacity):
+        self.lib, self.owner = owner.lib, owner
+        if field not in IFACE_FIELDS and field not in IFACE_FIELDS.values():
+            raise ValueError(f"interface_trace: field {field!r}, expected 'rho' (0) or 'phi' (1)")
+        z_lo, z_hi = (0, owner.n[2]) if window is None else (int(window[0]), int(window[1]))
+        h = ctypes.c_void_p()
+        check(getattr(self.lib, create)(owner._h, int(IFACE_FIELDS.get(field, field)), float(level), z_lo, z_hi, int(every),
+                                        int(capacity), ctypes.byref(h)))
+        self._h = h
+        self.level, self.field, self.window = float(level), field, (z_lo, z_hi)
+        if not hasattr(owner, "_dependents"):
+            owner._dependents = []
+        owner._dependents.append(self)               # closed before the owner it reads
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.bflbm_iface_destroy(self._h)
+            self._h = None
+            deps = getattr(self.owner, "_dependents", [])
+            if self in deps:
+                deps.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sample(self):
+        """Record the resident state now (e.g. frame 0); the every-counter does not move."""
+        check(self.lib.bflbm_iface_sample(self._h))
+
+    def reset(self):
+        """Forget the samples and restart the every-counter."""
+        check(self.lib.bflbm_iface_reset(self._h))
+
+    def _count(self):
+        n, b = ctypes.c_longlong(), ctypes.c_int()
+        check(self.lib.bflbm_iface_count(self._h, ctypes.byref(n), ctypes.byref(b)))
+        return n.value, b.value
+
+    @property
+    def count(self):
+        return self._count()[0]
+
+    def geometry(self):
+        """(nx, ny, segments of the scan, pairs (z-1, z) per segment): which launch shape the library chose."""
+        v = [ctypes.c_int() for _ in range(4)]
+        check(self.lib.bflbm_iface_geometry(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def read(self):
+        """(steps[count, B] int64, h[count, B, 2, ny, nx]), direction 0 rising, 1 falling, NaN where a column has no
+        crossing; synchronises the owner's stream."""
+        n, b = self._count()
+        nx, ny = self.geometry()[:2]
+        steps = np.empty((n, b), dtype=np.int64)
+        h = np.empty((n, b, 2, ny, nx))
+        check(self.lib.bflbm_iface_read(self._h, 0, n, _ptr(h), _ptr(steps)))
+        return steps, h
+
+    def rising(self):
+        """h[count, B, ny, nx] of the first pair with d(z-1) < level <= d(z)."""
+        return self.read()[1][:, :, 0]
+
+    def falling(self):
+        """h[count, B, ny, nx] of the first pair with d(z-1) >= level > d(z)."""
+        return self.read()[1][:, :, 1]
+
+
 # kernel schedules of include/bflbm.h (bflbm_set_schedule): "fused" = plane march with the ring densities pulled
 # (bit-exact), "handover" = plane march with the ring densities handed over from the previous step (tolerance)
 SCHEDULES = {"two_pass": 0, "fused": 1, "fused_exact": 1, "auto": 2, "handover": 3}
@@ -381,6 +459,13 @@ class BinaryLBM(_DropletMixin):
     def trace(self, every, capacity, threshold=None):
         """Record the droplet moments of the cells with rho > threshold (None: every cell) after every `every`-th step."""
         return Trace(self, "bflbm_trace_create", every, capacity, threshold)
+
+    def interface_trace(self, level, field="rho", window=None, every=1, capacity=64):
+        """Record, after every `every`-th step, the rising and falling height of the `field` = level contour ("rho" or
+        "phi") above every column, scanned over the planes window = (z_lo, z_hi) (None: all): InterfaceTrace.
+        The device buffer of `capacity` samples is allocated at once: capacity x 2 ny nx doubles (the default 64 takes
+        256 MiB on a 512 x 512 column lattice); a step whose sample would not fit is refused, so size it for the run."""
+        return InterfaceTrace(self, "bflbm_iface_create", level, field, window, every, capacity)
 
     def com_sums(self):
         s = (ctypes.c_double * 4)()
@@ -720,6 +805,12 @@ class BatchLBM:
         """Record every replica's droplet moments (cells with rho > threshold; None: every cell) after every `every`-th
         batch step."""
         return Trace(self, "bflbm_batch_trace_create", every, capacity, threshold)
+
+    def interface_trace(self, level, field="rho", window=None, every=1, capacity=64):
+        """Record every replica's contour heights (BinaryLBM.interface_trace) after every `every`-th batch step.  The
+        device buffer is allocated at once: capacity x B x 2 ny nx doubles (the default 64 takes 32 MiB for 16 replicas
+        of 8 x 256 columns)."""
+        return InterfaceTrace(self, "bflbm_batch_iface_create", level, field, window, every, capacity)
 
     def structfact(self, var_names, **kw):
         """One structure-factor accumulator for the whole batch (structfact.BatchStructFact; every=k attaches it)."""

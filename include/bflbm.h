@@ -310,6 +310,56 @@ int bflbm_trace_read(bflbm_trace* t, long long first, long long count,
                      double* rec   /* [count][nreplicas][12] */,
                      long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
 
+/* ---- Interface traces: the height of a density contour above every column of every replica, recorded on the device
+ * and read once at the end (the flat-interface height field of Flat_Interface.ipynb, cells 4 and 7-9, whose spectrum
+ * <|h_q|^2> is compared with kBT / (gamma q^2); the reference's flat-interface box is 8 x 256 x 64).
+ * An interface trace is attached to one lone single-slab context or one replica batch, like an ensemble trace.
+ *  - definition (stated here and nowhere else).  Three settings: a field (0 = rho, the density of fluid f; 1 = phi, the
+ *    density of fluid g), a `level`, and a z-window [z_lo, z_hi) with 0 <= z_lo, z_hi <= nz and z_hi - z_lo >= 2.
+ *    d(z) is the field's density of the resident state at (x, y, z), the sum of the 19 pulled populations in index order:
+ *    the double bflbm_get_hydrovsbar component 0 (rho) or 1 (phi) holds.  For every column (x, y) two heights are
+ *    recorded, both from scanning z = z_lo+1 ... z_hi-1 upward without a periodic wrap:
+ *      rising:   the first z with d(z-1) <  level <= d(z)
+ *      falling:  the first z with d(z-1) >= level >  d(z)
+ *    and in both cases h = (double)(z-1) + (level - d(z-1)) / (d(z) - d(z-1)): two IEEE subtractions, one division, one
+ *    addition, no contraction (linear interpolation, as skimage.find_contours does).  A column without such a pair
+ *    records a quiet NaN; a NaN density satisfies neither condition.
+ *  - sample: [replica][2][ny][nx] doubles, dense, direction 0 rising, direction 1 falling.
+ *  - kernels: stage 1 gives every column a thread, splits the pairs (z-1, z) of the window into contiguous segments and
+ *    writes per segment the first rising and first falling candidate (152 B read per site of the window, nothing
+ *    written per site); stage 2 takes, per column and direction, the first non-NaN candidate in segment order.  The
+ *    number of segments is the library's choice (enough workgroups to fill the device, each segment at least 4 pairs,
+ *    an unmeasured heuristic) and changes no bit of a sample; bflbm_iface_geometry reports it.  Both launches go to the
+ *    owner's stream; only rho / phi populations are read, nothing of the owner is written.
+ *  - sampling rule, capacity, step labels: those of the ensemble traces above.  The trace counts the steps taken through
+ *    its owner since its creation or reset and samples after a step when that count is a multiple of `every`;
+ *    bflbm_iface_sample records the resident state now without moving the count; bflbm_iface_reset forgets the samples
+ *    and restarts the count; every sample is labelled on the host with each replica's step counter.  bflbm_step,
+ *    bflbm_batch_step and bflbm_step_boundary refuse, before any launch and with state and counters untouched, a call
+ *    whose samples would not fit ("interface trace full"); bflbm_iface_sample on a full trace is refused the same way.
+ *  - an owner may carry several interface traces (rho and phi, two levels ...).  After a step they are served in the order
+ *    of their creation, after the owner's ensemble trace and before a batch's structure-factor accumulators; the
+ *    capacity check covers all of them before the first launch.
+ *  - refused at creation (non-zero return, a message naming the call, nothing allocated): null arguments, a field other
+ *    than 0 or 1, a NaN level, a window outside the lattice or shorter than two planes, every < 1, capacity < 1, a
+ *    capacity beyond 1 TB of heights, a replica view (use bflbm_batch_iface_create), a context with nranks > 1, an open
+ *    step.  An open step also refuses bflbm_iface_sample, _reset and _read.
+ *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_iface_read, _count,
+ *    _geometry and _destroy still work, bflbm_iface_sample fails.
+ *  - bflbm_iface_read synchronises the owner's stream; no other call of this group does. */
+typedef struct bflbm_iface bflbm_iface;
+int bflbm_iface_create(bflbm_ctx* c, int field, double level, int z_lo, int z_hi, int every, long long capacity, bflbm_iface** out);
+int bflbm_batch_iface_create(bflbm_batch* b, int field, double level, int z_lo, int z_hi, int every, long long capacity, bflbm_iface** out);
+int bflbm_iface_destroy(bflbm_iface* t);
+int bflbm_iface_sample(bflbm_iface* t);                 /* record the resident state now (e.g. frame 0) */
+int bflbm_iface_reset(bflbm_iface* t);                  /* forget the samples, restart the every-counter */
+int bflbm_iface_count(const bflbm_iface* t, long long* nsamples, int* nreplicas);
+int bflbm_iface_geometry(const bflbm_iface* t, int* nx, int* ny, int* nsegments /* of stage 1 */,
+                         int* segment_pairs /* pairs (z-1, z) per segment; the last segment may hold fewer */);
+int bflbm_iface_read(bflbm_iface* t, long long first, long long count,
+                     double* h     /* [count][nreplicas][2][ny][nx] */,
+                     long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
+
 /* ---- Ensemble structure factors: S(k) of every replica of a batch in one batched pass (the reference's live job
  * accumulates structure factors every out_SF_step steps, main_run_job.cpp:299-310, :342-349; Mixture.ipynb reads them).
  * One accumulator serves the whole batch.  A frame enqueues, on the batch's stream and without a host synchronisation,

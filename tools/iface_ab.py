@@ -1,0 +1,135 @@
+"""What recording the flat-interface height field of an ensemble costs (profiles/iface_throughput.txt).
+
+Workload: a batch of 16 x (8 x 256 x 64) stripes with the parameters of Flat_Interface.ipynb (alpha0 = 1.5, rho_lo = 0.1,
+rho_hi = 3, kappa = 0.1, kBT = 1e-5), `--steps` steps, the rho = 1.55 contour heights of every column of every replica
+wanted every `--every`-th step.  Three variants, one fresh process each, interleaved a / b / c `--rounds` times:
+
+    a  no observable: batch.LBM_timestep(steps)
+    b  the interface trace: batch.interface_trace(every=10), batch.LBM_timestep(steps), one read() at the end
+    c  through the host: LBM_hydrovars_density(ncomp=1) on every view plus analysis.interface_heights, every 10 steps
+
+The time is the host clock around the whole block, ended by a device synchronisation (variant c is made of host round
+trips, so a device-side timer would miss what it costs); a warm-up block of the same variant runs first.  Every worker
+process runs under its own time limit and the driver stops at the first one that fails.
+
+    python tools/iface_ab.py [--steps 2000] [--every 10] [--rounds 3] [--out profiles/iface_throughput.txt]
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPE, REPLICAS = (8, 256, 64), 16
+PARAMS = dict(alpha0=1.5, rho_lo=0.1, rho_hi=3.0, kappa=0.1, kBT=1e-5)
+LEVEL = 1.55
+VARIANTS = {"a": "no observable", "b": "interface trace", "c": "density per view + numpy contour"}
+
+
+def worker(variant, steps, every):
+    import numpy as np
+    import __graft_entry__ as ge
+    pkg = ge.load_package()
+    warm = max(2 * every, steps // 20 // every * every)
+    with pkg.BatchLBM(SHAPE, params=PARAMS, replicas=REPLICAS) as batch:
+        for rep in batch.replicas:
+            rep.LBM_init_stripe(0.5)
+        tr = batch.interface_trace(LEVEL, every=every, capacity=max(steps, warm) // every) if variant == "b" else None
+        geometry = None if tr is None else list(tr.geometry())            # the launch shape the library chose, as observed
+
+        def block(k):
+            if variant == "c":
+                out = []
+                for _ in range(k // every):
+                    batch.LBM_timestep(every)
+                    out.append([pkg.analysis.interface_heights(rep.LBM_hydrovars_density(ncomp=1)[0], LEVEL) for rep in batch.replicas])
+                return np.array(out)
+            batch.LBM_timestep(k)
+            if tr is None:
+                batch.sync()
+                return None
+            h = tr.read()[1]
+            tr.reset()
+            return h
+
+        block(warm)
+        batch.sync()
+        t0 = time.perf_counter()
+        h = block(steps)
+        batch.sync()
+        dt = time.perf_counter() - t0
+        schedule = batch.resolved_schedule()
+    sites = SHAPE[0] * SHAPE[1] * SHAPE[2]
+    nan = None if h is None else int(np.isnan(h[:, :, 1]).sum())          # falling heights: the stripe fills every column
+    print(json.dumps(dict(variant=variant, n=list(SHAPE), replicas=REPLICAS, steps=steps, every=every, seconds=dt, schedule=schedule,
+                          samples=None if h is None else int(h.shape[0]), falling_nan=nan, geometry=geometry,
+                          us_per_step=dt / steps * 1e6, mlups=REPLICAS * sites * steps / dt / 1e6)), flush=True)
+
+
+def drive(steps, every, rounds, limit):
+    results = {}
+    for rnd in range(rounds):
+        for variant in "abc":
+            cmd = [sys.executable, os.path.abspath(__file__), "--worker", variant, "--steps", str(steps), "--every", str(every)]
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)     # a failure or a time limit ends the run
+            if r.returncode != 0:
+                sys.stderr.write(r.stdout + r.stderr)
+                raise SystemExit(f"worker {variant} failed with status {r.returncode}; nothing more is started")
+            rec = json.loads(r.stdout.strip().splitlines()[-1])
+            results.setdefault(variant, []).append(rec)
+            print(f"round {rnd} {variant}: {rec['us_per_step']:9.1f} us/step ({rec['schedule']}, {rec['samples']} samples)", flush=True)
+    return results
+
+
+def report(by, steps, every, rounds):
+    n = SHAPE
+    lines = [f"# tools/iface_ab.py --steps {steps} --every {every} --rounds {rounds}: one fresh process per variant, interleaved a b c; host",
+             "# clock around the block, ended by a device synchronisation; stripes with the Flat_Interface.ipynb parameters, kBT = 1e-5,",
+             f"# rho = {LEVEL} contour heights of every column wanted every {every}-th step",
+             f"# (b)/(a) by the traffic model: 1 + 152 / (608 x {every}) = {1 + 152 / (608 * every):.3f} plus two small launches per sample",
+             f"{n[0]}x{n[1]}x{n[2]} x {REPLICAS} replicas, schedule {by['a'][0]['schedule']}"]
+    med = {}
+    for v in "abc":
+        us = [r["us_per_step"] for r in by[v]]
+        med[v] = statistics.median(us)
+        lines.append(f"  {v}  {VARIANTS[v]:<34s} median {med[v]:9.1f} us/step   min {min(us):9.1f}  max {max(us):9.1f}   rounds: "
+                     + "  ".join(f"{u:.1f}" for u in us))
+    nx, ny, nseg, seg_pairs = by["b"][0]["geometry"]
+    npairs = n[2] - 1
+    lines.append(f"  b  bflbm_iface_geometry: {nx} x {ny} columns, {nseg} segments of {seg_pairs} pairs (the last {npairs - (nseg - 1) * seg_pairs}) over"
+                 f" the {npairs} pairs of the full window")
+    wins = [b["us_per_step"] < c["us_per_step"] for b, c in zip(by["b"], by["c"])]
+    lines.append(f"  b/a = {med['b'] / med['a']:.3f}   c/b = {med['c'] / med['b']:.2f}   b faster than c in {sum(wins)} of {len(wins)} rounds")
+    return lines
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--every", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--limit", type=float, default=120.0, help="time limit of one worker process in seconds")
+    ap.add_argument("--out", default=None, help="also write the table to this file")
+    ap.add_argument("--worker", choices=sorted(VARIANTS), default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.steps % a.every:
+        raise SystemExit("--steps must be a multiple of --every")
+    if a.worker:
+        return worker(a.worker, a.steps, a.every)
+    results = drive(a.steps, a.every, a.rounds, a.limit)
+    lines = report(results, a.steps, a.every, a.rounds)
+    print("\n".join(lines))
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+    if not all(b["us_per_step"] < c["us_per_step"] for b, c in zip(results["b"], results["c"])):
+        raise SystemExit("the interface trace was not faster than the host path in every round")
+
+
+if __name__ == "__main__":
+    main()
