@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -86,6 +87,7 @@ void derive(const bflbm_params& p, DevParams& d) {
 
 }  // namespace
 
+struct bflbm_recorder;
 struct bflbm_ctx {
   bflbm_params prm;
   DevParams dp;
@@ -125,25 +127,29 @@ struct bflbm_ctx {
   double com[3] = {0., 0., 0.}; // global centre of mass (update_com) of the resident state
   bool com_valid = false;
   bflbm_batch* batch = nullptr; // non-null: a replica view owned by this batch (bflbm_batch_replica)
-  bflbm_trace* trace = nullptr; // the trace attached to this lone context (bflbm_trace.h); it outlives the context detached
-  std::vector<bflbm_iface*> ifaces;   // the interface traces attached to this lone context (bflbm_iface.h), in creation order
+  std::vector<bflbm_recorder*> recorders;   // what records from this lone context (bflbm_recorder.h), in creation order
   bool record_stale = true;     // a view: its batch record (parameters, buffers, step counter) must be written again
   // what describes the resident state, and what was derived from it, is reset by the transitions below (state_replaced ...)
 };
 
-namespace {
+// include/bflbm.h, "Replica batch"
+struct bflbm_batch {
+  std::vector<bflbm_ctx*> ctx;          // the replica views
+  hipStream_t stream = nullptr;         // every replica's stream
+  int device = 0;
+  Geo G;                                // the replicas' common geometry
+  int schedule = 2;                     // 0 two-pass, 1 fused, 2 auto
+  BatchRec* d_rec = nullptr;            // per-replica records read by the kernels
+  BatchRec* h_rec = nullptr;            // pinned host copy of what was uploaded
+  long long k = 0;                      // batch steps since the records were written
+  std::vector<bflbm_recorder*> recorders;     // what records from this batch (bflbm_recorder.h), in creation order
+  double* d_obs = nullptr;              // dense [B][ncomp][nz][ny][nx] of bflbm_batch_get_hydrovs / _hydrovsbar, allocated at first use
+  size_t obs_doubles = 0;
+};
 
-// the owner's side of an ensemble trace (bflbm_trace.h): would the samples of `nsteps` more steps overflow it; one step
-// was taken through the owner (samples when due); the owner goes away
-bool trace_overflows(const bflbm_trace* t, long long nsteps);
-int trace_after_step(bflbm_trace* t);
-void trace_detach(bflbm_trace* t);
-// the same three for the interface traces (bflbm_iface.h); an owner may carry several, served in creation order
-bool iface_overflows(const bflbm_iface* t, long long nsteps);
-int iface_after_step(bflbm_iface* t);
-void iface_detach(bflbm_iface* t);
-#define BFLBM_REFUSE_TRACE_FULL(t, call, nsteps) do { if ((t) && trace_overflows(t, nsteps)) return fail("%s: trace full: the samples of %lld more step(s) do not fit (read it and bflbm_trace_reset, or create a larger one)", call, (long long)(nsteps)); } while (0)
-#define BFLBM_REFUSE_IFACE_FULL(list, call, nsteps) do { for (const bflbm_iface* t_ : (list)) if (iface_overflows(t_, nsteps)) return fail("%s: interface trace full: the samples of %lld more step(s) do not fit (read it and bflbm_iface_reset, or create a larger one)", call, (long long)(nsteps)); } while (0)
+#include "bflbm_recorder.h"
+
+namespace {
 
 dim3 plane_grid(const bflbm_ctx* c, int nplanes) {
   return dim3((unsigned)((c->G.plane + 255) / 256), (unsigned)nplanes, 1);
@@ -673,8 +679,7 @@ int bflbm_destroy(bflbm_ctx* c) {
   if (!c) return 0;
   BFLBM_REFUSE_VIEW(c, "bflbm_destroy", "the batch owns it: use bflbm_batch_destroy");
   hipSetDevice(c->dom.device);
-  if (c->trace) trace_detach(c->trace);
-  while (!c->ifaces.empty()) iface_detach(c->ifaces.back());
+  recorders_detach_all(c);
   if (c->stream && c->own_stream) hipStreamSynchronize(c->stream);
   if (c->S[0]) hipFree(c->S[0]);                 // S[1] lives in the same allocation
   if (c->frames[0]) hipFree(c->frames[0]);
@@ -885,8 +890,7 @@ int bflbm_step_boundary(bflbm_ctx* c) {
   if (!c) return fail("null context");
   BFLBM_REFUSE_VIEW(c, "bflbm_step_boundary", "use bflbm_batch_step");
   if (c->step_open()) return fail("step already open");
-  BFLBM_REFUSE_TRACE_FULL(c->trace, "bflbm_step_boundary", 1);
-  BFLBM_REFUSE_IFACE_FULL(c->ifaces, "bflbm_step_boundary", 1);
+  if (recorders_refuse_full(c, "bflbm_step_boundary", 1)) return 1;
   HIP_TRY(hipSetDevice(c->dom.device));
   if (prepare_ref(c)) return 1;
   const int sch = frames_for_next_step(c, true);
@@ -911,9 +915,7 @@ int bflbm_step_finish(bflbm_ctx* c) {
   BFLBM_REFUSE_VIEW(c, "bflbm_step_finish", "use bflbm_batch_step");
   if (!c->step_open()) return fail("no open step");
   state_advanced(c);
-  if (c->trace && trace_after_step(c->trace)) return 1;
-  for (bflbm_iface* t : c->ifaces) if (iface_after_step(t)) return 1;
-  return 0;
+  return recorders_after_step(c);
 }
 
 int bflbm_step(bflbm_ctx* c, int nsteps) {
@@ -921,8 +923,7 @@ int bflbm_step(bflbm_ctx* c, int nsteps) {
   BFLBM_REFUSE_VIEW(c, "bflbm_step", "use bflbm_batch_step");
   if (nsteps < 0) return fail("nsteps < 0");
   if (!c->G.zwrap && nsteps > 1) return fail("bflbm_step: nranks > 1 needs a halo exchange between steps; use nsteps == 1");
-  BFLBM_REFUSE_TRACE_FULL(c->trace, "bflbm_step", nsteps);
-  BFLBM_REFUSE_IFACE_FULL(c->ifaces, "bflbm_step", nsteps);
+  if (recorders_refuse_full(c, "bflbm_step", nsteps)) return 1;
   for (int s = 0; s < nsteps; ++s) if (bflbm_step_boundary(c) || bflbm_step_interior(c) || bflbm_step_finish(c)) return 1;
   return 0;
 }
@@ -1509,29 +1510,9 @@ int bflbm_ring_sync(bflbm_ring* r) {
 }  // extern "C"
 
 // ---- replica batch (include/bflbm.h, "Replica batch"; kernels in bflbm_batch.h) -----------------------------------------
-struct bflbm_batch {
-  std::vector<bflbm_ctx*> ctx;          // the replica views
-  hipStream_t stream = nullptr;         // every replica's stream
-  int device = 0;
-  Geo G;                                // the replicas' common geometry
-  int schedule = 2;                     // 0 two-pass, 1 fused, 2 auto
-  BatchRec* d_rec = nullptr;            // per-replica records read by the kernels
-  BatchRec* h_rec = nullptr;            // pinned host copy of what was uploaded
-  long long k = 0;                      // batch steps since the records were written
-  bflbm_trace* trace = nullptr;         // the trace attached to this batch (bflbm_trace.h)
-  std::vector<bflbm_iface*> ifaces;     // the interface traces attached to this batch (bflbm_iface.h), in creation order
-  std::vector<bflbm_batch_sf*> sfs;     // the structure-factor accumulators living on this batch (bflbm_batch_sf.h)
-  double* d_obs = nullptr;              // dense [B][ncomp][nz][ny][nx] of bflbm_batch_get_hydrovs / _hydrovsbar, allocated at first use
-  size_t obs_doubles = 0;
-};
-
 namespace {
 
-// the batch's side of its structure-factor accumulators (bflbm_batch_sf.h): one step was taken through the batch (a frame
-// when due); the batch goes away; the getters' dense buffer
-int batch_sf_after_step(bflbm_batch_sf* s);
-void batch_sf_detach(bflbm_batch_sf* s);
-void batch_obs_free(bflbm_batch* b);
+void batch_obs_free(bflbm_batch* b);                 // the getters' dense buffer (bflbm_batch_sf.h)
 
 // `auto` of a batch: the rule of exact_quiet_schedule over the whole batch -- the one-pass kernel once the fused
 // workgroups of all replicas fill the compute units, the two-pass schedule otherwise.  Unlike a lone lattice, a batch
@@ -1622,9 +1603,7 @@ int bflbm_batch_destroy(bflbm_batch* b) {
   if (!b) return 0;
   hipSetDevice(b->device);
   if (b->stream) hipStreamSynchronize(b->stream);
-  if (b->trace) trace_detach(b->trace);
-  while (!b->ifaces.empty()) iface_detach(b->ifaces.back());
-  while (!b->sfs.empty()) batch_sf_detach(b->sfs.back());
+  recorders_detach_all(b);
   batch_obs_free(b);
   for (bflbm_ctx* c : b->ctx) { c->batch = nullptr; bflbm_destroy(c); }
   if (b->d_rec) hipFree(b->d_rec);
@@ -1670,8 +1649,7 @@ int bflbm_batch_step(bflbm_batch* b, int nsteps) {
     return fail("bflbm_batch_step: replicas %s have kBT == 0 and replicas %s kBT != 0; a batch steps all replicas with noise or none",
                 replica_list(quiet).c_str(), replica_list(noisy).c_str());
   for (const bflbm_ctx* c : b->ctx) if (c->step_open()) return fail("bflbm_batch_step: a replica has an open step");
-  BFLBM_REFUSE_TRACE_FULL(b->trace, "bflbm_batch_step", nsteps);
-  BFLBM_REFUSE_IFACE_FULL(b->ifaces, "bflbm_batch_step", nsteps);
+  if (recorders_refuse_full(b, "bflbm_batch_step", nsteps)) return 1;
   if (nsteps == 0) return 0;
   HIP_TRY(hipSetDevice(b->device));
   const int sch = batch_resolved(b);
@@ -1686,9 +1664,7 @@ int bflbm_batch_step(bflbm_batch* b, int nsteps) {
     if (e != hipSuccess) return fail("bflbm_batch_step: launch failed: %s", hipGetErrorString(e));
     b->k += 1;
     for (bflbm_ctx* c : b->ctx) state_advanced(c);
-    if (b->trace && trace_after_step(b->trace)) return 1;
-    for (bflbm_iface* t : b->ifaces) if (iface_after_step(t)) return 1;
-    for (bflbm_batch_sf* s : b->sfs) if (batch_sf_after_step(s)) return 1;
+    if (recorders_after_step(b)) return 1;
   }
   return 0;
 }

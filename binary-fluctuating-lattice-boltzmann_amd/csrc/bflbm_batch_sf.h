@@ -9,6 +9,7 @@
 // hydrovs is observed and some replica's densities are not those of its resident state.
 // k_observe_batch computes, per site, what k_observe computes (the same device functions in the same order, no injected
 // noise, no reference state), so the stacked getters bflbm_batch_get_hydrovs / _hydrovsbar return the doubles of the views'.
+// The link to the batch, the every-count and the detaching are those of bflbm_recorder.h.
 // Included by bflbm.hip after bflbm_batch.h, bflbm_sf.h and bflbm_trace.h (needs bflbm_batch, FftApi, SfPairs).
 #ifndef BFLBM_BATCH_SF_H_
 #define BFLBM_BATCH_SF_H_
@@ -168,24 +169,20 @@ int batch_observe_launch(bflbm_batch* b, int what, const ObsSel& sel, double* ou
 
 }  // namespace
 
-struct bflbm_batch_sf {
-  bflbm_batch* batch = nullptr;     // null once the batch is gone (detached)
-  int device = 0;
-  int nrep = 1;
+struct bflbm_batch_sf : bflbm_recorder {  // n: frames accumulated; every == 0: fed by bflbm_batch_sf_accumulate only
   int nx = 0, ny = 0, nz = 0;
-  long long n = 0, nk = 0;          // sites, half-spectrum size
+  long long nsites = 0, nk = 0;     // sites, half-spectrum size
   SfPairs pairs;                    // a, b: slots of the pair's variables
   ObsSel sel;
   int lb = 0;                       // 0 hydrovs, 1 hydrovsbar
-  int every = 0;
-  long long since = 0;              // steps taken through the batch since creation or reset
-  long long nsamples = 0;
-  double* fields = nullptr;         // [nrep][nsel][n]
+  double* fields = nullptr;         // [nrep][nsel][nsites]
   double2* hat = nullptr;           // [nrep][nsel][nk]
   double2* acc = nullptr;           // [nrep][npairs][nk]
-  double* expand = nullptr;         // [npairs][n]
+  double* expand = nullptr;         // [npairs][nsites]
   hipfftHandle plan = nullptr;
   size_t acc_bytes() const { return (size_t)nrep * pairs.n * nk * sizeof(double2); }
+  bflbm_batch_sf() : bflbm_recorder("structure-factor accumulator", "bflbm_batch_sf") {}
+  int record() override;
 };
 
 namespace {
@@ -203,27 +200,11 @@ int batch_sf_frame(bflbm_batch_sf* s, const char* call) {
   g_fft.set_stream(s->plan, b->stream);
   if (g_fft.exec_d2z(s->plan, s->fields, (hipfftDoubleComplex*)s->hat) != HIPFFT_SUCCESS) return fail("%s: hipfftExecD2Z failed", call);
   const dim3 grid((unsigned)((s->nk + 255) / 256), (unsigned)s->pairs.n, (unsigned)s->nrep);
-  hipLaunchKernelGGL(k_sf_accumulate_batch, grid, dim3(256), 0, b->stream, s->hat, s->acc, s->nk, s->sel.nsel, s->pairs, 1.0 / (double)s->n);
+  hipLaunchKernelGGL(k_sf_accumulate_batch, grid, dim3(256), 0, b->stream, s->hat, s->acc, s->nk, s->sel.nsel, s->pairs, 1.0 / (double)s->nsites);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail("%s: accumulation launch failed: %s", call, hipGetErrorString(e));
-  s->nsamples += 1;
+  s->n += 1;
   return 0;
-}
-
-int batch_sf_after_step(bflbm_batch_sf* s) {
-  if (s->every < 1) return 0;
-  s->since += 1;
-  return (s->since % s->every == 0) ? batch_sf_frame(s, "bflbm_batch_step (structure-factor frame)") : 0;
-}
-
-// the batch goes away: what was enqueued completes, the spectra stay readable
-void batch_sf_detach(bflbm_batch_sf* s) {
-  bflbm_batch* b = s->batch;
-  if (!b) return;
-  hipSetDevice(s->device);
-  (void)hipStreamSynchronize(b->stream);
-  b->sfs.erase(std::remove(b->sfs.begin(), b->sfs.end(), s), b->sfs.end());
-  s->batch = nullptr;
 }
 
 void batch_obs_free(bflbm_batch* b) {
@@ -253,6 +234,8 @@ int batch_get(bflbm_batch* b, int what, int ncomp, double* dst, const char* call
 
 }  // namespace
 
+int bflbm_batch_sf::record() { return batch_sf_frame(this, "bflbm_batch_step (structure-factor frame)"); }
+
 extern "C" {
 
 int bflbm_batch_sf_create(bflbm_batch* b, int npairs, const int* var_a, const int* var_b, const double* scale,
@@ -268,11 +251,11 @@ int bflbm_batch_sf_create(bflbm_batch* b, int npairs, const int* var_a, const in
   if (load_fft()) return 1;
   HIP_TRY(hipSetDevice(b->device));
   bflbm_batch_sf* s = new bflbm_batch_sf();
-  s->batch = b; s->device = b->device; s->nrep = (int)b->ctx.size();
+  recorder_bind(s, nullptr, b, every);
   s->nx = b->G.nx; s->ny = b->G.ny; s->nz = b->G.nzs;
-  s->n = (long long)s->nx * s->ny * s->nz;
+  s->nsites = (long long)s->nx * s->ny * s->nz;
   s->nk = (long long)(s->nx / 2 + 1) * s->ny * s->nz;
-  s->lb = lb_hydrovars ? 1 : 0; s->every = every;
+  s->lb = lb_hydrovars ? 1 : 0;
   s->sel.mask = 0; s->sel.nsel = 0;
   for (int p = 0; p < npairs; ++p) { s->sel.mask |= 1u << var_a[p]; s->sel.mask |= 1u << var_b[p]; }
   for (int c = 0; c < BFLBM_NHYDRO_; ++c) s->sel.slot[c] = (s->sel.mask & (1u << c)) ? s->sel.nsel++ : 0;
@@ -282,8 +265,8 @@ int bflbm_batch_sf_create(bflbm_batch* b, int npairs, const int* var_a, const in
     s->pairs.b[p] = p < npairs ? s->sel.slot[var_b[p]] : 0;
     s->pairs.scale[p] = (p < npairs && scale) ? scale[p] : 1.0;
   }
-  const size_t fb = (size_t)s->nrep * s->sel.nsel * s->n * sizeof(double), hb = (size_t)s->nrep * s->sel.nsel * s->nk * sizeof(double2);
-  const size_t ab = s->acc_bytes(), eb = (size_t)npairs * s->n * sizeof(double);
+  const size_t fb = (size_t)s->nrep * s->sel.nsel * s->nsites * sizeof(double), hb = (size_t)s->nrep * s->sel.nsel * s->nk * sizeof(double2);
+  const size_t ab = s->acc_bytes(), eb = (size_t)npairs * s->nsites * sizeof(double);
   hipError_t e = hipMalloc((void**)&s->fields, fb);
   if (e == hipSuccess) e = hipMalloc((void**)&s->hat, hb);
   if (e == hipSuccess) e = hipMalloc((void**)&s->acc, ab);
@@ -294,7 +277,7 @@ int bflbm_batch_sf_create(bflbm_batch* b, int npairs, const int* var_a, const in
     return fail("bflbm_batch_sf_create: out of device memory (fields %zu + spectra %zu + accumulators %zu + download %zu bytes): %s", fb, hb, ab, eb, hipGetErrorString(e));
   }
   int dims[3] = {s->nz, s->ny, s->nx};
-  if (g_fft.plan_many(&s->plan, 3, dims, nullptr, 1, (int)s->n, nullptr, 1, (int)s->nk, HIPFFT_D2Z, s->nrep * s->sel.nsel) != HIPFFT_SUCCESS) {
+  if (g_fft.plan_many(&s->plan, 3, dims, nullptr, 1, (int)s->nsites, nullptr, 1, (int)s->nk, HIPFFT_D2Z, s->nrep * s->sel.nsel) != HIPFFT_SUCCESS) {
     s->plan = nullptr;
     batch_sf_free(s);
     return fail("bflbm_batch_sf_create: hipfftPlanMany failed for %d transforms of %d x %d x %d", (int)b->ctx.size() * s->sel.nsel, b->G.nx, b->G.ny, b->G.nzs);
@@ -302,14 +285,14 @@ int bflbm_batch_sf_create(bflbm_batch* b, int npairs, const int* var_a, const in
   g_fft.set_stream(s->plan, b->stream);
   e = hipMemsetAsync(s->acc, 0, ab, b->stream);
   if (e != hipSuccess) { batch_sf_free(s); return fail("bflbm_batch_sf_create: %s", hipGetErrorString(e)); }
-  b->sfs.push_back(s);
+  b->recorders.push_back(s);
   *out = s;
   return 0;
 }
 
 int bflbm_batch_sf_destroy(bflbm_batch_sf* s) {
   if (!s) return 0;
-  batch_sf_detach(s);                                  // waits for the frames in flight: they write the buffers freed below
+  recorder_detach(s);                                  // waits for the frames in flight: they write the buffers freed below
   hipSetDevice(s->device);
   batch_sf_free(s);
   return 0;
@@ -319,7 +302,7 @@ int bflbm_batch_sf_reset(bflbm_batch_sf* s) {
   if (!s) return fail("bflbm_batch_sf_reset: null argument");
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipMemsetAsync(s->acc, 0, s->acc_bytes(), s->batch ? s->batch->stream : nullptr));
-  s->nsamples = 0; s->since = 0;
+  s->n = 0; s->since = 0;
   return 0;
 }
 
@@ -329,14 +312,14 @@ int bflbm_batch_sf_accumulate(bflbm_batch_sf* s, int reset) {
   if (reset) {                                         // FortStructure's reset: a new average; the every-count does not move
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipMemsetAsync(s->acc, 0, s->acc_bytes(), s->batch->stream));
-    s->nsamples = 0;
+    s->n = 0;
   }
   return batch_sf_frame(s, "bflbm_batch_sf_accumulate");
 }
 
 int bflbm_batch_sf_nsamples(const bflbm_batch_sf* s, long long* n) {
   if (!s || !n) return fail("bflbm_batch_sf_nsamples: null argument");
-  *n = s->nsamples;
+  *n = s->n;
   return 0;
 }
 
@@ -346,13 +329,13 @@ int bflbm_batch_sf_get(bflbm_batch_sf* s, int replica, int what, int zero_avg, d
   if (what < 0 || what > 2) return fail("bflbm_batch_sf_get: what must be 0, 1 or 2");
   HIP_TRY(hipSetDevice(s->device));
   const hipStream_t stream = s->batch ? s->batch->stream : nullptr;   // detaching waited for everything enqueued
-  const long long frames = std::max(s->nsamples, 1LL);
+  const long long frames = std::max(s->n, 1LL);
   const double inv = 1.0 / (replica < 0 ? (double)s->nrep * (double)frames : (double)frames);
-  const dim3 grid((unsigned)((s->n + 255) / 256), (unsigned)s->pairs.n);
+  const dim3 grid((unsigned)((s->nsites + 255) / 256), (unsigned)s->pairs.n);
   hipLaunchKernelGGL(k_sf_expand_batch, grid, dim3(256), 0, stream, s->acc, s->expand, s->nx, s->ny, s->nz, s->pairs.n, s->nrep,
                      replica, inv, what, zero_avg);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(dst, s->expand, (size_t)s->pairs.n * s->n * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(dst, s->expand, (size_t)s->pairs.n * s->nsites * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   return 0;
 }

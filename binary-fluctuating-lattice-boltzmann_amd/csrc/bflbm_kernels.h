@@ -149,6 +149,13 @@ __device__ __forceinline__ void pull_site(const double* __restrict__ S, const Ge
     gs[i] = ld_sb(b + (long long)Q*G.vol, o);
   }
 }
+// the 19 pulled populations of the one fluid whose first population is F, added in index order: the double k_density stores
+__device__ __forceinline__ double pull_density(const double* __restrict__ F, const Geo& G, const SiteOff& I) {
+  double fs[Q];
+#pragma unroll
+  for (int i = 0; i < Q; ++i) fs[i] = ld_sb(F + (long long)i * G.vol + I.pl[1 - Vel::cz[i]], I.o[1 - Vel::cy[i]][1 - Vel::cx[i]]);
+  return d_density(fs);
+}
 // nb[i] = field(x + c_i)
 __device__ __forceinline__ void gather_field(const double* __restrict__ fld, const SiteOff& I, double (&nb)[Q]) {
 #pragma unroll

@@ -1,0 +1,189 @@
+// bflbm_recorder.h -- the one lifecycle of everything that records from an owner's resident state: ensemble traces
+// (bflbm_trace.h), interface traces (bflbm_iface.h) and ensemble structure factors (bflbm_batch_sf.h).  A recorder is
+// attached to a lone context or a batch, is served after every step on the owner's stream in creation order, survives
+// its owner detached (readable, no longer fed) and is destroyed by its own call ("Recorders").
+// Host code only.  Included by bflbm.hip once bflbm_ctx and bflbm_batch are complete (needs fail, HIP_TRY).
+#ifndef BFLBM_RECORDER_H_
+#define BFLBM_RECORDER_H_
+
+struct bflbm_recorder {
+  bflbm_ctx* ctx = nullptr;        // the owner: a lone context ...
+  bflbm_batch* batch = nullptr;    // ... or a batch; both null once the owner is gone (detached)
+  int device = 0;
+  int nrep = 1;
+  int every = 0;                   // a sample after every `every`-th step through the owner; 0: stepping never serves it
+  long long since = 0;             // steps taken through the owner since creation or reset
+  long long n = 0;                 // samples (frames) recorded
+  long long capacity = std::numeric_limits<long long>::max();   // unbounded: an accumulator
+  std::vector<long long> steps;    // [n][nrep]: every replica's step counter at the sample
+  const char* const noun;          // "trace", "interface trace": the messages
+  const char* const abi;           // "bflbm_trace", "bflbm_iface": the calls the messages name
+  bflbm_recorder(const char* noun_, const char* abi_) : noun(noun_), abi(abi_) {}
+  virtual ~bflbm_recorder() {}
+  virtual int record() = 0;        // enqueue one sample (frame) of the resident state now; no host synchronisation
+};
+
+// what the two trace kinds add: `capacity` samples of `per` doubles on the device, and a stage buffer of the kind's own
+struct bflbm_sample_store : bflbm_recorder {
+  using bflbm_recorder::bflbm_recorder;
+  size_t per = 0;
+  double* d_rec = nullptr;         // [capacity][per]
+  double* d_stage = nullptr;       // stage 1 -> stage 2
+};
+
+namespace {
+
+inline bool recorder_attached(const bflbm_recorder* r) { return r->ctx || r->batch; }
+inline hipStream_t recorder_stream(const bflbm_recorder* r) { return r->ctx ? r->ctx->stream : r->batch->stream; }
+inline bool recorder_owner_open(const bflbm_recorder* r) { return r->ctx && r->ctx->step_open(); }
+inline std::vector<bflbm_recorder*>& recorder_list(bflbm_recorder* r) { return r->ctx ? r->ctx->recorders : r->batch->recorders; }
+
+// samples that `nsteps` more steps through the owner add
+inline long long recorder_due(const bflbm_recorder* r, long long nsteps) { return r->every ? (r->since + nsteps) / r->every - r->since / r->every : 0; }
+inline bool recorder_overflows(const bflbm_recorder* r, long long nsteps) { return recorder_due(r, nsteps) > r->capacity - r->n; }
+
+// the link to the owner; the owner's list takes the recorder once nothing can fail any more
+void recorder_bind(bflbm_recorder* r, bflbm_ctx* c, bflbm_batch* b, int every) {
+  r->ctx = c; r->batch = b; r->every = every;
+  r->device = c ? c->dom.device : b->device;
+  r->nrep = c ? 1 : (int)b->ctx.size();
+}
+
+int recorder_after_step(bflbm_recorder* r) {
+  r->since += 1;
+  return (r->every && r->since % r->every == 0) ? r->record() : 0;
+}
+
+// the owner goes away (or the recorder does): what was enqueued completes, what was recorded stays readable
+void recorder_detach(bflbm_recorder* r) {
+  if (!recorder_attached(r)) return;
+  hipSetDevice(r->device);
+  (void)hipStreamSynchronize(recorder_stream(r));
+  std::vector<bflbm_recorder*>& list = recorder_list(r);
+  list.erase(std::remove(list.begin(), list.end(), r), list.end());
+  r->ctx = nullptr; r->batch = nullptr;
+}
+
+// ---- the owner's side: a bflbm_ctx or a bflbm_batch with its `recorders` in creation order -------------------------------
+template <class Owner> void recorders_detach_all(Owner* o) { while (!o->recorders.empty()) recorder_detach(o->recorders.back()); }
+
+// a call of `nsteps` steps is refused before any launch when some recorder's samples would not fit
+template <class Owner> int recorders_refuse_full(const Owner* o, const char* call, long long nsteps) {
+  for (const bflbm_recorder* r : o->recorders)
+    if (recorder_overflows(r, nsteps))
+      return fail("%s: %s full: the samples of %lld more step(s) do not fit (read it and %s_reset, or create a larger one)", call, r->noun, nsteps, r->abi);
+  return 0;
+}
+
+// one step was taken through the owner
+template <class Owner> int recorders_after_step(Owner* o) {
+  for (bflbm_recorder* r : o->recorders) if (recorder_after_step(r)) return 1;
+  return 0;
+}
+
+// ---- the sample store of the two trace kinds ---------------------------------------------------------------------------
+int store_refuse_cadence(const char* call, int every, long long capacity) {
+  if (every < 1) return fail("%s: every must be >= 1 (got %d)", call, every);
+  if (capacity < 1) return fail("%s: capacity must be >= 1 (got %lld)", call, capacity);
+  return 0;
+}
+// `batch_call`: the creation call of the kind that takes a batch; `noun`: the kind's, as in its messages
+int store_refuse_owner(const bflbm_ctx* c, const char* call, const char* batch_call, const char* noun) {
+  if (c && c->batch) return fail("%s: the context is a replica of a batch; use %s on the batch", call, batch_call);
+  if (c && !c->G.zwrap) return fail("%s: a slab of a decomposed lattice (nranks > 1); %ss take a lone single-slab context or a batch", call, noun);
+  return 0;
+}
+
+// allocate [capacity][per] and the stage buffer and attach the store to its owner; `shape`: what besides the replicas
+// multiplies the capacity, for the message.  On failure the store owns nothing.
+int store_attach(bflbm_sample_store* s, bflbm_ctx* c, bflbm_batch* b, const char* call, int every, long long capacity,
+                 size_t per, size_t stage_doubles, const char* shape) {
+  if (c && c->step_open()) return fail("%s inside an open step", call);
+  recorder_bind(s, c, b, every);
+  if ((unsigned long long)capacity > ((1ULL << 40) / sizeof(double)) / per)
+    return fail("%s: capacity %lld x %d replicas%s exceeds 1 TB of records", call, capacity, s->nrep, shape);
+  HIP_TRY(hipSetDevice(s->device));
+  hipError_t e = hipMalloc((void**)&s->d_rec, (size_t)capacity * per * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&s->d_stage, stage_doubles * sizeof(double));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (s->d_rec) hipFree(s->d_rec);
+    s->d_rec = nullptr;
+    return fail("%s: %s", call, hipGetErrorString(e));
+  }
+  s->capacity = capacity; s->per = per;
+  recorder_list(s).push_back(s);
+  return 0;
+}
+
+// the head and the tail of a kind's record(): refuse a full store and select the device; the slot of sample n; count
+// the sample under every replica's step counter
+int store_begin(const bflbm_sample_store* s) {
+  if (s->n >= s->capacity) return fail("%s full: %lld samples recorded (read it and %s_reset, or create a larger one)", s->noun, s->n, s->abi);
+  HIP_TRY(hipSetDevice(s->device));
+  return 0;
+}
+inline double* store_slot(const bflbm_sample_store* s) { return s->d_rec + (size_t)s->n * s->per; }
+void store_recorded(bflbm_sample_store* s) {
+  if (s->batch) for (const bflbm_ctx* c : s->batch->ctx) s->steps.push_back(c->steps);
+  else s->steps.push_back(s->ctx->steps);
+  s->n += 1;
+}
+
+int store_destroy(bflbm_sample_store* s) {
+  if (!s) return 0;
+  recorder_detach(s);                                  // waits for the work in flight: it writes the buffers freed below
+  hipSetDevice(s->device);
+  if (s->d_rec) hipFree(s->d_rec);
+  if (s->d_stage) hipFree(s->d_stage);
+  delete s;
+  return 0;
+}
+
+// `abi` below: the kind's prefix again, for the refusal of a null store, which has no abi field to read
+int store_sample(bflbm_sample_store* s, const char* abi) {
+  if (!s) return fail("%s_sample: null argument", abi);
+  if (!recorder_attached(s)) return fail("%s_sample: the owner of the %s was destroyed", abi, s->noun);
+  if (recorder_owner_open(s)) return fail("%s_sample inside an open step", abi);
+  return s->record();
+}
+
+int store_reset(bflbm_sample_store* s, const char* abi) {
+  if (!s) return fail("%s_reset: null argument", abi);
+  if (recorder_owner_open(s)) return fail("%s_reset inside an open step", abi);
+  s->n = 0; s->since = 0;
+  s->steps.clear();
+  return 0;
+}
+
+int store_count(const bflbm_sample_store* s, const char* abi, long long* nsamples, int* nreplicas) {
+  if (!s) return fail("%s_count: null argument", abi);
+  if (nsamples) *nsamples = s->n;
+  if (nreplicas) *nreplicas = s->nrep;
+  return 0;
+}
+
+int store_read(bflbm_sample_store* s, const char* abi, long long first, long long count, double* rec, long long* steps) {
+  if (!s) return fail("%s_read: null argument", abi);
+  if (first < 0 || count < 0 || first > s->n || count > s->n - first)
+    return fail("%s_read: samples [%lld, %lld + %lld) of %lld recorded", abi, first, first, count, s->n);
+  if (count == 0) return 0;
+  if (!rec) return fail("%s_read: null argument", abi);
+  if (recorder_owner_open(s)) return fail("%s_read inside an open step", abi);
+  HIP_TRY(hipSetDevice(s->device));
+  const double* src = s->d_rec + (size_t)first * s->per;
+  const size_t nb = (size_t)count * s->per * sizeof(double);
+  if (recorder_attached(s)) {
+    const hipStream_t stream = recorder_stream(s);
+    HIP_TRY(hipMemcpyAsync(rec, src, nb, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+  } else {
+    HIP_TRY(hipMemcpy(rec, src, nb, hipMemcpyDeviceToHost));   // detaching waited for everything enqueued
+  }
+  if (steps) std::copy(s->steps.begin() + (size_t)first * s->nrep, s->steps.begin() + (size_t)(first + count) * s->nrep, steps);
+  return 0;
+}
+
+}  // namespace
+
+#endif  // BFLBM_RECORDER_H_

@@ -5,24 +5,16 @@
 // The sums are added in the order of bflbm_droplet.h (block_sum over 256 consecutive sites of the padded plane, the
 // strided sum and tree of k_sum_partials per plane, the planes in sequence), so a record equals bflbm_droplet_moments
 // of the same state bit for bit and does not depend on how the lattice is run.
-// Included by bflbm.hip after bflbm_droplet.h (needs bflbm_ctx, bflbm_batch, block_sum).
+// The lifecycle and the sample store are those of bflbm_recorder.h; here are the kernels, their launch and the checks of
+// the kind's own arguments.  Included by bflbm.hip after bflbm_droplet.h (needs bflbm_ctx, bflbm_batch, block_sum).
 #ifndef BFLBM_TRACE_H_
 #define BFLBM_TRACE_H_
 
-struct bflbm_trace {
-  bflbm_ctx* ctx = nullptr;        // the owner: a lone context ...
-  bflbm_batch* batch = nullptr;    // ... or a batch; both null once the owner is gone (detached)
-  int device = 0;
-  int nrep = 1;
+struct bflbm_trace : bflbm_sample_store {  // d_rec [capacity][nrep][kNTrace], d_stage [nrep][nz][plane blocks][kNTrace]
   Geo G;
-  int every = 1;
-  long long capacity = 0;
   double threshold = 0.;
-  long long since = 0;             // steps taken through the owner since creation or reset
-  long long n = 0;                 // samples recorded
-  double* d_rec = nullptr;         // [capacity][nrep][kNTrace]
-  double* d_partial = nullptr;     // [nrep][nz][plane blocks][kNTrace]: stage 1 -> stage 2
-  std::vector<long long> steps;    // [n][nrep]: every replica's step counter at the sample
+  bflbm_trace() : bflbm_sample_store("trace", "bflbm_trace") {}
+  int record() override;
 };
 
 namespace {
@@ -41,10 +33,7 @@ __device__ __forceinline__ void trace_moments_body(const double* __restrict__ S,
   const int x = (int)(s_ - (long long)y * G.pitch);
   if (s_ < G.plane && x < G.nx) {
     SiteOff I; site_offsets(G, x, y, p, I);
-    double fs[Q];
-#pragma unroll
-    for (int i = 0; i < Q; ++i) fs[i] = ld_sb(S + (long long)i * G.vol + I.pl[1 - Vel::cz[i]], I.o[1 - Vel::cy[i]][1 - Vel::cx[i]]);
-    const double r = d_density(fs);
+    const double r = pull_density(S, G, I);
     v[10] = r;
     if (threshold == -INFINITY || r > threshold) {     // -inf: every cell, whatever its density is
       const int z = p;
@@ -94,86 +83,41 @@ __global__ void __launch_bounds__(256) k_trace_finish(const double* __restrict__
   if (threadIdx.x == 0) for (int k = 0; k < kNTrace; ++k) out[(long long)blockIdx.x * kNTrace + k] = acc[k];
 }
 
-inline bool trace_attached(const bflbm_trace* t) { return t->ctx || t->batch; }
-inline hipStream_t trace_stream(const bflbm_trace* t) { return t->ctx ? t->ctx->stream : t->batch->stream; }
-inline bool trace_owner_open(const bflbm_trace* t) { return t->ctx && t->ctx->step_open(); }
-
-// samples that `nsteps` more steps through the owner add
-inline long long trace_due(const bflbm_trace* t, long long nsteps) { return (t->since + nsteps) / t->every - t->since / t->every; }
-bool trace_overflows(const bflbm_trace* t, long long nsteps) { return t->n + trace_due(t, nsteps) > t->capacity; }
-
-// enqueue the reduction of the resident state into slot n; no host synchronisation
-int trace_record(bflbm_trace* t) {
-  if (t->n >= t->capacity) return fail("trace full: %lld samples recorded (read it and bflbm_trace_reset, or create a larger one)", t->n);
-  HIP_TRY(hipSetDevice(t->device));
-  const Geo& G = t->G;
-  const dim3 grid((unsigned)((G.plane + 255) / 256), (unsigned)G.nz, (unsigned)t->nrep);
-  const hipStream_t stream = trace_stream(t);
-  if (t->batch) {
-    bflbm_batch* b = t->batch;
-    if (batch_sync_table(b)) return 1;                 // a sample between steps (frame 0): the records may be stale
-    hipLaunchKernelGGL(k_trace_moments_batch, grid, dim3(256), 0, stream, b->d_rec, t->d_partial, G, (int)b->k, t->threshold);
-  } else {
-    hipLaunchKernelGGL(k_trace_moments, grid, dim3(256), 0, stream, t->ctx->S[t->ctx->cur], t->d_partial, G, t->threshold);
-  }
-  HIP_TRY(hipGetLastError());
-  double* slot = t->d_rec + (size_t)t->n * t->nrep * kNTrace;
-  hipLaunchKernelGGL(k_trace_finish, dim3((unsigned)t->nrep), dim3(256), 0, stream, t->d_partial, slot, (int)grid.x, (int)grid.y);
-  HIP_TRY(hipGetLastError());
-  if (t->batch) for (const bflbm_ctx* c : t->batch->ctx) t->steps.push_back(c->steps);
-  else t->steps.push_back(t->ctx->steps);
-  t->n += 1;
-  return 0;
-}
-
-int trace_after_step(bflbm_trace* t) {
-  t->since += 1;
-  return (t->since % t->every == 0) ? trace_record(t) : 0;
-}
-
-// the owner goes away: what was enqueued completes, the samples stay readable
-void trace_detach(bflbm_trace* t) {
-  hipSetDevice(t->device);
-  (void)hipStreamSynchronize(trace_stream(t));
-  if (t->ctx) t->ctx->trace = nullptr;
-  if (t->batch) t->batch->trace = nullptr;
-  t->ctx = nullptr; t->batch = nullptr;
-}
-
 int trace_create(bflbm_ctx* c, bflbm_batch* b, int every, long long capacity, double threshold, bflbm_trace** out) {
   const char* call = b ? "bflbm_batch_trace_create" : "bflbm_trace_create";
-  if (every < 1) return fail("%s: every must be >= 1 (got %d)", call, every);
-  if (capacity < 1) return fail("%s: capacity must be >= 1 (got %lld)", call, capacity);
+  if (store_refuse_cadence(call, every, capacity)) return 1;
   if (threshold != threshold) return fail("%s: the threshold is NaN (-INFINITY takes every cell)", call);
-  if (c && c->batch) return fail("%s: the context is a replica of a batch; use bflbm_batch_trace_create on the batch", call);
-  if (c && !c->G.zwrap) return fail("%s: a slab of a decomposed lattice (nranks > 1); traces take a lone single-slab context or a batch", call);
-  if (c ? c->trace != nullptr : b->trace != nullptr) return fail("%s: the owner already has a trace", call);
-  if (c && c->step_open()) return fail("%s inside an open step", call);
-  const Geo& G = c ? c->G : b->G;
-  const int nrep = c ? 1 : (int)b->ctx.size();
-  const size_t rec_doubles_per_sample = (size_t)nrep * kNTrace;
-  if ((unsigned long long)capacity > ((1ULL << 40) / sizeof(double)) / rec_doubles_per_sample)
-    return fail("%s: capacity %lld x %d replicas exceeds 1 TB of records", call, capacity, nrep);
-  const int device = c ? c->dom.device : b->device;
-  HIP_TRY(hipSetDevice(device));
-  const size_t nblocks = (size_t)((G.plane + 255) / 256) * (size_t)G.nz;
-  bflbm_trace* t = new bflbm_trace();
-  hipError_t e = hipMalloc((void**)&t->d_rec, (size_t)capacity * rec_doubles_per_sample * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void**)&t->d_partial, nblocks * rec_doubles_per_sample * sizeof(double));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (t->d_rec) hipFree(t->d_rec);
-    delete t;
-    return fail("%s: %s", call, hipGetErrorString(e));
-  }
-  t->ctx = c; t->batch = b; t->device = device; t->nrep = nrep; t->G = G;
-  t->every = every; t->capacity = capacity; t->threshold = threshold;
-  if (c) c->trace = t; else b->trace = t;
-  *out = t;
+  if (store_refuse_owner(c, call, "bflbm_batch_trace_create", "trace")) return 1;
+  for (const bflbm_recorder* r : c ? c->recorders : b->recorders)
+    if (dynamic_cast<const bflbm_trace*>(r)) return fail("%s: the owner already has a trace", call);
+  std::unique_ptr<bflbm_trace> t(new bflbm_trace());
+  t->G = c ? c->G : b->G; t->threshold = threshold;
+  const size_t per = (size_t)(c ? 1 : b->ctx.size()) * kNTrace;
+  const size_t nblocks = (size_t)((t->G.plane + 255) / 256) * (size_t)t->G.nz;
+  if (store_attach(t.get(), c, b, call, every, capacity, per, nblocks * per, "")) return 1;
+  *out = t.release();
   return 0;
 }
 
 }  // namespace
+
+// enqueue the reduction of the resident state into slot n; no host synchronisation
+int bflbm_trace::record() {
+  if (store_begin(this)) return 1;
+  const dim3 grid((unsigned)((G.plane + 255) / 256), (unsigned)G.nz, (unsigned)nrep);
+  const hipStream_t stream = recorder_stream(this);
+  if (batch) {
+    if (batch_sync_table(batch)) return 1;             // a sample between steps (frame 0): the records may be stale
+    hipLaunchKernelGGL(k_trace_moments_batch, grid, dim3(256), 0, stream, batch->d_rec, d_stage, G, (int)batch->k, threshold);
+  } else {
+    hipLaunchKernelGGL(k_trace_moments, grid, dim3(256), 0, stream, ctx->S[ctx->cur], d_stage, G, threshold);
+  }
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_trace_finish, dim3((unsigned)nrep), dim3(256), 0, stream, d_stage, store_slot(this), (int)grid.x, (int)grid.y);
+  HIP_TRY(hipGetLastError());
+  store_recorded(this);
+  return 0;
+}
 
 extern "C" {
 
@@ -186,58 +130,12 @@ int bflbm_batch_trace_create(bflbm_batch* b, int every, long long capacity, doub
   return trace_create(nullptr, b, every, capacity, threshold, out);
 }
 
-int bflbm_trace_destroy(bflbm_trace* t) {
-  if (!t) return 0;
-  if (trace_attached(t)) trace_detach(t);              // waits for the reductions in flight: they write the buffers freed below
-  hipSetDevice(t->device);
-  if (t->d_rec) hipFree(t->d_rec);
-  if (t->d_partial) hipFree(t->d_partial);
-  delete t;
-  return 0;
-}
-
-int bflbm_trace_sample(bflbm_trace* t) {
-  if (!t) return fail("bflbm_trace_sample: null argument");
-  if (!trace_attached(t)) return fail("bflbm_trace_sample: the owner of the trace was destroyed");
-  if (trace_owner_open(t)) return fail("bflbm_trace_sample inside an open step");
-  return trace_record(t);
-}
-
-int bflbm_trace_reset(bflbm_trace* t) {
-  if (!t) return fail("bflbm_trace_reset: null argument");
-  if (trace_attached(t) && trace_owner_open(t)) return fail("bflbm_trace_reset inside an open step");
-  t->n = 0; t->since = 0;
-  t->steps.clear();
-  return 0;
-}
-
-int bflbm_trace_count(const bflbm_trace* t, long long* nsamples, int* nreplicas) {
-  if (!t) return fail("bflbm_trace_count: null argument");
-  if (nsamples) *nsamples = t->n;
-  if (nreplicas) *nreplicas = t->nrep;
-  return 0;
-}
-
+int bflbm_trace_destroy(bflbm_trace* t) { return store_destroy(t); }
+int bflbm_trace_sample(bflbm_trace* t) { return store_sample(t, "bflbm_trace"); }
+int bflbm_trace_reset(bflbm_trace* t) { return store_reset(t, "bflbm_trace"); }
+int bflbm_trace_count(const bflbm_trace* t, long long* nsamples, int* nreplicas) { return store_count(t, "bflbm_trace", nsamples, nreplicas); }
 int bflbm_trace_read(bflbm_trace* t, long long first, long long count, double* rec, long long* steps) {
-  if (!t) return fail("bflbm_trace_read: null argument");
-  if (first < 0 || count < 0 || first > t->n || count > t->n - first)
-    return fail("bflbm_trace_read: samples [%lld, %lld + %lld) of %lld recorded", first, first, count, t->n);
-  if (count == 0) return 0;
-  if (!rec) return fail("bflbm_trace_read: null argument");
-  if (trace_attached(t) && trace_owner_open(t)) return fail("bflbm_trace_read inside an open step");
-  HIP_TRY(hipSetDevice(t->device));
-  const size_t per = (size_t)t->nrep * kNTrace;
-  const double* src = t->d_rec + (size_t)first * per;
-  const size_t nb = (size_t)count * per * sizeof(double);
-  if (trace_attached(t)) {
-    const hipStream_t stream = trace_stream(t);
-    HIP_TRY(hipMemcpyAsync(rec, src, nb, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-  } else {
-    HIP_TRY(hipMemcpy(rec, src, nb, hipMemcpyDeviceToHost));   // detaching waited for everything enqueued
-  }
-  if (steps) std::copy(t->steps.begin() + (size_t)first * t->nrep, t->steps.begin() + (size_t)(first + count) * t->nrep, steps);
-  return 0;
+  return store_read(t, "bflbm_trace", first, count, rec, steps);
 }
 
 }  // extern "C"

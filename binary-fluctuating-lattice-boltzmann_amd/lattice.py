@@ -104,27 +104,38 @@ class _DropletMixin:
         return tuple(res)
 
 
-class Trace:
-    """Droplet moments of every replica recorded on the device every `every` steps through the owner (a lone
-    single-slab BinaryLBM or a BatchLBM) and read once: include/bflbm.h, "Ensemble traces".  Made by owner.trace()."""
+def _register(owner, dep):
+    """`dep` lives on `owner`: owner.close() meets it first (closes it, or calls its _owner_closing where it has one)."""
+    if not hasattr(owner, "_dependents"):
+        owner._dependents = []
+    owner._dependents.append(dep)
 
-    def __init__(self, owner, create, every, capacity, threshold):
+
+def _unregister(owner, dep):
+    deps = getattr(owner, "_dependents", [])
+    if dep in deps:
+        deps.remove(dep)
+
+
+class _Recorder:
+    """What Trace and InterfaceTrace share: the handle made by `create` on the owner, closed before the owner it reads,
+    and the calls <_abi>_destroy / _sample / _reset / _count."""
+
+    def __init__(self, owner, create, *args):
         self.lib, self.owner = owner.lib, owner
         h = ctypes.c_void_p()
-        thr = -np.inf if threshold is None else float(threshold)
-        check(getattr(self.lib, create)(owner._h, int(every), int(capacity), thr, ctypes.byref(h)))
+        check(getattr(self.lib, create)(owner._h, *args, ctypes.byref(h)))
         self._h = h
-        if not hasattr(owner, "_dependents"):
-            owner._dependents = []
-        owner._dependents.append(self)               # closed before the owner it reads
+        _register(owner, self)
+
+    def _call(self, name, *args):
+        return getattr(self.lib, self._abi + "_" + name)(self._h, *args)
 
     def close(self):
         if getattr(self, "_h", None):
-            self.lib.bflbm_trace_destroy(self._h)
+            self._call("destroy")
             self._h = None
-            deps = getattr(self.owner, "_dependents", [])
-            if self in deps:
-                deps.remove(self)
+            _unregister(self.owner, self)
 
     def __del__(self):
         try:
@@ -134,20 +145,29 @@ class Trace:
 
     def sample(self):
         """Record the resident state now (e.g. frame 0); the every-counter does not move."""
-        check(self.lib.bflbm_trace_sample(self._h))
+        check(self._call("sample"))
 
     def reset(self):
         """Forget the samples and restart the every-counter."""
-        check(self.lib.bflbm_trace_reset(self._h))
+        check(self._call("reset"))
 
     def _count(self):
         n, b = ctypes.c_longlong(), ctypes.c_int()
-        check(self.lib.bflbm_trace_count(self._h, ctypes.byref(n), ctypes.byref(b)))
+        check(self._call("count", ctypes.byref(n), ctypes.byref(b)))
         return n.value, b.value
 
     @property
     def count(self):
         return self._count()[0]
+
+
+class Trace(_Recorder):
+    """Droplet moments of every replica recorded on the device every `every` steps through the owner (a lone
+    single-slab BinaryLBM or a BatchLBM) and read once: include/bflbm.h, "Ensemble traces".  Made by owner.trace()."""
+    _abi = "bflbm_trace"
+
+    def __init__(self, owner, create, every, capacity, threshold):
+        super().__init__(owner, create, int(every), int(capacity), -np.inf if threshold is None else float(threshold))
 
     def read(self):
         """(steps[count, B] int64, rec[count, B, 12]); synchronises the owner's stream."""
@@ -166,55 +186,18 @@ class Trace:
 IFACE_FIELDS = {"rho": 0, "phi": 1}
 
 
-class InterfaceTrace:
+class InterfaceTrace(_Recorder):
     """Contour heights of every column of every replica recorded on the device every `every` steps through the owner (a
     lone single-slab BinaryLBM or a BatchLBM) and read once: include/bflbm.h, "Interface traces".  Made by
     owner.interface_trace(); an owner may carry several."""
+    _abi = "bflbm_iface"
 
     def __init__(self, owner, create, level, field, window, every, capacity):
-        self.lib, self.owner = owner.lib, owner
         if field not in IFACE_FIELDS and field not in IFACE_FIELDS.values():
             raise ValueError(f"interface_trace: field {field!r}, expected 'rho' (0) or 'phi' (1)")
         z_lo, z_hi = (0, owner.n[2]) if window is None else (int(window[0]), int(window[1]))
-        h = ctypes.c_void_p()
-        check(getattr(self.lib, create)(owner._h, int(IFACE_FIELDS.get(field, field)), float(level), z_lo, z_hi, int(every),
-                                        int(capacity), ctypes.byref(h)))
-        self._h = h
+        super().__init__(owner, create, int(IFACE_FIELDS.get(field, field)), float(level), z_lo, z_hi, int(every), int(capacity))
         self.level, self.field, self.window = float(level), field, (z_lo, z_hi)
-        if not hasattr(owner, "_dependents"):
-            owner._dependents = []
-        owner._dependents.append(self)               # closed before the owner it reads
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.bflbm_iface_destroy(self._h)
-            self._h = None
-            deps = getattr(self.owner, "_dependents", [])
-            if self in deps:
-                deps.remove(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def sample(self):
-        """Record the resident state now (e.g. frame 0); the every-counter does not move."""
-        check(self.lib.bflbm_iface_sample(self._h))
-
-    def reset(self):
-        """Forget the samples and restart the every-counter."""
-        check(self.lib.bflbm_iface_reset(self._h))
-
-    def _count(self):
-        n, b = ctypes.c_longlong(), ctypes.c_int()
-        check(self.lib.bflbm_iface_count(self._h, ctypes.byref(n), ctypes.byref(b)))
-        return n.value, b.value
-
-    @property
-    def count(self):
-        return self._count()[0]
 
     def geometry(self):
         """(nx, ny, segments of the scan, pairs (z-1, z) per segment): which launch shape the library chose."""

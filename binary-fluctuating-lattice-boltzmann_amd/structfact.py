@@ -16,6 +16,7 @@ the GPU (hipFFT D2Z on the resident state, csrc/bflbm_sf.h) with the same interf
 import numpy as np
 
 from . import plotfile as pf
+from .lattice import _register, _unregister
 
 # main_run_job.cpp:301-306
 PAIR_A = [0, 1, 0, 2, 3, 4, 6, 7, 8, 2, 9, 15, 16, 17, 15, 18, 19, 20, 21, 20, 20, 21]
@@ -91,17 +92,13 @@ class DeviceStructFact(StructFact):
         self._pre = "bflbm_ring_sf_" if type(lbm).__name__ == "RingLBM" else "bflbm_sf_"
         _lib.check(getattr(lbm.lib, self._pre + "create")(lbm._h, n, a, b, sc, ctypes.byref(h)))
         self._h = h
-        if not hasattr(lbm, "_dependents"):
-            lbm._dependents = []
-        lbm._dependents.append(self)             # closed before the context it lives on
+        _register(lbm, self)                     # closed before the context it lives on
 
     def close(self):
         if getattr(self, "_h", None):
             getattr(self._libh, self._pre + "destroy")(self._h)
             self._h = None
-            deps = getattr(self.lbm, "_dependents", [])
-            if self in deps:
-                deps.remove(self)
+            _unregister(self.lbm, self)
 
     def __del__(self):
         try:
@@ -155,23 +152,17 @@ class BatchStructFact(StructFact):
         h = ctypes.c_void_p()
         _lib.check(batch.lib.bflbm_batch_sf_create(batch._h, n, a, b, sc, int(self.lb), self.every, ctypes.byref(h)))
         self._h = h
-        if not hasattr(batch, "_dependents"):
-            batch._dependents = []
-        batch._dependents.append(self)           # closed before the batch it reads
+        _register(batch, self)
 
     def close(self):
         if getattr(self, "_h", None):
             self._libh.bflbm_batch_sf_destroy(self._h)
             self._h = None
-            deps = getattr(self.batch, "_dependents", [])
-            if self in deps:
-                deps.remove(self)
+            self._owner_closing()
 
     def _owner_closing(self):
         """BatchLBM.close(): bflbm_batch_destroy detaches the accumulator; its spectra stay readable until close()."""
-        deps = getattr(self.batch, "_dependents", [])
-        if self in deps:
-            deps.remove(self)
+        _unregister(self.batch, self)
 
     def __del__(self):
         try:

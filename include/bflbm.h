@@ -337,9 +337,10 @@ int bflbm_trace_read(bflbm_trace* t, long long first, long long count,
  *    and restarts the count; every sample is labelled on the host with each replica's step counter.  bflbm_step,
  *    bflbm_batch_step and bflbm_step_boundary refuse, before any launch and with state and counters untouched, a call
  *    whose samples would not fit ("interface trace full"); bflbm_iface_sample on a full trace is refused the same way.
- *  - an owner may carry several interface traces (rho and phi, two levels ...).  After a step they are served in the order
- *    of their creation, after the owner's ensemble trace and before a batch's structure-factor accumulators; the
- *    capacity check covers all of them before the first launch.
+ *  - an owner may carry several interface traces (rho and phi, two levels ...).  After a step the recorders of all kinds
+ *    on one owner (ensemble trace, interface traces, a batch's structure-factor accumulators) are served in the order of
+ *    their creation; no recorded value depends on that order, and the capacity check covers all of them before the first
+ *    launch.
  *  - refused at creation (non-zero return, a message naming the call, nothing allocated): null arguments, a field other
  *    than 0 or 1, a NaN level, a window outside the lattice or shorter than two planes, every < 1, capacity < 1, a
  *    capacity beyond 1 TB of heights, a replica view (use bflbm_batch_iface_create), a context with nranks > 1, an open
@@ -374,7 +375,7 @@ int bflbm_iface_read(bflbm_iface* t, long long first, long long count,
  *    geometry.  what = 0 of the ensemble is the magnitude of that complex mean, not a mean of magnitudes.
  *  - sampling rule: every = 0: frames are taken only by bflbm_batch_sf_accumulate.  every >= 1: the accumulator is
  *    attached; it counts the steps taken through bflbm_batch_step since its creation or reset and bflbm_batch_step enqueues
- *    a frame after each step at which that count is a multiple of `every` (the trace's rule; after the trace's sample).
+ *    a frame after each step at which that count is a multiple of `every` (the trace's rule; recorders are served in creation order).
  *    bflbm_batch_sf_accumulate is allowed on an attached accumulator and does not move the count, with reset != 0 too
  *    (FortStructure's reset: the running sums and nsamples start again with this frame).  bflbm_batch_sf_reset zeroes the
  *    sums, sets nsamples = 0 and restarts the count.  nsamples counts the frames whose launches were all accepted.
