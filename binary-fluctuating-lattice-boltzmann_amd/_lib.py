@@ -112,6 +112,7 @@ SIGNATURES = {
     "bflbm_batch_resolved_schedule": (ctypes.c_int, [_vp, _P(ctypes.c_int)]),
     "bflbm_batch_step": (ctypes.c_int, [_vp, ctypes.c_int]),
     "bflbm_batch_sync": (ctypes.c_int, [_vp]),
+    "bflbm_fused_plan_query": (ctypes.c_int, [_P(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int)]),
     "bflbm_trace_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, _P(_vp)]),
     "bflbm_batch_trace_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, _P(_vp)]),
     "bflbm_trace_destroy": (ctypes.c_int, [_vp]),

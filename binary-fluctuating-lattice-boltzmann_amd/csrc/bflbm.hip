@@ -493,26 +493,12 @@ int bflbm_device_count(int* n) {
   return 0;
 }
 
-// ext: a replica of a batch (bflbm_batch_create): runs on the batch's stream ext and draws no placement
-static int create_ctx(const bflbm_params* p, const bflbm_domain* d, hipStream_t ext, bflbm_ctx** out) {
-  if (!p || !d || !out) return fail("bflbm_create: null argument");
-  if (d->n[0] < 1 || d->n[1] < 1 || d->n[2] < 1) return fail("bflbm_create: lattice size must be >= 1");
-  if (d->nranks < 1 || d->rank < 0 || d->rank >= d->nranks) return fail("bflbm_create: bad rank/nranks");
-  if (d->z0 < 0 || d->z1 > d->n[2] || d->z1 <= d->z0) return fail("bflbm_create: bad slab [%d,%d) of nz=%d", d->z0, d->z1, d->n[2]);
-  if (d->nranks == 1 && (d->z0 != 0 || d->z1 != d->n[2])) return fail("bflbm_create: a single slab must cover all of z");
-  if (d->nranks > 1 && d->z1 - d->z0 < 4) return fail("bflbm_create: a slab needs at least 4 planes when nranks > 1");
-  if ((long long)(d->n[0] + 15) * d->n[1] * (long long)(d->z1 - d->z0 + 4) >= (1LL << 31)) return fail("bflbm_create: slab too large for 32-bit site offsets");
-  if ((long long)(d->n[0] + 15) * d->n[1] >= (1LL << 28)) return fail("bflbm_create: a plane must stay below 2 GB (32-bit byte offsets inside a plane)");
-  HIP_TRY(hipSetDevice(d->device));
-  bflbm_ctx* c = new bflbm_ctx();
-  c->prm = *p; c->dom = *d;
-  derive(c->prm, c->dp);
-  c->nzl = d->z1 - d->z0;
-  Geo& G = c->G;
+// Storage geometry of the slab [z0, z1) of a domain: host arithmetic only (create_ctx, bflbm_fused_plan_query)
+static void domain_geo(const bflbm_domain* d, Geo& G) {
   G.nx = d->n[0]; G.ny = d->n[1]; G.nz = d->n[2];
   G.zwrap = (d->nranks == 1) ? 1 : 0;
   G.H = G.zwrap ? 0 : 2;
-  G.nzs = c->nzl + 2 * G.H;
+  G.nzs = (d->z1 - d->z0) + 2 * G.H;
   G.z0 = d->z0;
   // rows of the resident arrays start on 128-byte lines for any nx.  Measured against dense rows on one box
   // (A/B of the two libraries, +-0.5 %): 250^3 +1.5 %, 300^3 +3.9 %, 257^3 +2.7 %, no change when nx is a
@@ -528,6 +514,25 @@ static int create_ctx(const bflbm_params* p, const bflbm_domain* d, hipStream_t 
   // The pad is 1040 doubles: 65552 was A/B-tested again in round 2 and is indistinguishable (NOTES.md section 3.1).
   constexpr long long pad = 1040;
   G.vol = G.plane * G.nzs + pad;
+}
+
+// ext: a replica of a batch (bflbm_batch_create): runs on the batch's stream ext and draws no placement
+static int create_ctx(const bflbm_params* p, const bflbm_domain* d, hipStream_t ext, bflbm_ctx** out) {
+  if (!p || !d || !out) return fail("bflbm_create: null argument");
+  if (d->n[0] < 1 || d->n[1] < 1 || d->n[2] < 1) return fail("bflbm_create: lattice size must be >= 1");
+  if (d->nranks < 1 || d->rank < 0 || d->rank >= d->nranks) return fail("bflbm_create: bad rank/nranks");
+  if (d->z0 < 0 || d->z1 > d->n[2] || d->z1 <= d->z0) return fail("bflbm_create: bad slab [%d,%d) of nz=%d", d->z0, d->z1, d->n[2]);
+  if (d->nranks == 1 && (d->z0 != 0 || d->z1 != d->n[2])) return fail("bflbm_create: a single slab must cover all of z");
+  if (d->nranks > 1 && d->z1 - d->z0 < 4) return fail("bflbm_create: a slab needs at least 4 planes when nranks > 1");
+  if ((long long)(d->n[0] + 15) * d->n[1] * (long long)(d->z1 - d->z0 + 4) >= (1LL << 31)) return fail("bflbm_create: slab too large for 32-bit site offsets");
+  if ((long long)(d->n[0] + 15) * d->n[1] >= (1LL << 28)) return fail("bflbm_create: a plane must stay below 2 GB (32-bit byte offsets inside a plane)");
+  HIP_TRY(hipSetDevice(d->device));
+  bflbm_ctx* c = new bflbm_ctx();
+  c->prm = *p; c->dom = *d;
+  derive(c->prm, c->dp);
+  c->nzl = d->z1 - d->z0;
+  domain_geo(d, c->G);
+  const Geo& G = c->G;
   const size_t sbytes = (size_t)2 * Q * G.vol * sizeof(double);
   const size_t fbytes = (size_t)G.vol * sizeof(double);
   hipError_t e = hipSuccess;
@@ -1673,6 +1678,42 @@ int bflbm_batch_sync(bflbm_batch* b) {
   if (!b) return fail("null batch");
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+// The plan of the one-pass schedule for a periodic lattice n[3] (see include/bflbm.h).  Host arithmetic only: the planner
+// functions the launches call (fused_launch, batch_fused_launch), with compute_units > 0 in place of device_cus() for this call.
+int bflbm_fused_plan_query(const int n[3], int nreplicas, int noise, int compute_units, int out[16]) {
+  if (!n || !out) return fail("bflbm_fused_plan_query: null argument");
+  if (nreplicas < 1 || nreplicas > 65535) return fail("bflbm_fused_plan_query: nreplicas must be in 1..65535 (got %d)", nreplicas);
+  if (n[0] < 1 || n[1] < 1 || n[2] < 1) return fail("bflbm_fused_plan_query: lattice size must be >= 1 (got %d x %d x %d)", n[0], n[1], n[2]);
+  if ((long long)(n[0] + 15) * n[1] * (long long)(n[2] + 4) >= (1LL << 31) || (long long)(n[0] + 15) * n[1] >= (1LL << 28))
+    return fail("bflbm_fused_plan_query: %d x %d x %d is too large for 32-bit site offsets", n[0], n[1], n[2]);
+  if (compute_units < 0) return fail("bflbm_fused_plan_query: compute_units < 0");
+  bflbm_domain d;
+  for (int a = 0; a < 3; ++a) d.n[a] = n[a];
+  d.z0 = 0; d.z1 = n[2]; d.rank = 0; d.nranks = 1; d.device = 0;
+  Geo G;
+  domain_geo(&d, G);
+  const int mode = noise ? 1 : 0;
+  const int held = g_fused_ncu;
+  if (compute_units > 0) g_fused_ncu = compute_units;
+  FusedGrid F;
+  const int threads = nreplicas == 1 ? FUSED_TX * FUSED_TY : batch_fused_threads(mode);
+  const int TX = nreplicas == 1 ? fused_plan(G, 0, G.nzs, mode, 0, F) : batch_fused_plan(G, nreplicas, mode, F);
+  const int ncu = device_cus();
+  g_fused_ncu = held;
+  const long long all = (long long)nreplicas * F.total;
+  const long long per_xcd = nreplicas == 1 ? F.per_xcd : (all + 7) / 8;   // the lists of fused_map and batch_map
+  if (per_xcd * 8 > (long long)INT32_MAX) return fail("bflbm_fused_plan_query: the launch exceeds 2^31 workgroups");
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  out[0] = TX; out[1] = threads / TX;
+  out[2] = F.ntx; out[3] = F.nty; out[4] = F.sx;
+  out[5] = F.lz; out[6] = F.nchunks; out[7] = (F.pb - F.pa) - (F.nchunks - 1) * F.cstride;
+  out[8] = F.total; out[9] = (int)all;
+  out[10] = (int)((all + ncu - 1) / ncu);
+  out[11] = (int)per_xcd; out[12] = (int)(per_xcd * 8);
+  out[13] = ncu;
   return 0;
 }
 

@@ -821,6 +821,21 @@ class BatchLBM:
         return out
 
 
+PLAN_FIELDS = ("tile_x", "tile_y", "ntx", "nty", "sx", "planes_per_chunk", "chunks", "last_chunk_planes",
+               "workgroups_per_replica", "workgroups", "rounds", "per_xcd", "grid", "compute_units")
+
+
+def fused_plan_query(n, replicas=1, noise=False, compute_units=0):
+    """The launch plan of the one-pass schedule for a lattice n = (nx, ny, nz): a lone lattice (replicas=1) or a batch,
+    from the library's own planner (bflbm_fused_plan_query; no device needed).  compute_units=0: the device's count once
+    a context exists, 256 before.  -> dict of PLAN_FIELDS."""
+    n = (n, n, n) if np.isscalar(n) else tuple(n)
+    n3 = (ctypes.c_int * 3)(*[int(v) for v in n])
+    out = (ctypes.c_int * 16)()
+    check(_lib.load().bflbm_fused_plan_query(n3, int(replicas), int(bool(noise)), int(compute_units), out))
+    return dict(zip(PLAN_FIELDS, list(out)))
+
+
 def rng_site_normals(seed, site, noise_index):
     """Host evaluation of the project's Gaussian stream: the 33 normals of one site and noise index."""
     out = (ctypes.c_double * 36)()

@@ -264,6 +264,22 @@ int bflbm_batch_resolved_schedule(const bflbm_batch* b, int* schedule);
 int bflbm_batch_step(bflbm_batch* b, int nsteps);
 int bflbm_batch_sync(bflbm_batch* b);
 
+/* The launch plan of the one-pass schedule (1) for a periodic lattice n[3]: the tile shape, the z-chunking and the work
+ * list that bflbm_step (nreplicas == 1) or bflbm_batch_step (nreplicas > 1: a batch, with its 256-thread tile when
+ * noise != 0) would use, worked out by the planner the launches themselves call.  Host arithmetic only: it needs no
+ * device and no context, so a test can state which plan its case exercises.  compute_units > 0 replaces the device's
+ * compute-unit count for this call only; 0 is the count the library currently holds (the device's once a context was
+ * created on it, 256 before).  out[0..13], the rest zero:
+ *    0 tile width, 1 tile height (threads = width x height);
+ *    2 tiles in x, 3 tiles in y, 4 strip width in tiles of the column order;
+ *    5 planes per chunk, 6 chunks, 7 planes in the last chunk;
+ *    8 workgroups per replica, 9 workgroups over all replicas;
+ *   10 rounds = ceil(workgroups / compute units);
+ *   11 length of one XCD's part of the work list, 12 grid size launched (8 x that; the excess workgroups leave at once);
+ *   13 the compute units used.
+ * Fails on a null pointer, a size < 1 or too large for a context, nreplicas outside 1..65535, compute_units < 0. */
+int bflbm_fused_plan_query(const int n[3], int nreplicas, int noise, int compute_units, int out[16]);
+
 /* ---- Ensemble traces: droplet moments of every replica recorded on the device, read once at the end (the notebooks
  * observe their ensembles every step: nine 32^3 droplets in Surface_Tension.ipynb, a 64^3 droplet's centre of mass 3201
  * times in Droplet_Fluctuation.ipynb, whose estimator where(rho > 0.06, rho, 0) is threshold = 0.06).
