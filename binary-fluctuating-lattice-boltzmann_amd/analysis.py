@@ -10,6 +10,9 @@ so that no field has to leave the GPU; BinaryLBM.fit_droplet is the device versi
 Conventions of the notebooks: coordinates are cell centres (i + 1/2)/n of a unit box; fields are
 indexed [x, y, z] there -- pass `rho_xyz = rho.transpose(2, 1, 0)` for an array in (z, y, x) order.
 """
+import functools
+import math
+
 import numpy as np
 
 
@@ -123,6 +126,86 @@ def capillary_spectrum(h, axes=(-1,)):
         raise ValueError(f"capillary_spectrum: axes {axes} of an array with {h.ndim} dimensions (axis 0 is time)")
     hq = np.fft.fftn(h - h.mean(axis=0), axes=axes)
     return (np.abs(hq) ** 2).mean(axis=0), tuple(2 * np.pi * np.fft.fftfreq(h.shape[a]) for a in axes)
+
+
+# ---- binned structure factors: the numpy restatement of the spectrum trace (include/bflbm.h, "Spectrum traces") ----------
+SPECTRUM_KINDS = {"shell": 0, "x": 1, "y": 2, "z": 3}
+
+
+def _shell_of(k2, w):
+    """The integer s >= 0 with (2s-1)^2 w^2 <= 4 k2 < (2s+1)^2 w^2, in Python integers."""
+    s = (math.isqrt(4 * k2) // w + 1) // 2
+    while s > 0 and (2 * s - 1) ** 2 * w * w > 4 * k2:
+        s -= 1
+    while (2 * s + 1) ** 2 * w * w <= 4 * k2:
+        s += 1
+    return s
+
+
+@functools.lru_cache(maxsize=8)
+def _spectrum_bins(n, kind, zero_avg):
+    nx, ny, nz = n
+    kx, ky, kz = [np.minimum(np.arange(m), m - np.arange(m)).astype(np.int64) for m in (nx, ny, nz)]   # |k| in fftn's order
+    if kind == 0:
+        L = math.lcm(nx, ny, nz)
+        if 12 * (L // 2) ** 2 >= 2 ** 63:
+            raise ValueError(f"spectrum_bins: lcm{n} = {L} is too large for shells: 12 (L/2)^2 must fit in 63 bits")
+        w = L // max(n)
+        k2 = ((kz * (L // nz)) ** 2)[:, None, None] + ((ky * (L // ny)) ** 2)[None, :, None] + ((kx * (L // nx)) ** 2)[None, None, :]
+        values, inverse = np.unique(k2, return_inverse=True)
+        bins = np.array([_shell_of(int(v), w) for v in values], dtype=np.int64)[inverse].reshape(k2.shape)
+    else:
+        bins = np.broadcast_to([kx[None, None, :], ky[None, :, None], kz[:, None, None]][kind - 1], (nz, ny, nx)).copy()
+    nbins = int(bins.max()) + 1
+    if zero_avg:
+        bins[0, 0, 0] = -1
+    keep = bins.ravel() >= 0
+    count = np.bincount(bins.ravel()[keep], minlength=nbins).astype(np.int64)
+    if kind == 0:
+        fx, fy, fz = kx / nx, ky / ny, kz / nz
+        q_mode = 2.0 * np.pi * np.sqrt((fx * fx)[None, None, :] + (fy * fy)[None, :, None] + (fz * fz)[:, None, None])
+        order = np.argsort(bins.ravel()[keep], kind="stable")
+        sorted_q = q_mode.ravel()[keep][order].astype(np.longdouble)
+        q = np.full(nbins, np.nan)
+        filled = np.flatnonzero(count)
+        starts = (np.cumsum(count) - count)[filled]
+        q[filled] = (np.add.reduceat(sorted_q, starts) / count[filled].astype(np.longdouble)).astype(np.float64)
+    else:
+        q = 2.0 * np.pi * np.arange(nbins) / float(n[kind - 1])
+    for a in (bins, count, q):
+        a.setflags(write=False)
+    return bins, count, q
+
+
+def spectrum_bins(n, kind, zero_avg=True):
+    """The bins of a spectrum trace on an n = (nx, ny, nz) lattice; kind "shell" (0), "x" (1), "y" (2) or "z" (3).
+    Returns (bin[nz, ny, nx] of every full-spectrum mode in numpy's fftn layout, -1 for the k = 0 mode that zero_avg
+    leaves out; count[nbins] int64; q[nbins]).  The shell of a mode is decided in Python integers (math.isqrt)."""
+    n = (n, n, n) if np.isscalar(n) else tuple(int(v) for v in n)
+    kind = SPECTRUM_KINDS.get(kind, kind)
+    if kind not in (0, 1, 2, 3):
+        raise ValueError(f"spectrum_bins: kind {kind!r}, expected one of {sorted(SPECTRUM_KINDS)} or 0..3")
+    return _spectrum_bins(n, int(kind), bool(zero_avg))
+
+
+def binned_spectrum(a_zyx, b_zyx, kind, zero_avg=True, scale=1.0):
+    """sum[bin] of S_ab(k) = scale Re(a^(k) conj(b^(k))) / N over the full spectrum (numpy fftn) of two fields [nz, ny, nx]."""
+    a, b = np.asarray(a_zyx, dtype=np.float64), np.asarray(b_zyx, dtype=np.float64)
+    if a.ndim != 3 or a.shape != b.shape:
+        raise ValueError(f"binned_spectrum: two fields [nz, ny, nx] of one shape, got {a.shape} and {b.shape}")
+    bins, count, _ = spectrum_bins(a.shape[::-1], kind, zero_avg)
+    s = (scale * np.fft.fftn(a) * np.conj(np.fft.fftn(b))).real / a.size
+    keep = bins.ravel() >= 0
+    return np.bincount(bins.ravel()[keep], weights=s.ravel()[keep], minlength=len(count))
+
+
+def domain_length(q, s_mean):
+    """L = 2 pi sum_{bin >= 1} S / sum_{bin >= 1} q S, the inverse first moment of a binned spectrum s_mean[..., nbins]
+    (sums / count); bins without modes (NaN) do not enter."""
+    q, s = np.asarray(q, dtype=np.float64), np.asarray(s_mean, dtype=np.float64)
+    ok = np.isfinite(q[1:]) & np.isfinite(s[..., 1:])
+    top = np.where(ok, s[..., 1:], 0.0).sum(axis=-1)
+    return 2.0 * np.pi * top / np.where(ok, q[1:] * s[..., 1:], 0.0).sum(axis=-1)
 
 
 # ---- the same observables from the device-reduced raw moments (BinaryLBM.droplet_moments) ----------------

@@ -1,5 +1,6 @@
 // bflbm_recorder.h -- the one lifecycle of everything that records from an owner's resident state: ensemble traces
-// (bflbm_trace.h), interface traces (bflbm_iface.h) and ensemble structure factors (bflbm_batch_sf.h).  A recorder is
+// (bflbm_trace.h), interface traces (bflbm_iface.h), spectrum traces (bflbm_spectrum.h) and ensemble structure factors
+// (bflbm_batch_sf.h).  A recorder is
 // attached to a lone context or a batch, is served after every step on the owner's stream in creation order, survives
 // its owner detached (readable, no longer fed) and is destroyed by its own call ("Recorders").
 // Host code only.  Included by bflbm.hip once bflbm_ctx and bflbm_batch are complete (needs fail, HIP_TRY).
@@ -23,7 +24,7 @@ struct bflbm_recorder {
   virtual int record() = 0;        // enqueue one sample (frame) of the resident state now; no host synchronisation
 };
 
-// what the two trace kinds add: `capacity` samples of `per` doubles on the device, and a stage buffer of the kind's own
+// what the trace kinds add: `capacity` samples of `per` doubles on the device, and a stage buffer of the kind's own
 struct bflbm_sample_store : bflbm_recorder {
   using bflbm_recorder::bflbm_recorder;
   size_t per = 0;

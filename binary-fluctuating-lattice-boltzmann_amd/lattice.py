@@ -224,6 +224,75 @@ class InterfaceTrace(_Recorder):
         return self.read()[1][:, :, 1]
 
 
+class SpectrumTrace(_Recorder):
+    """The structure factor of chosen pairs of hydrodynamic variables of every sample, binned into shells in |q| or into
+    |k| along one axis, recorded on the device every `every` steps through the owner (a lone single-slab BinaryLBM or a
+    BatchLBM) and read once: include/bflbm.h, "Spectrum traces".  Made by owner.spectrum_trace(); an owner may carry
+    several.  Closing the owner detaches the trace: it stays readable until its own close()."""
+    _abi = "bflbm_spectrum"
+
+    def __init__(self, owner, create, names_or_pairs, kind, every, capacity, lb_hydrovars, zero_avg, var_scaling):
+        from . import analysis, structfact
+        if isinstance(kind, str) and kind not in analysis.SPECTRUM_KINDS:
+            raise ValueError(f"spectrum_trace: kind {kind!r}, expected one of {sorted(analysis.SPECTRUM_KINDS)} or 0..3")
+        items = list(names_or_pairs)
+        if items and isinstance(items[0], str):              # variable names: the pairs of structfact.StructFact
+            self.names = items
+            self.pairs = structfact.StructFact(items).pairs
+        else:
+            self.names = None
+            self.pairs = [(int(a), int(b)) for a, b in items]
+        n = len(self.pairs)
+        self.scale = [1.0] * n if var_scaling is None else [float(v) for v in var_scaling]
+        if len(self.scale) != n:
+            raise ValueError(f"spectrum_trace: {len(self.scale)} scalings for {n} pairs")
+        self.kind, self.lb, self.zero_avg = int(analysis.SPECTRUM_KINDS.get(kind, kind)), bool(lb_hydrovars), bool(zero_avg)
+        a = (ctypes.c_int * max(n, 1))(*[p[0] for p in self.pairs])
+        b = (ctypes.c_int * max(n, 1))(*[p[1] for p in self.pairs])
+        sc = (ctypes.c_double * max(n, 1))(*self.scale)
+        super().__init__(owner, create, n, a, b, sc, int(self.lb), self.kind, int(self.zero_avg), int(every), int(capacity))
+
+    def _owner_closing(self):
+        """The owner's close(): the library detaches the trace; its samples stay readable until close()."""
+        _unregister(self.owner, self)
+
+    def pair_names(self):
+        names = self.names
+        if names is None:
+            from . import plotfile
+            names = plotfile.variable_names(NHYDROBAR if self.lb else NHYDRO)
+        return ["struct_fact_%s_%s" % (names[b], names[a]) for a, b in self.pairs]
+
+    def geometry(self):
+        """(bins, pairs, chunks of the sorted index list, the most chunks any bin has): what the library built."""
+        v = [ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong(), ctypes.c_int()]
+        check(self.lib.bflbm_spectrum_geometry(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def bins(self):
+        """(count[nbins] int64: full-spectrum modes per bin, q[nbins]: the bin's wave number)."""
+        nbins = self.geometry()[0]
+        count, q = np.empty(nbins, dtype=np.int64), np.empty(nbins)
+        check(self.lib.bflbm_spectrum_bins(self._h, _ptr(count), _ptr(q)))
+        return count, q
+
+    def read(self):
+        """(steps[count, B] int64, sums[count, B, npairs, nbins]); synchronises the owner's stream."""
+        n, b = self._count()
+        nbins, npairs = self.geometry()[:2]
+        steps = np.empty((n, b), dtype=np.int64)
+        sums = np.empty((n, b, npairs, nbins))
+        check(self.lib.bflbm_spectrum_read(self._h, 0, n, _ptr(sums), _ptr(steps)))
+        return steps, sums
+
+    def mean(self):
+        """sums / count [count, B, npairs, nbins]: the bin averages, NaN where a bin has no modes."""
+        count = self.bins()[0]
+        sums = self.read()[1]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(count > 0, sums / count, np.nan)
+
+
 # kernel schedules of include/bflbm.h (bflbm_set_schedule): "fused" = plane march with the ring densities pulled
 # (bit-exact), "handover" = plane march with the ring densities handed over from the previous step (tolerance)
 SCHEDULES = {"two_pass": 0, "fused": 1, "fused_exact": 1, "auto": 2, "handover": 3}
@@ -269,8 +338,8 @@ class BinaryLBM(_DropletMixin):
     # -- lifetime -------------------------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None):
-            for d in list(getattr(self, "_dependents", [])):   # e.g. structure-factor accumulators living on this context
-                d.close()
+            for d in list(getattr(self, "_dependents", [])):   # e.g. structure-factor accumulators living on this context:
+                getattr(d, "_owner_closing", d.close)()        # closed; a spectrum trace: detached by the library, still readable
             if not getattr(self, "_borrowed", False):
                 self.lib.bflbm_destroy(self._h)
             self._h = None
@@ -449,6 +518,12 @@ class BinaryLBM(_DropletMixin):
         The device buffer of `capacity` samples is allocated at once: capacity x 2 ny nx doubles (the default 64 takes
         256 MiB on a 512 x 512 column lattice); a step whose sample would not fit is refused, so size it for the run."""
         return InterfaceTrace(self, "bflbm_iface_create", level, field, window, every, capacity)
+
+    def spectrum_trace(self, var_names_or_pairs, kind="shell", every=1, capacity=64, lb_hydrovars=False, zero_avg=True, var_scaling=None):
+        """Record, after every `every`-th step, the structure factor of pairs of hydrovs (lb_hydrovars: hydrovsbar)
+        variables binned into shells in |q| (kind "shell") or into |k| along one axis ("x", "y", "z"): SpectrumTrace.
+        Variable names form the pairs of structfact.StructFact; a list of index pairs (a, b) is taken as it is."""
+        return SpectrumTrace(self, "bflbm_spectrum_create", var_names_or_pairs, kind, every, capacity, lb_hydrovars, zero_avg, var_scaling)
 
     def com_sums(self):
         s = (ctypes.c_double * 4)()
@@ -794,6 +869,11 @@ class BatchLBM:
         device buffer is allocated at once: capacity x B x 2 ny nx doubles (the default 64 takes 32 MiB for 16 replicas
         of 8 x 256 columns)."""
         return InterfaceTrace(self, "bflbm_batch_iface_create", level, field, window, every, capacity)
+
+    def spectrum_trace(self, var_names_or_pairs, kind="shell", every=1, capacity=64, lb_hydrovars=False, zero_avg=True, var_scaling=None):
+        """Record every replica's binned structure factors (BinaryLBM.spectrum_trace) after every `every`-th batch step,
+        with one observation launch, one batched transform and two binning launches per sample."""
+        return SpectrumTrace(self, "bflbm_batch_spectrum_create", var_names_or_pairs, kind, every, capacity, lb_hydrovars, zero_avg, var_scaling)
 
     def structfact(self, var_names, **kw):
         """One structure-factor accumulator for the whole batch (structfact.BatchStructFact; every=k attaches it)."""

@@ -423,6 +423,75 @@ int bflbm_batch_sf_get(bflbm_batch_sf* s, int replica, int what, int zero_avg, d
 int bflbm_batch_get_hydrovs(bflbm_batch* b, double* dst, int ncomp);     /* dst[B][ncomp][nz][ny][nx] */
 int bflbm_batch_get_hydrovsbar(bflbm_batch* b, double* dst, int ncomp);
 
+/* ---- Spectrum traces: the structure factor of every sample, binned, recorded on the device as a time series and read
+ * once at the end (the observable of a coarsening mixture: the shell-averaged S(k, t) of rho - phi and its first moment,
+ * the domain length; Mixture.ipynb cell 2 reads the spectra reduced to the kx axis).  The accumulators above keep one
+ * running mean of the full 3-D spectrum; a spectrum trace keeps, per sample, replica and pair, one sum per bin.
+ * A spectrum trace is attached to one lone single-slab context or one replica batch, like an ensemble trace.
+ *  - definition (stated here and nowhere else).  For a pair (a, b) of real fields on the nx x ny x nz periodic lattice,
+ *    N = nx ny nz, a^ the unnormalised DFT as in bflbm_sf_*:
+ *      S_ab(k) = scale Re(a^(k) conj(b^(k))) / N        over the FULL spectrum,
+ *    with the signed integer frequencies kx in (-nx/2, nx/2], ky, kz likewise; only |kx|, |ky|, |kz| enter a bin.  The
+ *    imaginary parts of k and -k cancel in every bin, so only the real part is recorded.  A sample holds
+ *      sum[bin] = sum over the modes k with bin(k) = bin of S_ab(k).
+ *    Bin rules (`kind`):
+ *      0, shells:  L = lcm(nx, ny, nz), W = L / max(nx, ny, nz), K2 = (kx L/nx)^2 + (ky L/ny)^2 + (kz L/nz)^2 (an exact
+ *                  64-bit integer); bin(k) is the integer s >= 0 with (2s-1)^2 W^2 <= 4 K2 < (2s+1)^2 W^2 (s = 0: the
+ *                  upper bound alone, i.e. (2s-1) W <= 2 sqrt(K2) < (2s+1) W): |q| rounded half up in units of the
+ *                  smallest non-zero wavenumber of the longest axis, decided in integers, never through a
+ *                  floating-point square root.  A cubic box gives the usual round(|k|) shells (16^3: 15 bins
+ *                  with 1, 18, 62, 98, 210, 350, ... modes).  Refused where 12 (L/2)^2 does not fit in 63 bits.
+ *      1, 2, 3:    axis x, y, z: bin(k) = |kx| (|ky|, |kz|), summed over the other two axes.
+ *    zero_avg != 0 (WritePlotFile's flag) leaves the k = 0 mode out of the sum AND out of the count of bin 0.
+ *    The number of bins is the largest bin of any mode plus one.  Per bin the geometry fixes
+ *      count[bin]: the number of full-spectrum modes in the bin (they add up to N, or N - 1 with zero_avg),
+ *      q[bin]:     kind 0: the mean over the bin's modes of |q| = 2 pi sqrt((kx/nx)^2 + (ky/ny)^2 + (kz/nz)^2), a quiet
+ *                  NaN for a bin without modes; kinds 1-3: 2 pi bin / n_axis.
+ *    From the half spectrum hipFFT returns (mx = 0 ... nx/2) a mode has weight 1 where mx = 0 or 2 mx = nx and weight 2
+ *    otherwise; its partner -k lies in the same bin by construction.
+ *  - sample: [replica][pair][bin] doubles.  Pairs, scale and lb_hydrovars (0: var_a / var_b index hydrovs, != 0:
+ *    hydrovsbar) are those of bflbm_batch_sf_create, fixed at creation.
+ *  - how a sample is taken, on the owner's stream and without a host synchronisation: the accumulators' observation (a
+ *    batch: one launch over all replicas, only the variables that occur in a pair, into a buffer of the trace; a lone
+ *    context: into its scratch state buffer, as bflbm_sf_accumulate), hipFFT D2Z (a batch: one plan of B x distinct
+ *    variables transforms; a lone context: one execution per distinct variable), and two binning launches.  At creation
+ *    the trace sorts the half-spectrum indices by (bin, index) into a list of 32-bit indices (4 B per half-spectrum
+ *    point; refused beyond 2^32 points) and cuts it into chunks of at most 2048 entries that never cross a bin (an
+ *    untimed heuristic; bflbm_spectrum_geometry reports the outcome).  Stage 1 gives every (chunk, pair, replica) a
+ *    workgroup of 256 threads; a thread adds weight (scale a^) . b^ / N of the chunk's entries tid, tid + 256, ... in
+ *    that order, the workgroup adds the 256 sums by a binary tree.  Stage 2 adds, per (bin, pair, replica), the bin's
+ *    chunk sums in chunk order and writes the sample's slot.  No atomics: a record depends on the spectra and the
+ *    chunk table alone, not on the number of replicas, `every`, the capacity or what else is attached.
+ *  - what is touched on the owner: what the accumulators touch.  Observing hydrovs rewrites rho / phi by the density
+ *    pass where they are stale; a lone context's scratch state buffer is overwritten (between steps it holds nothing
+ *    the next step reads).  The resident state, the step counters and everything the owner computes are unchanged.
+ *  - sampling rule, capacity, step labels, order among the recorders of one owner: those of the ensemble and interface
+ *    traces above ("spectrum trace full").  An owner may carry any number of spectrum traces.
+ *  - refused at creation (non-zero return, a message naming the call, nothing allocated): null arguments, npairs outside
+ *    1..32, a variable outside hydrovs (with lb_hydrovars: outside hydrovsbar), kind outside 0..3, every < 1,
+ *    capacity < 1, a capacity beyond 1 TB of sums, the 2^32 and 63-bit limits above, a replica view (use
+ *    bflbm_batch_spectrum_create), a context with nranks > 1, an open step, a failed allocation (the message gives the
+ *    bytes of each buffer).  An open step also refuses bflbm_spectrum_sample, _reset and _read.
+ *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_spectrum_read, _count,
+ *    _geometry, _bins and _destroy still work, bflbm_spectrum_sample fails.
+ *  - creation uploads the tables with blocking copies.  After it only bflbm_spectrum_read and bflbm_spectrum_destroy
+ *    synchronise the owner's stream. */
+typedef struct bflbm_spectrum bflbm_spectrum;
+int bflbm_spectrum_create(bflbm_ctx* c, int npairs, const int* var_a, const int* var_b, const double* scale /* or NULL */,
+                          int lb_hydrovars, int kind, int zero_avg, int every, long long capacity, bflbm_spectrum** out);
+int bflbm_batch_spectrum_create(bflbm_batch* b, int npairs, const int* var_a, const int* var_b, const double* scale /* or NULL */,
+                                int lb_hydrovars, int kind, int zero_avg, int every, long long capacity, bflbm_spectrum** out);
+int bflbm_spectrum_destroy(bflbm_spectrum* t);
+int bflbm_spectrum_sample(bflbm_spectrum* t);              /* record the resident state now (e.g. frame 0) */
+int bflbm_spectrum_reset(bflbm_spectrum* t);               /* forget the samples, restart the every-counter */
+int bflbm_spectrum_count(const bflbm_spectrum* t, long long* nsamples, int* nreplicas);
+int bflbm_spectrum_geometry(const bflbm_spectrum* t, int* nbins, int* npairs, long long* nchunks /* of stage 1 */,
+                            int* max_chunks_per_bin);
+int bflbm_spectrum_bins(const bflbm_spectrum* t, long long* count /* [nbins] */, double* q /* [nbins] */);
+int bflbm_spectrum_read(bflbm_spectrum* t, long long first, long long count,
+                        double* sums  /* [count][nreplicas][npairs][nbins] */,
+                        long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
+
 /* Materialise the per-step fields the reference keeps in MultiFabs, for the state
  * after the last completed step:
  *   hydrovsbar comps 0..8  (LBM_hydrovars_density, LBM_binary.H:315-354)
