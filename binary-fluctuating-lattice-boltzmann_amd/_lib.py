@@ -115,6 +115,7 @@ SIGNATURES = {
     "bflbm_fused_plan_query": (ctypes.c_int, [_P(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int)]),
     "bflbm_trace_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, _P(_vp)]),
     "bflbm_batch_trace_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, _P(_vp)]),
+    "bflbm_ring_trace_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, _P(_vp)]),
     "bflbm_trace_destroy": (ctypes.c_int, [_vp]),
     "bflbm_trace_sample": (ctypes.c_int, [_vp]),
     "bflbm_trace_reset": (ctypes.c_int, [_vp]),
@@ -136,6 +137,7 @@ SIGNATURES = {
     "bflbm_batch_sf_get": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
     "bflbm_spectrum_create": (ctypes.c_int, [_vp, ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
     "bflbm_batch_spectrum_create": (ctypes.c_int, [_vp, ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_ring_spectrum_create": (ctypes.c_int, [_vp, ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
     "bflbm_spectrum_destroy": (ctypes.c_int, [_vp]),
     "bflbm_spectrum_sample": (ctypes.c_int, [_vp]),
     "bflbm_spectrum_reset": (ctypes.c_int, [_vp]),

@@ -147,6 +147,20 @@ struct bflbm_batch {
   size_t obs_doubles = 0;
 };
 
+// single-process ring of slabs (include/bflbm.h, "Ring")
+struct bflbm_ring {
+  std::vector<bflbm_ctx*> ctx;
+  std::vector<hipStream_t> comm;        // per slab: copies + unpack, concurrent with the interior kernel
+  std::vector<hipEvent_t> packed;       // per slab: the planes its neighbours copy are final (recorded on the slab's main stream)
+  std::vector<hipEvent_t> unpacked;     // per slab: both halo faces stored (recorded on the comm stream)
+  std::vector<std::array<bool, 2>> peer_ok;   // per slab: kernels on its device may read the lower / upper neighbour's memory
+  size_t bytes = 0;
+  bool overlap = true;                  // false: the faces move after the interior sweep (measures what the overlap buys)
+  int transport = 0;                    // 0: gather kernel reading the neighbour in place where reachable; 1: copy engine, one copy per plane
+  int last_kernel_faces = 0, last_copy_faces = 0;   // what the last exchange used
+  std::vector<bflbm_recorder*> recorders;     // what records from this ring of more than one slab (bflbm_recorder.h), in creation order
+};
+
 #include "bflbm_recorder.h"
 
 namespace {
@@ -1220,18 +1234,14 @@ int bflbm_device_bytes(const bflbm_ctx* c, size_t* bytes) {
 }
 
 
-// ---- single-process ring of slabs -----------------------------------------------------------
-struct bflbm_ring {
-  std::vector<bflbm_ctx*> ctx;
-  std::vector<hipStream_t> comm;        // per slab: copies + unpack, concurrent with the interior kernel
-  std::vector<hipEvent_t> packed;       // per slab: the planes its neighbours copy are final (recorded on the slab's main stream)
-  std::vector<hipEvent_t> unpacked;     // per slab: both halo faces stored (recorded on the comm stream)
-  std::vector<std::array<bool, 2>> peer_ok;   // per slab: kernels on its device may read the lower / upper neighbour's memory
-  size_t bytes = 0;
-  bool overlap = true;                  // false: the faces move after the interior sweep (measures what the overlap buys)
-  int transport = 0;                    // 0: gather kernel reading the neighbour in place where reachable; 1: copy engine, one copy per plane
-  int last_kernel_faces = 0, last_copy_faces = 0;   // what the last exchange used
-};
+// ---- single-process ring of slabs (struct bflbm_ring: above, with the other owners of recorders) ----------------------
+
+// BFLBM_RING_COPY_FALLBACK=1 forces the copy paths (what GPUs without peer mapping get) in ring_copy and in the transpose of
+// a ring's spectrum trace, so that both branches are exercised on a one-GPU box (tests/test_gpu_slabs.py); read once
+static bool ring_force_copies() {
+  static const bool force = [] { const char* e = getenv("BFLBM_RING_COPY_FALLBACK"); return e && atoi(e) != 0; }();
+  return force;
+}
 
 // Halo exchange of the ring without staging: every (component, plane) entry of the halo table is one
 // contiguous plane (pitch*ny doubles) in the source slab and in the destination slab, so each face is moved by
@@ -1268,10 +1278,7 @@ static int ring_copy(bflbm_ring* r, int kind) {
       double* dst_base = halo_buffer(c, kind);
       const double* src_base = halo_buffer(src, kind);
       for (int e = 0; e < 2 * Q; ++e) if (Tu.comp[e] != Tp.comp[e]) return fail("halo tables of neighbouring slabs disagree");
-      // BFLBM_RING_COPY_FALLBACK=1 forces the per-plane copies (what a pair of GPUs without peer mapping gets), so that
-      // both branches are exercised on a one-GPU box (tests/test_gpu_slabs.py)
-      static const bool force_copies = [] { const char* e = getenv("BFLBM_RING_COPY_FALLBACK"); return e && atoi(e) != 0; }();
-      const bool reachable = !force_copies && r->transport == 0 && ((src->dom.device == c->dom.device) || r->peer_ok[k][side]);
+      const bool reachable = !ring_force_copies() && r->transport == 0 && ((src->dom.device == c->dom.device) || r->peer_ok[k][side]);
       if (reachable && (c->G.plane % 2 == 0) && (c->G.vol % 2 == 0) && (src->G.vol % 2 == 0)) {
         ++r->last_kernel_faces;
         // one gather kernel per face reads the neighbour's planes in place (peer memory over xGMI between GPUs)
@@ -1358,6 +1365,7 @@ int bflbm_ring_create(const bflbm_params* p, const int n[3], int nslabs, const i
 
 int bflbm_ring_destroy(bflbm_ring* r) {
   if (!r) return 0;
+  recorders_detach_all(r);                                  // what they recorded stays readable
   for (size_t k = 0; k < r->ctx.size(); ++k) {
     hipSetDevice(r->ctx[k]->dom.device);
     if (k < r->comm.size() && r->comm[k]) { hipStreamSynchronize(r->comm[k]); hipStreamDestroy(r->comm[k]); }
@@ -1476,7 +1484,8 @@ int bflbm_ring_prepare_ref(bflbm_ring* r) {     // before reading noise / hydrov
 int bflbm_ring_step(bflbm_ring* r, int nsteps) {
   if (!r) return fail("null ring");
   if (nsteps < 0) return fail("nsteps < 0");
-  if (r->ctx.size() == 1) return bflbm_step(r->ctx[0], nsteps);
+  if (r->ctx.size() == 1) return bflbm_step(r->ctx[0], nsteps);     // its recorders are ctx[0]'s own
+  if (recorders_refuse_full(r, "bflbm_ring_step", nsteps)) return 1;
   for (int s = 0; s < nsteps; ++s) {
     if (ring_prepare_ref(r)) return 1;
     for (bflbm_ctx* c : r->ctx) if (bflbm_step_boundary(c)) return 1;
@@ -1487,6 +1496,7 @@ int bflbm_ring_step(bflbm_ring* r, int nsteps) {
                                                             // interior launches so that the 76 copy calls per slab delay nothing)
     if (ring_join(r)) return 1;
     for (bflbm_ctx* c : r->ctx) if (bflbm_step_finish(c)) return 1;
+    if (recorders_after_step(r)) return 1;                  // the halos ring_join made final are the resident state's
   }
   return 0;
 }
@@ -1726,3 +1736,4 @@ int bflbm_fused_plan_query(const int n[3], int nreplicas, int noise, int compute
 #include "bflbm_iface.h"
 #include "bflbm_batch_sf.h"
 #include "bflbm_spectrum.h"
+#include "bflbm_spectrum_ring.h"

@@ -1,15 +1,18 @@
 // bflbm_recorder.h -- the one lifecycle of everything that records from an owner's resident state: ensemble traces
 // (bflbm_trace.h), interface traces (bflbm_iface.h), spectrum traces (bflbm_spectrum.h) and ensemble structure factors
 // (bflbm_batch_sf.h).  A recorder is
-// attached to a lone context or a batch, is served after every step on the owner's stream in creation order, survives
-// its owner detached (readable, no longer fed) and is destroyed by its own call ("Recorders").
-// Host code only.  Included by bflbm.hip once bflbm_ctx and bflbm_batch are complete (needs fail, HIP_TRY).
+// attached to a lone context, a batch or a ring of more than one slab, is served after every step on the owner's stream(s)
+// in creation order, survives its owner detached (readable, no longer fed) and is destroyed by its own call (DESIGN.md,
+// "Recorders").  A ring serves its recorders from bflbm_ring_step only, after the bflbm_step_finish of every slab; its
+// samples carry slab 0's step counter and its records live on slab 0's device, written on slab 0's stream.
+// Host code only.  Included by bflbm.hip once bflbm_ctx, bflbm_batch and bflbm_ring are complete (needs fail, HIP_TRY).
 #ifndef BFLBM_RECORDER_H_
 #define BFLBM_RECORDER_H_
 
 struct bflbm_recorder {
   bflbm_ctx* ctx = nullptr;        // the owner: a lone context ...
-  bflbm_batch* batch = nullptr;    // ... or a batch; both null once the owner is gone (detached)
+  bflbm_batch* batch = nullptr;    // ... or a batch ...
+  bflbm_ring* ring = nullptr;      // ... or a ring of more than one slab; all null once the owner is gone (detached)
   int device = 0;
   int nrep = 1;
   int every = 0;                   // a sample after every `every`-th step through the owner; 0: stepping never serves it
@@ -34,20 +37,22 @@ struct bflbm_sample_store : bflbm_recorder {
 
 namespace {
 
-inline bool recorder_attached(const bflbm_recorder* r) { return r->ctx || r->batch; }
-inline hipStream_t recorder_stream(const bflbm_recorder* r) { return r->ctx ? r->ctx->stream : r->batch->stream; }
-inline bool recorder_owner_open(const bflbm_recorder* r) { return r->ctx && r->ctx->step_open(); }
-inline std::vector<bflbm_recorder*>& recorder_list(bflbm_recorder* r) { return r->ctx ? r->ctx->recorders : r->batch->recorders; }
+inline bool recorder_attached(const bflbm_recorder* r) { return r->ctx || r->batch || r->ring; }
+// the stream that writes the records: a ring's is slab 0's
+inline hipStream_t recorder_stream(const bflbm_recorder* r) { return r->ctx ? r->ctx->stream : (r->batch ? r->batch->stream : r->ring->ctx[0]->stream); }
+inline bool ring_step_open(const bflbm_ring* g) { for (const bflbm_ctx* c : g->ctx) if (c->step_open()) return true; return false; }
+inline bool recorder_owner_open(const bflbm_recorder* r) { return (r->ctx && r->ctx->step_open()) || (r->ring && ring_step_open(r->ring)); }
+inline std::vector<bflbm_recorder*>& recorder_list(bflbm_recorder* r) { return r->ctx ? r->ctx->recorders : (r->batch ? r->batch->recorders : r->ring->recorders); }
 
 // samples that `nsteps` more steps through the owner add
 inline long long recorder_due(const bflbm_recorder* r, long long nsteps) { return r->every ? (r->since + nsteps) / r->every - r->since / r->every : 0; }
 inline bool recorder_overflows(const bflbm_recorder* r, long long nsteps) { return recorder_due(r, nsteps) > r->capacity - r->n; }
 
 // the link to the owner; the owner's list takes the recorder once nothing can fail any more
-void recorder_bind(bflbm_recorder* r, bflbm_ctx* c, bflbm_batch* b, int every) {
-  r->ctx = c; r->batch = b; r->every = every;
-  r->device = c ? c->dom.device : b->device;
-  r->nrep = c ? 1 : (int)b->ctx.size();
+void recorder_bind(bflbm_recorder* r, bflbm_ctx* c, bflbm_batch* b, int every, bflbm_ring* g = nullptr) {
+  r->ctx = c; r->batch = b; r->ring = g; r->every = every;
+  r->device = c ? c->dom.device : (b ? b->device : g->ctx[0]->dom.device);
+  r->nrep = b ? (int)b->ctx.size() : 1;
 }
 
 int recorder_after_step(bflbm_recorder* r) {
@@ -58,14 +63,18 @@ int recorder_after_step(bflbm_recorder* r) {
 // the owner goes away (or the recorder does): what was enqueued completes, what was recorded stays readable
 void recorder_detach(bflbm_recorder* r) {
   if (!recorder_attached(r)) return;
-  hipSetDevice(r->device);
-  (void)hipStreamSynchronize(recorder_stream(r));
+  if (r->ring) {                                       // a sample runs on every slab's stream
+    for (const bflbm_ctx* c : r->ring->ctx) { hipSetDevice(c->dom.device); (void)hipStreamSynchronize(c->stream); }
+  } else {
+    hipSetDevice(r->device);
+    (void)hipStreamSynchronize(recorder_stream(r));
+  }
   std::vector<bflbm_recorder*>& list = recorder_list(r);
   list.erase(std::remove(list.begin(), list.end(), r), list.end());
-  r->ctx = nullptr; r->batch = nullptr;
+  r->ctx = nullptr; r->batch = nullptr; r->ring = nullptr;
 }
 
-// ---- the owner's side: a bflbm_ctx or a bflbm_batch with its `recorders` in creation order -------------------------------
+// ---- the owner's side: a bflbm_ctx, a bflbm_batch or a bflbm_ring with its `recorders` in creation order -------------------------------
 template <class Owner> void recorders_detach_all(Owner* o) { while (!o->recorders.empty()) recorder_detach(o->recorders.back()); }
 
 // a call of `nsteps` steps is refused before any launch when some recorder's samples would not fit
@@ -98,9 +107,9 @@ int store_refuse_owner(const bflbm_ctx* c, const char* call, const char* batch_c
 // allocate [capacity][per] and the stage buffer and attach the store to its owner; `shape`: what besides the replicas
 // multiplies the capacity, for the message.  On failure the store owns nothing.
 int store_attach(bflbm_sample_store* s, bflbm_ctx* c, bflbm_batch* b, const char* call, int every, long long capacity,
-                 size_t per, size_t stage_doubles, const char* shape) {
-  if (c && c->step_open()) return fail("%s inside an open step", call);
-  recorder_bind(s, c, b, every);
+                 size_t per, size_t stage_doubles, const char* shape, bflbm_ring* g = nullptr) {
+  if ((c && c->step_open()) || (g && ring_step_open(g))) return fail("%s inside an open step", call);
+  recorder_bind(s, c, b, every, g);
   if ((unsigned long long)capacity > ((1ULL << 40) / sizeof(double)) / per)
     return fail("%s: capacity %lld x %d replicas%s exceeds 1 TB of records", call, capacity, s->nrep, shape);
   HIP_TRY(hipSetDevice(s->device));
@@ -127,7 +136,7 @@ int store_begin(const bflbm_sample_store* s) {
 inline double* store_slot(const bflbm_sample_store* s) { return s->d_rec + (size_t)s->n * s->per; }
 void store_recorded(bflbm_sample_store* s) {
   if (s->batch) for (const bflbm_ctx* c : s->batch->ctx) s->steps.push_back(c->steps);
-  else s->steps.push_back(s->ctx->steps);
+  else s->steps.push_back(s->ctx ? s->ctx->steps : s->ring->ctx[0]->steps);
   s->n += 1;
 }
 

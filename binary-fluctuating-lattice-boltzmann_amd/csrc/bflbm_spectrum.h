@@ -12,6 +12,8 @@
 //   k_spectrum_finish               stage 2: per bin, pair and replica the chunk sums in chunk order, into the slot.
 // The list holds the half-spectrum indices sorted by (bin, index), 4 B each; a chunk never crosses a bin, so a record
 // depends on the spectra and the chunk table alone.  No atomics, no LDS beyond the tree, no scratch.
+// A ring of z-slabs takes its samples by a slab FFT with one sorted list per slab (spectrum_tables::build_slab here, the
+// rest in bflbm_spectrum_ring.h); the handle, the per-handle calls and the two binning kernels are the ones below.
 // The lifecycle and the sample store are those of bflbm_recorder.h.  Included by bflbm.hip after bflbm_batch_sf.h (needs
 // bflbm_ctx, bflbm_batch, block_sum, FftApi, SfPairs, ObsSel, batch_observe_launch, observe_launch).
 #ifndef BFLBM_SPECTRUM_H_
@@ -65,10 +67,14 @@ inline int shell_of(uint64_t K2, uint64_t W) {
   return (int)s;
 }
 
-// kind 0 shells (L from shell_lcm, not 0), 1 / 2 / 3 |kx| / |ky| / |kz|; nk = (nx/2+1) ny nz <= 2^32
-inline void build(int nx, int ny, int nz, int kind, int zero_avg, uint64_t L, int chunk_len, Tables& T) {
-  const int nxc = nx / 2 + 1;
-  const long long nk = (long long)nxc * ny * nz;
+// kind 0 shells (L from shell_lcm, not 0), 1 / 2 / 3 |kx| / |ky| / |kz|; nk = (nx/2+1) ny nz <= 2^32.
+// The slab form: the rows ky in [ky0, ky1) of the half spectrum only, as the slab of a ring holds them after its z
+// transform.  The list then holds LOCAL indices (mz * nky + (my - ky0)) * (nx/2+1) + mx, nky = ky1 - ky0, sorted by
+// (bin, local index); the bins are those of the whole box (nbins too), count and q cover the slab's own rows, and k = 0
+// is left out on the slab that holds ky = 0.  build() is the slab form over all rows.
+inline void build_slab(int nx, int ny, int nz, int ky0, int ky1, int kind, int zero_avg, uint64_t L, int chunk_len, Tables& T) {
+  const int nxc = nx / 2 + 1, nky = ky1 - ky0;
+  const long long nk = (long long)nxc * nky * nz;
   const uint64_t W = kind == 0 ? L / (uint64_t)std::max(nx, std::max(ny, nz)) : 1;
   const uint64_t ux = kind == 0 ? L / nx : 0, uy = kind == 0 ? L / ny : 0, uz = kind == 0 ? L / nz : 0;
   // |k| per index and, for the shells, the terms of K2 per axis
@@ -77,18 +83,17 @@ inline void build(int nx, int ny, int nz, int kind, int zero_avg, uint64_t L, in
   for (int m = 0; m < ny; ++m) { const uint64_t k = (uint64_t)std::min(m, ny - m); ty[m] = kind == 0 ? (k * uy) * (k * uy) : k; }
   for (int m = 0; m < nz; ++m) { const uint64_t k = (uint64_t)std::min(m, nz - m); tz[m] = kind == 0 ? (k * uz) * (k * uz) : k; }
   std::vector<int> bin((size_t)nk);
-  int top = 0;
   for (int mz = 0; mz < nz; ++mz)
-    for (int my = 0; my < ny; ++my) {
-      int* row = bin.data() + ((size_t)mz * ny + my) * nxc;
-      for (int mx = 0; mx < nxc; ++mx) {
-        const int s = kind == 0 ? shell_of(tx[mx] + ty[my] + tz[mz], W) : (int)(kind == 1 ? tx[mx] : (kind == 2 ? ty[my] : tz[mz]));
-        row[mx] = s;
-        top = std::max(top, s);
-      }
+    for (int my = ky0; my < ky1; ++my) {
+      int* row = bin.data() + ((size_t)mz * nky + (my - ky0)) * nxc;
+      for (int mx = 0; mx < nxc; ++mx)
+        row[mx] = kind == 0 ? shell_of(tx[mx] + ty[my] + tz[mz], W) : (int)(kind == 1 ? tx[mx] : (kind == 2 ? ty[my] : tz[mz]));
     }
+  // the top bin of the whole box: every term is largest at its Nyquist index, and the bin does not decrease with a term
+  const uint64_t mtx = tx[nxc - 1], mty = ty[ny / 2], mtz = tz[nz / 2];
+  const int top = kind == 0 ? shell_of(mtx + mty + mtz, W) : (int)(kind == 1 ? mtx : (kind == 2 ? mty : mtz));
   T.nbins = top + 1;
-  if (zero_avg) bin[0] = -1;                               // k = 0: neither summed nor counted
+  if (zero_avg && ky0 == 0) bin[0] = -1;                   // k = 0: neither summed nor counted
   // a counting sort keeps the index order inside a bin
   std::vector<long long> first((size_t)T.nbins + 1, 0);
   for (long long i = 0; i < nk; ++i) if (bin[(size_t)i] >= 0) first[(size_t)bin[(size_t)i] + 1] += 1;
@@ -100,9 +105,9 @@ inline void build(int nx, int ny, int nz, int kind, int zero_avg, uint64_t L, in
   {
     std::vector<long long> at(first.begin(), first.end() - 1);
     for (int mz = 0; mz < nz; ++mz)
-      for (int my = 0; my < ny; ++my)
+      for (int my = ky0; my < ky1; ++my)
         for (int mx = 0; mx < nxc; ++mx) {
-          const long long i = ((long long)mz * ny + my) * nxc + mx;
+          const long long i = ((long long)mz * nky + (my - ky0)) * nxc + mx;
           const int s = bin[(size_t)i];
           if (s < 0) continue;
           T.list[(size_t)at[(size_t)s]++] = (uint32_t)i;
@@ -131,9 +136,33 @@ inline void build(int nx, int ny, int nz, int kind, int zero_avg, uint64_t L, in
   T.bin_first[(size_t)T.nbins] = (int)T.chunks.size();
 }
 
+inline void build(int nx, int ny, int nz, int kind, int zero_avg, uint64_t L, int chunk_len, Tables& T) {
+  build_slab(nx, ny, nz, 0, ny, kind, zero_avg, L, chunk_len, T);
+}
+
 }  // namespace spectrum_tables
 
 #ifndef BFLBM_SPECTRUM_TABLES_ONLY
+
+// a ring's trace (bflbm_spectrum_ring.h): what slab d holds on its own device.  Slab d owns the rows ky in [ky0, ky1).
+struct SpectrumSrc { const double2* h2; int z0, nzl; };   // a source slab of the transpose, as k_spectrum_collect reads it
+struct SpectrumSlab {
+  int device = 0, ky0 = 0, ky1 = 0;
+  long long nk = 0, nchunks = 0;    // nz nky nxc; chunks of the slab's own sorted list
+  hipfftHandle plan2d = nullptr, plan1d = nullptr;
+  double2* h2 = nullptr;            // [var][nzl][ny][nxc]: the 2-D transforms of the own planes; the other slabs read it
+  double2* zb = nullptr;            // [var][nz][nky][nxc]: the own rows of every plane, transformed along z in place
+  uint32_t* d_list = nullptr;       // the slab's tables (spectrum_tables::build_slab)
+  spectrum_tables::Chunk* d_chunks = nullptr;
+  int* d_bin_first = nullptr;
+  double* partial = nullptr;        // [pair][chunk]
+  double* sum = nullptr;            // [pair][bin]; slab 0 has none: it writes block 0 of the handle's d_stage
+  SpectrumSrc* d_src = nullptr;     // [nslabs], in slab order
+  bool reachable = false;           // every source is on this device or peer-mapped: k_spectrum_collect may read it in place
+  hipEvent_t planes = nullptr;      // h2 is complete (recorded on the slab's stream) ...
+  hipEvent_t collected = nullptr;   // ... and this slab has taken its rows of every other slab's h2
+  hipEvent_t summed = nullptr;      // sum is complete
+};
 
 struct bflbm_spectrum : bflbm_sample_store {  // d_rec [capacity][nrep][npairs][nbins], d_stage [nrep][npairs][nchunks]
   int nx = 0, ny = 0, nz = 0;
@@ -155,12 +184,26 @@ struct bflbm_spectrum : bflbm_sample_store {  // d_rec [capacity][nrep][npairs][
   spectrum_tables::Chunk* d_chunks = nullptr;
   int* d_bin_first = nullptr;       // [nbins + 1]
   hipfftHandle plan = nullptr;
+  // a ring: d_stage is [nslabs][npairs][nbins] on slab 0's device, nchunks the slabs' total, max_chunks_per_bin the most
+  // of any (slab, bin); the members from `fields` to `plan` stay empty
+  std::vector<SpectrumSlab> slab;
+  hipEvent_t combined = nullptr;    // slab 0 has taken every slab's sums
   bflbm_spectrum() : bflbm_sample_store("spectrum trace", "bflbm_spectrum") {}
   ~bflbm_spectrum() override {
     if (plan) g_fft.destroy(plan);
     for (void* p : {(void*)fields, (void*)hat, (void*)d_list, (void*)d_chunks, (void*)d_bin_first}) if (p) hipFree(p);
+    for (SpectrumSlab& q : slab) {
+      hipSetDevice(q.device);
+      if (q.plan2d) g_fft.destroy(q.plan2d);
+      if (q.plan1d) g_fft.destroy(q.plan1d);
+      for (void* p : {(void*)q.h2, (void*)q.zb, (void*)q.d_list, (void*)q.d_chunks, (void*)q.d_bin_first, (void*)q.partial, (void*)q.sum, (void*)q.d_src})
+        if (p) hipFree(p);
+      for (hipEvent_t e : {q.planes, q.collected, q.summed}) if (e) hipEventDestroy(e);
+    }
+    if (combined) { hipSetDevice(device); hipEventDestroy(combined); }
   }
   int record() override;
+  int record_ring();                // bflbm_spectrum_ring.h
 };
 
 namespace {
@@ -203,9 +246,9 @@ __global__ void __launch_bounds__(256) k_spectrum_finish(const double* __restric
   out[row * nbins + bin] = acc;
 }
 
-int spectrum_create(bflbm_ctx* c, bflbm_batch* b, int npairs, const int* var_a, const int* var_b, const double* scale,
-                    int lb_hydrovars, int kind, int zero_avg, int every, long long capacity, bflbm_spectrum** out) {
-  const char* call = b ? "bflbm_batch_spectrum_create" : "bflbm_spectrum_create";
+// what every creation call refuses about its own arguments ...
+int spectrum_refuse_args(const char* call, int npairs, const int* var_a, const int* var_b, int lb_hydrovars, int kind,
+                         int every, long long capacity) {
   if (npairs < 1 || npairs > 32) return fail("%s: 1..32 pairs (got %d)", call, npairs);
   const int most = lb_hydrovars ? BFLBM_NHYDROBAR : BFLBM_NHYDRO;
   for (int p = 0; p < npairs; ++p)
@@ -213,22 +256,24 @@ int spectrum_create(bflbm_ctx* c, bflbm_batch* b, int npairs, const int* var_a, 
       if (v < 0 || v >= most)
         return fail("%s: pair %d: variable index %d outside %s (0..%d)", call, p, v, lb_hydrovars ? "hydrovsbar" : "hydrovs", most - 1);
   if (kind < 0 || kind > 3) return fail("%s: kind must be 0 (shells), 1, 2 or 3 (axis x, y, z) (got %d)", call, kind);
-  if (store_refuse_cadence(call, every, capacity) || store_refuse_owner(c, call, "bflbm_batch_spectrum_create", "spectrum trace")) return 1;
-  if (c && c->step_open()) return fail("%s inside an open step", call);
-  const Geo& G = c ? c->G : b->G;
+  return store_refuse_cadence(call, every, capacity);
+}
+// ... and about the owner's box; *L: the lcm of the shells (1 for an axis)
+int spectrum_refuse_box(const char* call, int kind, const Geo& G, uint64_t* L) {
   const int nx = G.nx, ny = G.ny, nz = G.nz;
   const long long nk = (long long)(nx / 2 + 1) * ny * nz;
   if (nk > (1LL << 32)) return fail("%s: the half spectrum of %d x %d x %d has %lld points, more than the 2^32 the index list holds", call, nx, ny, nz, nk);
-  const uint64_t L = kind == 0 ? spectrum_tables::shell_lcm(nx, ny, nz) : 1;
-  if (!L) return fail("%s: lcm(%d, %d, %d) is too large for shells: 12 (L/2)^2 must fit in 63 bits", call, nx, ny, nz);
-  if (load_fft()) return 1;
-  HIP_TRY(hipSetDevice(c ? c->dom.device : b->device));
+  *L = kind == 0 ? spectrum_tables::shell_lcm(nx, ny, nz) : 1;
+  if (!*L) return fail("%s: lcm(%d, %d, %d) is too large for shells: 12 (L/2)^2 must fit in 63 bits", call, nx, ny, nz);
+  return 0;
+}
 
-  std::unique_ptr<bflbm_spectrum> t(new bflbm_spectrum());
-  const int nrep = c ? 1 : (int)b->ctx.size();
-  t->nx = nx; t->ny = ny; t->nz = nz; t->nk = nk; t->nsites = (long long)nx * ny * nz;
+// the box, the kind and where a pair's spectra lie
+void spectrum_select(bflbm_spectrum* t, const Geo& G, int npairs, const int* var_a, const int* var_b, const double* scale,
+                     int lb_hydrovars, int kind, int zero_avg) {
+  t->nx = G.nx; t->ny = G.ny; t->nz = G.nz; t->nk = (long long)(G.nx / 2 + 1) * G.ny * G.nz; t->nsites = (long long)G.nx * G.ny * G.nz;
   t->kind = kind; t->zero_avg = zero_avg ? 1 : 0; t->lb = lb_hydrovars ? 1 : 0;
-  // where a pair's spectra lie: the slots of the batch observation, or the rank among the distinct variables
+  // the slots of the batch observation, or the rank among the distinct variables
   t->sel.mask = 0; t->sel.nsel = 0;
   for (int p = 0; p < npairs; ++p) { t->sel.mask |= 1u << var_a[p]; t->sel.mask |= 1u << var_b[p]; }
   for (int v = 0; v < BFLBM_NHYDRO_; ++v) {
@@ -243,6 +288,25 @@ int spectrum_create(bflbm_ctx* c, bflbm_batch* b, int npairs, const int* var_a, 
     t->pairs.b[p] = p < npairs ? t->sel.slot[var_b[p]] : 0;
     t->pairs.scale[p] = (p < npairs && scale) ? scale[p] : 1.0;
   }
+}
+
+int spectrum_create(bflbm_ctx* c, bflbm_batch* b, int npairs, const int* var_a, const int* var_b, const double* scale,
+                    int lb_hydrovars, int kind, int zero_avg, int every, long long capacity, bflbm_spectrum** out) {
+  const char* call = b ? "bflbm_batch_spectrum_create" : "bflbm_spectrum_create";
+  const Geo& G = c ? c->G : b->G;
+  uint64_t L = 0;
+  if (spectrum_refuse_args(call, npairs, var_a, var_b, lb_hydrovars, kind, every, capacity)) return 1;
+  if (store_refuse_owner(c, call, "bflbm_batch_spectrum_create", "spectrum trace")) return 1;
+  if (c && c->step_open()) return fail("%s inside an open step", call);
+  if (spectrum_refuse_box(call, kind, G, &L)) return 1;
+  const int nx = G.nx, ny = G.ny, nz = G.nz;
+  const long long nk = (long long)(nx / 2 + 1) * ny * nz;
+  if (load_fft()) return 1;
+  HIP_TRY(hipSetDevice(c ? c->dom.device : b->device));
+
+  std::unique_ptr<bflbm_spectrum> t(new bflbm_spectrum());
+  const int nrep = c ? 1 : (int)b->ctx.size();
+  spectrum_select(t.get(), G, npairs, var_a, var_b, scale, lb_hydrovars, kind, zero_avg);
   spectrum_tables::Tables T;
   spectrum_tables::build(nx, ny, nz, kind, t->zero_avg, L, spectrum_tables::kChunkLen, T);
   t->nbins = T.nbins; t->nchunks = (long long)T.chunks.size(); t->max_chunks_per_bin = T.max_chunks_per_bin;
@@ -288,6 +352,7 @@ int spectrum_create(bflbm_ctx* c, bflbm_batch* b, int npairs, const int* var_a, 
 
 // enqueue the observation, the transforms and the two binning stages of the resident state into slot n; no host synchronisation
 int bflbm_spectrum::record() {
+  if (ring) return record_ring();
   if (store_begin(this)) return 1;
   const hipStream_t stream = recorder_stream(this);
   g_fft.set_stream(plan, stream);                      // the owner's stream may have been replaced since the last sample

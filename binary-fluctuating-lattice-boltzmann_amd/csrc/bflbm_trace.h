@@ -6,15 +6,35 @@
 // strided sum and tree of k_sum_partials per plane, the planes in sequence), so a record equals bflbm_droplet_moments
 // of the same state bit for bit and does not depend on how the lattice is run.
 // The lifecycle and the sample store are those of bflbm_recorder.h; here are the kernels, their launch and the checks of
-// the kind's own arguments.  Included by bflbm.hip after bflbm_droplet.h (needs bflbm_ctx, bflbm_batch, block_sum).
+// the kind's own arguments.
+// A ring of z-slabs: stage 1 runs on every slab's own stream over the slab's own planes (z the global plane index, the
+// halo planes pulled through as the slab's density pass does) into [nzl][plane blocks][kNTrace] on the slab's device;
+// slab 0 writes its planes straight into the stage buffer [nz][plane blocks][kNTrace] and takes every other slab's block
+// with one contiguous (peer) copy after that slab's event, in global plane order; the same k_trace_finish then runs on
+// slab 0.  The summation order is a lone context's, so with the bit-exact schedules the record equals the lone trace's
+// bit for bit.  The next sample's stage 1 of a slab waits for the event that slab 0 has taken the last one's block.
+// Included by bflbm.hip after bflbm_droplet.h (needs bflbm_ctx, bflbm_batch, bflbm_ring, block_sum).
 #ifndef BFLBM_TRACE_H_
 #define BFLBM_TRACE_H_
 
 struct bflbm_trace : bflbm_sample_store {  // d_rec [capacity][nrep][kNTrace], d_stage [nrep][nz][plane blocks][kNTrace]
   Geo G;
   double threshold = 0.;
+  // a ring: what slab k > 0 holds on its device (slab 0 writes d_stage itself; part[0] stays empty)
+  struct Part { int device = 0; double* partial = nullptr; hipEvent_t done = nullptr; };   // [nzl][plane blocks][kNTrace]; stage 1 is complete
+  std::vector<Part> part;
+  hipEvent_t taken = nullptr;      // slab 0 has copied every slab's block
   bflbm_trace() : bflbm_sample_store("trace", "bflbm_trace") {}
+  ~bflbm_trace() override {
+    for (Part& q : part) {
+      hipSetDevice(q.device);
+      if (q.partial) hipFree(q.partial);
+      if (q.done) hipEventDestroy(q.done);
+    }
+    if (taken) { hipSetDevice(device); hipEventDestroy(taken); }
+  }
   int record() override;
+  int record_ring();
 };
 
 namespace {
@@ -26,7 +46,7 @@ constexpr int kNTrace = BFLBM_TRACE_NREC;
 // not touched.  `partial` is the lattice's own [nz][plane blocks][kNTrace].
 __device__ __forceinline__ void trace_moments_body(const double* __restrict__ S, double* __restrict__ partial, const Geo& G, double threshold) {
   const long long s_ = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int p = (int)blockIdx.y;                       // single slab: storage plane == global z (H = 0)
+  const int p = G.H + (int)blockIdx.y;                 // the own planes; a single slab: storage plane == global z (H = 0, z0 = 0)
   double v[kNTrace];
   for (int k = 0; k < kNTrace; ++k) v[k] = 0.;
   const int y = (int)(s_ / G.pitch);
@@ -36,7 +56,7 @@ __device__ __forceinline__ void trace_moments_body(const double* __restrict__ S,
     const double r = pull_density(S, G, I);
     v[10] = r;
     if (threshold == -INFINITY || r > threshold) {     // -inf: every cell, whatever its density is
-      const int z = p;
+      const int z = G.z0 + (int)blockIdx.y;
       const double m[10] = { 1., (double)x, (double)y, (double)z, (double)x * x, (double)x * y, (double)x * z,
                              (double)y * y, (double)y * z, (double)z * z };
       for (int k = 0; k < 10; ++k) v[k] = r * m[k];
@@ -46,7 +66,7 @@ __device__ __forceinline__ void trace_moments_body(const double* __restrict__ S,
   block_sum<kNTrace>(v, partial);
 }
 
-// grid (plane blocks, nz, 1): a lone context hands over its resident buffer
+// grid (plane blocks, own planes, 1): a lone context, or a slab of a ring, hands over its resident buffer
 __global__ void __launch_bounds__(256) k_trace_moments(const double* __restrict__ S, double* __restrict__ partial, Geo G, double threshold) {
   trace_moments_body(S, partial, G, threshold);
 }
@@ -83,18 +103,32 @@ __global__ void __launch_bounds__(256) k_trace_finish(const double* __restrict__
   if (threadIdx.x == 0) for (int k = 0; k < kNTrace; ++k) out[(long long)blockIdx.x * kNTrace + k] = acc[k];
 }
 
-int trace_create(bflbm_ctx* c, bflbm_batch* b, int every, long long capacity, double threshold, bflbm_trace** out) {
-  const char* call = b ? "bflbm_batch_trace_create" : "bflbm_trace_create";
+int trace_create(bflbm_ctx* c, bflbm_batch* b, bflbm_ring* g, int every, long long capacity, double threshold, bflbm_trace** out) {
+  const char* call = g ? "bflbm_ring_trace_create" : (b ? "bflbm_batch_trace_create" : "bflbm_trace_create");
   if (store_refuse_cadence(call, every, capacity)) return 1;
   if (threshold != threshold) return fail("%s: the threshold is NaN (-INFINITY takes every cell)", call);
   if (store_refuse_owner(c, call, "bflbm_batch_trace_create", "trace")) return 1;
-  for (const bflbm_recorder* r : c ? c->recorders : b->recorders)
+  for (const bflbm_recorder* r : c ? c->recorders : (b ? b->recorders : g->recorders))
     if (dynamic_cast<const bflbm_trace*>(r)) return fail("%s: the owner already has a trace", call);
   std::unique_ptr<bflbm_trace> t(new bflbm_trace());
-  t->G = c ? c->G : b->G; t->threshold = threshold;
-  const size_t per = (size_t)(c ? 1 : b->ctx.size()) * kNTrace;
-  const size_t nblocks = (size_t)((t->G.plane + 255) / 256) * (size_t)t->G.nz;
-  if (store_attach(t.get(), c, b, call, every, capacity, per, nblocks * per, "")) return 1;
+  t->G = c ? c->G : (b ? b->G : g->ctx[0]->G); t->threshold = threshold;
+  const size_t per = (size_t)(b ? b->ctx.size() : 1) * kNTrace;
+  const size_t nbx = (size_t)((t->G.plane + 255) / 256), nblocks = nbx * (size_t)t->G.nz;
+  if (g) {
+    if (ring_step_open(g)) return fail("%s inside an open step", call);
+    t->device = g->ctx[0]->dom.device;                   // the destructor's, should a step below fail
+    t->part.resize(g->ctx.size());
+    for (size_t k = 1; k < g->ctx.size(); ++k) {
+      bflbm_trace::Part& q = t->part[k];
+      q.device = g->ctx[k]->dom.device;
+      HIP_TRY(hipSetDevice(q.device));
+      HIP_TRY(hipMalloc((void**)&q.partial, (size_t)g->ctx[k]->nzl * nbx * kNTrace * sizeof(double)));
+      HIP_TRY(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
+    }
+    HIP_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipEventCreateWithFlags(&t->taken, hipEventDisableTiming));
+  }
+  if (store_attach(t.get(), c, b, call, every, capacity, per, nblocks * per, "", g)) return 1;
   *out = t.release();
   return 0;
 }
@@ -103,6 +137,7 @@ int trace_create(bflbm_ctx* c, bflbm_batch* b, int every, long long capacity, do
 
 // enqueue the reduction of the resident state into slot n; no host synchronisation
 int bflbm_trace::record() {
+  if (ring) return record_ring();
   if (store_begin(this)) return 1;
   const dim3 grid((unsigned)((G.plane + 255) / 256), (unsigned)G.nz, (unsigned)nrep);
   const hipStream_t stream = recorder_stream(this);
@@ -119,15 +154,49 @@ int bflbm_trace::record() {
   return 0;
 }
 
+int bflbm_trace::record_ring() {
+  if (store_begin(this)) return 1;
+  const int n = (int)ring->ctx.size();
+  const unsigned nbx = (unsigned)((G.plane + 255) / 256);
+  const size_t per_plane = (size_t)nbx * kNTrace;
+  for (int k = 0; k < n; ++k) {
+    bflbm_ctx* c = ring->ctx[k];
+    HIP_TRY(hipSetDevice(c->dom.device));
+    if (k > 0) HIP_TRY(hipStreamWaitEvent(c->stream, taken, 0));       // slab 0 may still be copying the last sample's block
+    hipLaunchKernelGGL(k_trace_moments, dim3(nbx, (unsigned)c->nzl, 1), dim3(256), 0, c->stream,
+                       c->S[c->cur], k > 0 ? part[k].partial : d_stage, c->G, threshold);
+    HIP_TRY(hipGetLastError());
+    if (k > 0) HIP_TRY(hipEventRecord(part[k].done, c->stream));
+  }
+  HIP_TRY(hipSetDevice(device));
+  const hipStream_t s0 = ring->ctx[0]->stream;
+  for (int k = 1; k < n; ++k) {
+    const bflbm_ctx* c = ring->ctx[k];
+    HIP_TRY(hipStreamWaitEvent(s0, part[k].done, 0));
+    HIP_TRY(hipMemcpyPeerAsync(d_stage + (size_t)c->dom.z0 * per_plane, device, part[k].partial, part[k].device,
+                               (size_t)c->nzl * per_plane * sizeof(double), s0));
+  }
+  HIP_TRY(hipEventRecord(taken, s0));
+  hipLaunchKernelGGL(k_trace_finish, dim3(1), dim3(256), 0, s0, d_stage, store_slot(this), (int)nbx, G.nz);
+  HIP_TRY(hipGetLastError());
+  store_recorded(this);
+  return 0;
+}
+
 extern "C" {
 
 int bflbm_trace_create(bflbm_ctx* c, int every, long long capacity, double threshold, bflbm_trace** out) {
   if (!c || !out) return fail("bflbm_trace_create: null argument");
-  return trace_create(c, nullptr, every, capacity, threshold, out);
+  return trace_create(c, nullptr, nullptr, every, capacity, threshold, out);
 }
 int bflbm_batch_trace_create(bflbm_batch* b, int every, long long capacity, double threshold, bflbm_trace** out) {
   if (!b || !out) return fail("bflbm_batch_trace_create: null argument");
-  return trace_create(nullptr, b, every, capacity, threshold, out);
+  return trace_create(nullptr, b, nullptr, every, capacity, threshold, out);
+}
+int bflbm_ring_trace_create(bflbm_ring* r, int every, long long capacity, double threshold, bflbm_trace** out) {
+  if (!r || !out) return fail("bflbm_ring_trace_create: null argument");
+  if (r->ctx.size() == 1) return bflbm_trace_create(r->ctx[0], every, capacity, threshold, out);   // the whole box: the lone trace of ctx[0]
+  return trace_create(nullptr, nullptr, r, every, capacity, threshold, out);
 }
 
 int bflbm_trace_destroy(bflbm_trace* t) { return store_destroy(t); }

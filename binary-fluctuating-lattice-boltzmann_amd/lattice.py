@@ -163,7 +163,7 @@ class _Recorder:
 
 class Trace(_Recorder):
     """Droplet moments of every replica recorded on the device every `every` steps through the owner (a lone
-    single-slab BinaryLBM or a BatchLBM) and read once: include/bflbm.h, "Ensemble traces".  Made by owner.trace()."""
+    single-slab BinaryLBM, a BatchLBM or a RingLBM) and read once: include/bflbm.h, "Ensemble traces".  Made by owner.trace()."""
     _abi = "bflbm_trace"
 
     def __init__(self, owner, create, every, capacity, threshold):
@@ -226,8 +226,8 @@ class InterfaceTrace(_Recorder):
 
 class SpectrumTrace(_Recorder):
     """The structure factor of chosen pairs of hydrodynamic variables of every sample, binned into shells in |q| or into
-    |k| along one axis, recorded on the device every `every` steps through the owner (a lone single-slab BinaryLBM or a
-    BatchLBM) and read once: include/bflbm.h, "Spectrum traces".  Made by owner.spectrum_trace(); an owner may carry
+    |k| along one axis, recorded on the device every `every` steps through the owner (a lone single-slab BinaryLBM, a
+    BatchLBM or a RingLBM) and read once: include/bflbm.h, "Spectrum traces".  Made by owner.spectrum_trace(); an owner may carry
     several.  Closing the owner detaches the trace: it stays readable until its own close()."""
     _abi = "bflbm_spectrum"
 
@@ -651,8 +651,8 @@ class RingLBM(_DropletMixin):
 
     def close(self):
         if getattr(self, "_h", None):
-            for d in list(getattr(self, "_dependents", [])):      # ring-level accumulators (structure factors)
-                d.close()
+            for d in list(getattr(self, "_dependents", [])):      # ring-level accumulators and the moments trace: closed;
+                getattr(d, "_owner_closing", d.close)()           # a spectrum trace: detached by the library, still readable
             for s in self.slabs:
                 for d in list(getattr(s, "_dependents", [])):
                     d.close()
@@ -694,6 +694,17 @@ class RingLBM(_DropletMixin):
 
     def LBM_timestep(self, nsteps=1):
         check(self.lib.bflbm_ring_step(self._h, int(nsteps)))
+
+    # -- recorders: served by LBM_timestep, not by stepping the slabs by hand -----------------
+    def trace(self, every, capacity, threshold=None):
+        """Record the droplet moments of the cells with rho > threshold (None: every cell) after every `every`-th step:
+        Trace, one replica, the record a lone lattice's bit for bit.  At most one per ring."""
+        return Trace(self, "bflbm_ring_trace_create", every, capacity, threshold)
+
+    def spectrum_trace(self, var_names_or_pairs, kind="shell", every=1, capacity=64, lb_hydrovars=False, zero_avg=True, var_scaling=None):
+        """Record, after every `every`-th step, the binned structure factor of pairs of hydrovs (lb_hydrovars: hydrovsbar)
+        variables by a slab FFT over the ring: SpectrumTrace, with the arguments of BinaryLBM.spectrum_trace."""
+        return SpectrumTrace(self, "bflbm_ring_spectrum_create", var_names_or_pairs, kind, every, capacity, lb_hydrovars, zero_avg, var_scaling)
 
     def _gather(self, ncomp, call):
         out = np.empty((ncomp, self.n[2], self.n[1], self.n[0]))

@@ -199,7 +199,11 @@ int bflbm_halo_planes(bflbm_ctx* c, int kind, int side, int pack, void** planes,
  * planes.  nslabs == 1 is the plain single-GPU case.  Per-slab work (upload, download, observables,
  * noise injection) goes through the slab's context from bflbm_ring_slab(); every bflbm_get_* /
  * bflbm_upload_fg / bflbm_download_fg call only touches the cells of the given box that lie in that slab,
- * so a driver simply loops over the slabs.  This is what include/bflbm_amrex.H drives. */
+ * so a driver simply loops over the slabs.  This is what include/bflbm_amrex.H drives.
+ * A ring of more than one slab may own recorders (bflbm_ring_trace_create, bflbm_ring_spectrum_create below):
+ * bflbm_ring_step refuses a call whose samples would not fit before any launch and serves the recorders once per step,
+ * after the bflbm_step_finish of every slab.  Stepping the slabs by hand through bflbm_ring_slab() serves nothing.
+ * bflbm_ring_destroy detaches the ring's recorders first; they stay readable. */
 typedef struct bflbm_ring bflbm_ring;
 int bflbm_ring_create(const bflbm_params* p, const int n[3], int nslabs, const int* devices, int ndevices, bflbm_ring** out);
 int bflbm_ring_destroy(bflbm_ring* r);
@@ -313,11 +317,21 @@ int bflbm_fused_plan_query(const int n[3], int nreplicas, int noise, int compute
  *    open step.  An open step also refuses bflbm_trace_sample, _reset and _read.
  *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_trace_read, _count and
  *    _destroy still work, bflbm_trace_sample fails.
- *  - bflbm_trace_read synchronises the owner's stream; no other call of this group does. */
+ *  - bflbm_trace_read synchronises the owner's stream; no other call of this group does.
+ *  - a ring of z-slabs (bflbm_ring_trace_create; the process-per-GPU slabs have no trace): one replica, at most one trace
+ *    per ring, labelled with the ring's step counter (slab 0's), sampled by bflbm_ring_step only.  Stage 1 runs on every
+ *    slab's own stream over the slab's own planes, z the global plane index, into block sums on the slab's device; slab 0
+ *    collects them in global plane order with one contiguous (peer) copy per slab, ordered by events and without a host
+ *    synchronisation, and adds them as above on its own stream.  The summation order is therefore exactly a lone
+ *    context's: with the bit-exact schedules the record equals the lone lattice's bit for bit, and with threshold =
+ *    -INFINITY entries 0..9 equal bflbm_ring_droplet_moments[0..9].  The records live on slab 0's device and
+ *    bflbm_trace_read synchronises slab 0's stream alone.  Creation, _sample, _reset and _read are refused while any
+ *    slab has an open step.  A ring of one slab gets the lone trace of its only context. */
 typedef struct bflbm_trace bflbm_trace;
 #define BFLBM_TRACE_NREC 12
 int bflbm_trace_create(bflbm_ctx* c, int every, long long capacity, double threshold, bflbm_trace** out);
 int bflbm_batch_trace_create(bflbm_batch* b, int every, long long capacity, double threshold, bflbm_trace** out);
+int bflbm_ring_trace_create(bflbm_ring* r, int every, long long capacity, double threshold, bflbm_trace** out);
 int bflbm_trace_destroy(bflbm_trace* t);
 int bflbm_trace_sample(bflbm_trace* t);                 /* record the resident state now (e.g. frame 0) */
 int bflbm_trace_reset(bflbm_trace* t);                  /* forget the samples, restart the every-counter */
@@ -475,12 +489,30 @@ int bflbm_batch_get_hydrovsbar(bflbm_batch* b, double* dst, int ncomp);
  *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_spectrum_read, _count,
  *    _geometry, _bins and _destroy still work, bflbm_spectrum_sample fails.
  *  - creation uploads the tables with blocking copies.  After it only bflbm_spectrum_read and bflbm_spectrum_destroy
- *    synchronise the owner's stream. */
+ *    synchronise the owner's stream.
+ *  - a ring of z-slabs (bflbm_ring_spectrum_create): the same definition, bins, count, q and sample layout with one
+ *    replica, labelled with slab 0's step counter, sampled by bflbm_ring_step only; refused like the lone call, and
+ *    where ny < nslabs or any slab has an open step.  Slab d of n owns the rows ky in [ny d / n, ny (d+1) / n).  A sample
+ *    runs on the slabs' streams, ordered by events and without a host synchronisation (hydrovs under reference-state
+ *    noise excepted: the global centre of mass is summed on the host first, as in bflbm_ring_sf_accumulate): every slab
+ *    observes its planes into its scratch state buffer and transforms them in (x, y); every slab gathers its rows of
+ *    every plane of every slab (a kernel that reads the other slabs' memory in place where it is on the same device or
+ *    peer-mapped, strided copies otherwise or with BFLBM_RING_COPY_FALLBACK=1: the same doubles), transforms them along
+ *    z and bins them as above over its OWN sorted list (local index (kz nky + ky - ky0) (nx/2+1) + kx, sorted by (bin,
+ *    local index), chunks of at most 2048 entries that never cross a bin, k = 0 left out on the slab that holds ky = 0
+ *    under zero_avg); slab 0 collects the n arrays of per-slab sums and adds them per (pair, bin) in the order
+ *    0 ... n-1 into the slot.  No atomics: a record depends on the spectra, the slabs' tables and the slab count alone.
+ *    It differs from a lone lattice's record of the same state by rounding (another FFT, another order).
+ *    bflbm_spectrum_geometry reports the chunks summed over the slabs and the most chunks any (slab, bin) has.  The
+ *    records live on slab 0's device; bflbm_spectrum_read synchronises slab 0's stream alone, _destroy every slab's.
+ *    A ring of one slab gets the lone trace of its only context. */
 typedef struct bflbm_spectrum bflbm_spectrum;
 int bflbm_spectrum_create(bflbm_ctx* c, int npairs, const int* var_a, const int* var_b, const double* scale /* or NULL */,
                           int lb_hydrovars, int kind, int zero_avg, int every, long long capacity, bflbm_spectrum** out);
 int bflbm_batch_spectrum_create(bflbm_batch* b, int npairs, const int* var_a, const int* var_b, const double* scale /* or NULL */,
                                 int lb_hydrovars, int kind, int zero_avg, int every, long long capacity, bflbm_spectrum** out);
+int bflbm_ring_spectrum_create(bflbm_ring* r, int npairs, const int* var_a, const int* var_b, const double* scale /* or NULL */,
+                               int lb_hydrovars, int kind, int zero_avg, int every, long long capacity, bflbm_spectrum** out);
 int bflbm_spectrum_destroy(bflbm_spectrum* t);
 int bflbm_spectrum_sample(bflbm_spectrum* t);              /* record the resident state now (e.g. frame 0) */
 int bflbm_spectrum_reset(bflbm_spectrum* t);               /* forget the samples, restart the every-counter */
