@@ -12,6 +12,8 @@ import ctypes
 import numpy as np
 import pytest
 
+from observable_twins import same_doubles as _same
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(8, 8, 8), (24, 24, 24), (20, 28, 24), (72, 12, 10), (64, 8, 16)]
@@ -22,12 +24,6 @@ HANDOVER_SHAPE = (64, 8, 16)
 # 9 of 64, 97 of 576, 69 of 560, 69-138 of 864 and 278-286 of 512 columns cross); each test asserts it on what it compares.
 RADIUS = {(8, 8, 8): 0.25, (24, 24, 24): 0.25, (20, 28, 24): 0.25, (72, 12, 10): 0.4, (64, 8, 16): 0.4}
 FIELDS = ("rho", "phi")
-
-
-def _same(a, b):
-    """Equal doubles, NaNs matched by position."""
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(a[~np.isnan(a)], b[~np.isnan(b)])
 
 
 def _droplet(pkg, n, schedule=None, kBT=0.0, radius=None, steps=2, **params):
