@@ -129,6 +129,14 @@ SIGNATURES = {
     "bflbm_iface_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
     "bflbm_iface_geometry": (ctypes.c_int, [_vp, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int)]),
     "bflbm_iface_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp]),
+    "bflbm_shape_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, _dp, ctypes.c_double, ctypes.c_int, _dp, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_batch_shape_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, _dp, ctypes.c_double, ctypes.c_int, _dp, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_shape_destroy": (ctypes.c_int, [_vp]),
+    "bflbm_shape_sample": (ctypes.c_int, [_vp]),
+    "bflbm_shape_reset": (ctypes.c_int, [_vp]),
+    "bflbm_shape_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
+    "bflbm_shape_geometry": (ctypes.c_int, [_vp, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int)]),
+    "bflbm_shape_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp]),
     "bflbm_batch_sf_create": (ctypes.c_int, [_vp, ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), _dp, ctypes.c_int, ctypes.c_int, _P(_vp)]),
     "bflbm_batch_sf_destroy": (ctypes.c_int, [_vp]),
     "bflbm_batch_sf_reset": (ctypes.c_int, [_vp]),

@@ -128,6 +128,138 @@ def capillary_spectrum(h, axes=(-1,)):
     return (np.abs(hq) ** 2).mean(axis=0), tuple(2 * np.pi * np.fft.fftfreq(h.shape[a]) for a in axes)
 
 
+# ---- droplet shape modes: the numpy restatement of the shape trace (include/bflbm.h, "Shape traces") and its projection ----
+SHAPE_DIRECTIONS = {"falling": 0, "rising": 1}
+
+
+def ray_nodes(ntheta, nphi):
+    """Directions and weights of a product quadrature on the sphere: ntheta Gauss-Legendre nodes in cos(theta) times nphi
+    equally spaced phi = 2 pi (k + 1/2) / nphi.  Returns (dirs[ntheta * nphi, 3], weights[ntheta * nphi]), theta-major; the
+    weights sum to 4 pi, and products of spherical harmonics of total degree < min(2 ntheta, nphi) integrate exactly.
+    These are the rays of a ShapeTrace (the r(theta, phi) grid of Droplet_Fluctuation.ipynb cell 32)."""
+    ntheta, nphi = int(ntheta), int(nphi)
+    if ntheta < 1 or nphi < 1:
+        raise ValueError(f"ray_nodes: ntheta {ntheta} and nphi {nphi} must be >= 1")
+    ct, wt = np.polynomial.legendre.leggauss(ntheta)
+    st = np.sqrt(1.0 - ct * ct)
+    phi = 2.0 * np.pi * (np.arange(nphi) + 0.5) / nphi
+    dirs = np.empty((ntheta, nphi, 3))
+    dirs[..., 0] = st[:, None] * np.cos(phi)[None, :]
+    dirs[..., 1] = st[:, None] * np.sin(phi)[None, :]
+    dirs[..., 2] = ct[:, None]
+    weights = np.repeat(wt * (2.0 * np.pi / nphi), nphi)
+    return dirs.reshape(-1, 3), weights
+
+
+def _density_at(d, px, py, pz):
+    """The trilinear density of the definition at the points (px, py, pz) of a field d[nz, ny, nx]."""
+    nz, ny, nx = d.shape
+    with np.errstate(invalid="ignore"):
+        ok = (np.abs(px) < 2.0 ** 30) & (np.abs(py) < 2.0 ** 30) & (np.abs(pz) < 2.0 ** 30)     # false for a NaN
+    qx, qy, qz = np.where(ok, px, 0.0), np.where(ok, py, 0.0), np.where(ok, pz, 0.0)
+    flx, fly, flz = np.floor(qx), np.floor(qy), np.floor(qz)
+    fx, fy, fz = qx - flx, qy - fly, qz - flz
+    x0, y0, z0 = flx.astype(np.int64) % nx, fly.astype(np.int64) % ny, flz.astype(np.int64) % nz   # numpy's % wraps negatives up
+    x1, y1, z1 = (x0 + 1) % nx, (y0 + 1) % ny, (z0 + 1) % nz
+    c00 = d[z0, y0, x0] + fx * (d[z0, y0, x1] - d[z0, y0, x0])
+    c10 = d[z0, y1, x0] + fx * (d[z0, y1, x1] - d[z0, y1, x0])
+    c01 = d[z1, y0, x0] + fx * (d[z1, y0, x1] - d[z1, y0, x0])
+    c11 = d[z1, y1, x0] + fx * (d[z1, y1, x1] - d[z1, y1, x0])
+    c0 = c00 + fy * (c10 - c00)
+    c1 = c01 + fy * (c11 - c01)
+    return np.where(ok, c0 + fz * (c1 - c0), np.nan)
+
+
+def droplet_radii(field_zyx, centre, dirs, level, step, nsteps, direction="falling"):
+    """The numpy restatement of the shape trace (include/bflbm.h, "Shape traces", is the definition), operation for
+    operation: along every unit vector dirs[j] from `centre` (cell indices x, y, z) the trilinearly interpolated, periodic
+    field_zyx[nz, ny, nx] is sampled at t_k = k step, k = 0 ... nsteps, and the first pair that falls (d_{k-1} >= level >
+    d_k) or rises (d_{k-1} < level <= d_k) through the level gives r = step ((k-1) + linear interpolation).  Returns
+    r[ndir], NaN where a ray has no such pair or the centre is not finite.  It stands for the marching-cubes surface of
+    Droplet_Fluctuation.ipynb cell 32, seen from the centre of mass."""
+    d = np.asarray(field_zyx, dtype=np.float64)
+    if d.ndim != 3:
+        raise ValueError(f"droplet_radii: a field [nz, ny, nx], got shape {d.shape}")
+    u = np.asarray(dirs, dtype=np.float64)
+    if u.ndim != 2 or u.shape[1] != 3:
+        raise ValueError(f"droplet_radii: dirs [ndir, 3], got shape {u.shape}")
+    rising = SHAPE_DIRECTIONS.get(direction, direction)
+    if rising not in (0, 1):
+        raise ValueError(f"droplet_radii: direction {direction!r}, expected 'falling' (0) or 'rising' (1)")
+    nsteps = int(nsteps)
+    if not (nsteps >= 1 and np.isfinite(step) and step > 0):
+        raise ValueError(f"droplet_radii: step {step} must be finite and > 0, nsteps {nsteps} >= 1")
+    c = np.asarray(centre, dtype=np.float64).reshape(3)
+    level, step = np.float64(level), np.float64(step)
+    r = np.full(len(u), np.nan)
+    found = np.zeros(len(u), dtype=bool)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        prev = _density_at(d, c[0] + np.float64(0.0) * u[:, 0], c[1] + np.float64(0.0) * u[:, 1], c[2] + np.float64(0.0) * u[:, 2])
+        for k in range(1, nsteps + 1):
+            t = np.float64(k) * step
+            cur = _density_at(d, c[0] + t * u[:, 0], c[1] + t * u[:, 1], c[2] + t * u[:, 2])
+            if rising:
+                hit, num, den = (prev < level) & (level <= cur), level - prev, cur - prev
+            else:
+                hit, num, den = (prev >= level) & (level > cur), prev - level, prev - cur
+            new = hit & ~found                                   # a NaN density compares false
+            r[new] = (step * (np.float64(k - 1) + num / den))[new]
+            found |= new
+            prev = cur
+    return r
+
+
+def real_harmonics(dirs, lmax):
+    """Orthonormal real spherical harmonics Y[ndir, (lmax + 1)^2] at the unit vectors dirs[ndir, 3], in the order l = 0 ...
+    lmax, m = -l ... l (m < 0: the sin(|m| phi) partner, m > 0: cos(m phi)), without the Condon-Shortley phase.  Built by
+    Cartesian recurrences, no angles: c_m + i s_m = (ux + i uy)^m; Q_m^m = (2m-1)!!, Q_{m+1}^m = (2m+1) uz Q_m^m,
+    Q_l^m = ((2l-1) uz Q_{l-1}^m - (l+m-1) Q_{l-2}^m) / (l-m); Y_lm = N_lm Q_l^|m| {sqrt(2) s_|m|, 1, sqrt(2) c_m} with
+    N_lm^2 = (2l+1) (l-|m|)! / (4 pi (l+|m|)!).  The basis of the zeta_lm of Droplet_Fluctuation.ipynb cells 38 and 41."""
+    u = np.asarray(dirs, dtype=np.float64)
+    lmax = int(lmax)
+    if u.ndim != 2 or u.shape[1] != 3 or lmax < 0:
+        raise ValueError(f"real_harmonics: dirs [ndir, 3] and lmax >= 0, got shape {u.shape} and lmax {lmax}")
+    ux, uy, uz = u[:, 0], u[:, 1], u[:, 2]
+    Y = np.empty((len(u), (lmax + 1) ** 2))
+    cm, sm = np.ones(len(u)), np.zeros(len(u))
+    qmm = 1.0
+    for m in range(lmax + 1):
+        if m > 0:
+            cm, sm = cm * ux - sm * uy, cm * uy + sm * ux
+            qmm *= 2 * m - 1
+        q2, q1 = None, np.full(len(u), qmm)                      # Q_{l-2}^m, Q_{l-1}^m
+        for l in range(m, lmax + 1):
+            if l == m:
+                q = q1
+            elif l == m + 1:
+                q = (2 * m + 1) * uz * q1
+            else:
+                q = ((2 * l - 1) * uz * q1 - (l + m - 1) * q2) / (l - m)
+            if l > m:
+                q2, q1 = q1, q
+            norm = math.sqrt((2 * l + 1) / (4.0 * math.pi) * math.factorial(l - m) / math.factorial(l + m))
+            if m == 0:
+                Y[:, l * l + l] = norm * q
+            else:
+                Y[:, l * l + l + m] = math.sqrt(2.0) * norm * q * cm
+                Y[:, l * l + l - m] = math.sqrt(2.0) * norm * q * sm
+    return Y
+
+
+def shape_modes(r, dirs, weights, lmax):
+    """a_lm = sum_j w_j r_j Y_lm(u_j) of radii r[..., ndir] on the rays dirs with quadrature weights (ray_nodes): the
+    shape coefficients a[..., (lmax + 1)^2] in the order of real_harmonics, a_00 = sqrt(4 pi) times the mean radius.  A
+    frame with a NaN radius gives NaN modes.  These are the zeta_lm(t) of Droplet_Fluctuation.ipynb cells 38 and 41, whose
+    variance the theory gives as kBT / (gamma (l-1)(l+2))."""
+    r = np.asarray(r, dtype=np.float64)
+    w = np.asarray(weights, dtype=np.float64)
+    Y = real_harmonics(dirs, lmax)
+    if r.shape[-1:] != w.shape or w.shape != (Y.shape[0],):
+        raise ValueError(f"shape_modes: r[..., ndir], dirs[ndir, 3] and weights[ndir] disagree: {r.shape}, {Y.shape[0]}, {w.shape}")
+    a = (r.reshape(-1, 1, len(w)) * w) @ Y                       # one product per frame: a NaN stays in its own frame
+    return a.reshape(r.shape[:-1] + (Y.shape[1],))
+
+
 # ---- binned structure factors: the numpy restatement of the spectrum trace (include/bflbm.h, "Spectrum traces") ----------
 SPECTRUM_KINDS = {"shell": 0, "x": 1, "y": 2, "z": 3}
 

@@ -1734,6 +1734,7 @@ int bflbm_fused_plan_query(const int n[3], int nreplicas, int noise, int compute
 #include "bflbm_droplet.h"
 #include "bflbm_trace.h"
 #include "bflbm_iface.h"
+#include "bflbm_shape.h"
 #include "bflbm_batch_sf.h"
 #include "bflbm_spectrum.h"
 #include "bflbm_spectrum_ring.h"

@@ -224,6 +224,59 @@ class InterfaceTrace(_Recorder):
         return self.read()[1][:, :, 1]
 
 
+class ShapeTrace(_Recorder):
+    """Droplet radii along fixed rays from a centre, for every replica, recorded on the device every `every` steps through
+    the owner (a lone single-slab BinaryLBM or a BatchLBM) and read once: include/bflbm.h, "Shape traces".  The device
+    stand-in for the marching-cubes surface and its spherical-harmonic expansion of Droplet_Fluctuation.ipynb (cells 32,
+    38, 41).  Made by owner.shape_trace(); an owner may carry several."""
+    _abi = "bflbm_shape"
+
+    def __init__(self, owner, create, level, nodes, field, direction, centre, threshold, step, rmax, every, capacity):
+        from . import analysis
+        if field not in IFACE_FIELDS and field not in IFACE_FIELDS.values():
+            raise ValueError(f"shape_trace: field {field!r}, expected 'rho' (0) or 'phi' (1)")
+        if direction not in analysis.SHAPE_DIRECTIONS and direction not in analysis.SHAPE_DIRECTIONS.values():
+            raise ValueError(f"shape_trace: direction {direction!r}, expected 'falling' (0) or 'rising' (1)")
+        dirs, weights = analysis.ray_nodes(16, 32) if nodes is None else nodes
+        self.dirs = np.ascontiguousarray(dirs, dtype=np.float64)
+        self.weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if self.dirs.ndim != 2 or self.dirs.shape[1] != 3 or self.weights.shape != (len(self.dirs),):
+            raise ValueError(f"shape_trace: nodes = (dirs[ndir, 3], weights[ndir]), got shapes {self.dirs.shape} and {self.weights.shape}")
+        rmax = min(owner.n) / 2 if rmax is None else float(rmax)
+        step = float(step)
+        if not (np.isfinite(step) and step > 0 and np.isfinite(rmax)):
+            raise ValueError(f"shape_trace: step {step} must be finite and > 0, rmax {rmax} finite")
+        nsteps = int(np.floor(rmax / step))
+        c = None if centre is None else (ctypes.c_double * 3)(*[float(v) for v in centre])
+        thr = -np.inf if threshold is None else float(threshold)
+        super().__init__(owner, create, int(IFACE_FIELDS.get(field, field)), float(level),
+                         int(analysis.SHAPE_DIRECTIONS.get(direction, direction)), c, thr, len(self.dirs),
+                         self.dirs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), step, nsteps, int(every), int(capacity))
+        self.level, self.field, self.direction, self.step = float(level), field, direction, step
+
+    def geometry(self):
+        """(ndir, nsteps, segments of the ray kernel, pairs (k-1, k) per segment): which launch shape the library chose."""
+        v = [ctypes.c_int() for _ in range(4)]
+        check(self.lib.bflbm_shape_geometry(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def read(self):
+        """(steps[count, B] int64, centre[count, B, 3], r[count, B, ndir]): the centre used (cell indices x, y, z) and the
+        radius along every ray, NaN where a ray has no crossing; synchronises the owner's stream."""
+        n, b = self._count()
+        ndir = self.geometry()[0]
+        steps = np.empty((n, b), dtype=np.int64)
+        rec = np.empty((n, b, 3 + ndir))
+        check(self.lib.bflbm_shape_read(self._h, 0, n, _ptr(rec), _ptr(steps)))
+        return steps, rec[..., :3], rec[..., 3:]
+
+    def modes(self, lmax):
+        """a[count, B, (lmax + 1)^2] = analysis.shape_modes of the recorded radii on the trace's nodes: the zeta_lm(t) of
+        the notebook's cells 38 and 41; NaN for a frame with a ray without a crossing."""
+        from . import analysis
+        return analysis.shape_modes(self.read()[2], self.dirs, self.weights, lmax)
+
+
 class SpectrumTrace(_Recorder):
     """The structure factor of chosen pairs of hydrodynamic variables of every sample, binned into shells in |q| or into
     |k| along one axis, recorded on the device every `every` steps through the owner (a lone single-slab BinaryLBM, a
@@ -518,6 +571,14 @@ class BinaryLBM(_DropletMixin):
         The device buffer of `capacity` samples is allocated at once: capacity x 2 ny nx doubles (the default 64 takes
         256 MiB on a 512 x 512 column lattice); a step whose sample would not fit is refused, so size it for the run."""
         return InterfaceTrace(self, "bflbm_iface_create", level, field, window, every, capacity)
+
+    def shape_trace(self, level, nodes=None, field="rho", direction="falling", centre=None, threshold=None, step=0.5, rmax=None, every=1, capacity=64):
+        """Record, after every `every`-th step, the radius at which the `field` ("rho" or "phi") falls (or, direction
+        "rising", rises) through `level` along fixed rays from a centre: ShapeTrace.  nodes = (dirs[ndir, 3], weights[ndir])
+        (None: analysis.ray_nodes(16, 32)); centre: a fixed one in cell indices (x, y, z), or None for the centre of mass of
+        the cells with rho > threshold (None: every cell), which is Trace.com() of the same state; the rays are sampled
+        every `step` cells out to rmax (None: half the smallest extent)."""
+        return ShapeTrace(self, "bflbm_shape_create", level, nodes, field, direction, centre, threshold, step, rmax, every, capacity)
 
     def spectrum_trace(self, var_names_or_pairs, kind="shell", every=1, capacity=64, lb_hydrovars=False, zero_avg=True, var_scaling=None):
         """Record, after every `every`-th step, the structure factor of pairs of hydrovs (lb_hydrovars: hydrovsbar)
@@ -880,6 +941,11 @@ class BatchLBM:
         device buffer is allocated at once: capacity x B x 2 ny nx doubles (the default 64 takes 32 MiB for 16 replicas
         of 8 x 256 columns)."""
         return InterfaceTrace(self, "bflbm_batch_iface_create", level, field, window, every, capacity)
+
+    def shape_trace(self, level, nodes=None, field="rho", direction="falling", centre=None, threshold=None, step=0.5, rmax=None, every=1, capacity=64):
+        """Record every replica's droplet radii along fixed rays (BinaryLBM.shape_trace) after every `every`-th batch step;
+        a fixed centre is one for all replicas, the centre of mass is each replica's own."""
+        return ShapeTrace(self, "bflbm_batch_shape_create", level, nodes, field, direction, centre, threshold, step, rmax, every, capacity)
 
     def spectrum_trace(self, var_names_or_pairs, kind="shell", every=1, capacity=64, lb_hydrovars=False, zero_avg=True, var_scaling=None):
         """Record every replica's binned structure factors (BinaryLBM.spectrum_trace) after every `every`-th batch step,

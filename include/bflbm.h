@@ -391,6 +391,70 @@ int bflbm_iface_read(bflbm_iface* t, long long first, long long count,
                      double* h     /* [count][nreplicas][2][ny][nx] */,
                      long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
 
+/* ---- Shape traces: the radius of a droplet's density contour along fixed rays from its centre, for every replica,
+ * recorded on the device and read once at the end (the droplet shape modes of Droplet_Fluctuation.ipynb, cells 32, 38
+ * and 41: the notebook extracts the rho = (max + min) / 2 surface of 2301 frames of a 32^3 droplet with marching cubes,
+ * expands its radius r(theta, phi) about the centre of mass in spherical harmonics and follows zeta_1m(t), zeta_2m(t);
+ * <|a_lm|^2> = kBT / (gamma (l-1)(l+2)) is the spherical twin of the capillary spectrum of the interface traces).
+ * A shape trace is attached to one lone single-slab context or one replica batch, like an interface trace: it is that
+ * trace turned from columns into rays.  The projection of the radii onto spherical harmonics is left to the host.
+ *  - definition (stated here and nowhere else).  Every operation is an IEEE double operation in the stated order, no
+ *    contraction.  Settings: a field (0 = rho, 1 = phi), a `level`, a direction (0 = falling outward, 1 = rising
+ *    outward), ndir unit vectors u_j given by the caller as dirs[ndir][3] (the library computes no angles and no
+ *    transcendentals), a step delta > 0, a number of steps K >= 1, and either a fixed centre c[3] in cell-index
+ *    coordinates (one for all replicas) or, with a null centre, a threshold.
+ *      centre (null centre): per replica and sample c_a = m_a / m_0, a = x, y, z, where m are the moments an ensemble
+ *        trace with that threshold records (records 1-3 and 0), computed by the same kernels in the same order: the
+ *        centre equals records 1-3 / record 0 of bflbm_trace_read of the same state bit for bit.  If no cell is above
+ *        the threshold the centre is 0 / 0 = NaN, and so is every radius of that replica.
+ *      density at a point p: i_a = floor(p_a), f_a = p_a - (double)i_a; the corner indices i_a and i_a + 1 are wrapped
+ *        periodically into [0, n_a), negative i_a included; d_xyz is the field's density of the resident state at the
+ *        eight corners (x, y, z each 0 for i_a, 1 for i_a + 1), the double bflbm_get_hydrovsbar component 0 / 1 holds;
+ *          c00 = d000 + fx (d100 - d000), c10 = d010 + fx (d110 - d010), c01 = d001 + fx (d101 - d001),
+ *          c11 = d011 + fx (d111 - d011);  c0 = c00 + fy (c10 - c00), c1 = c01 + fy (c11 - c01);  d = c0 + fz (c1 - c0).
+ *        A point with a coordinate that is NaN or not below 2^30 in magnitude has the density NaN; no index is formed
+ *        from it.
+ *      ray j: the sample points are p_a = c_a + t_k u_ja with t_k = (double)k delta, k = 0 ... K, and d_k their densities.
+ *        falling: the first k >= 1 with d_{k-1} >= level >  d_k gives r_j = delta ((double)(k-1) + (d_{k-1} - level) / (d_{k-1} - d_k))
+ *        rising:  the first k >= 1 with d_{k-1} <  level <= d_k gives r_j = delta ((double)(k-1) + (level - d_{k-1}) / (d_k - d_{k-1}))
+ *        No such k gives a quiet NaN; a NaN density satisfies neither condition.
+ *  - sample: [replica][3 + ndir] doubles: the centre used, then the radii r_0 ... r_{ndir-1}.
+ *  - kernels: with a null centre the two kernels of the ensemble trace reduce the moments into a buffer of the shape
+ *    trace's own; one kernel writes the chosen field's density of every site of every replica into the shape trace's own
+ *    copy (152 B read and 8 B written per site), so that a sample point reads 8 doubles; the ray kernel gives every ray a
+ *    lane, splits the pairs (k-1, k) into contiguous segments and writes per segment the first candidate; the last kernel
+ *    takes, per ray, the first non-NaN candidate in segment order.  The number of segments is the library's choice
+ *    (enough one-wave workgroups for one wave per SIMD, each segment at least 4 pairs, an unmeasured heuristic) and
+ *    changes no bit of a sample; bflbm_shape_geometry reports it.  All launches go to the owner's stream, there are no
+ *    atomics and no host round trip; nothing of the owner is written (not rho, phi or their validity).
+ *  - sampling rule, capacity ("shape trace full", refused before any launch), step labels, detaching, service in
+ *    creation order: those of the interface traces above.  An owner may carry several shape traces.
+ *  - refused at creation (non-zero return, a message naming the call, nothing allocated): null arguments, a field or a
+ *    direction other than 0 or 1, a NaN level, a NaN threshold with a null centre, a non-finite fixed centre, ndir < 1
+ *    or > 65536, a direction with a non-finite component or with |u.u - 1| > 1e-6, a step that is not finite or <= 0,
+ *    nsteps < 1, every < 1, capacity < 1, a capacity beyond 1 TB of records, a replica view (use
+ *    bflbm_batch_shape_create), a context with nranks > 1, an open step.  An open step also refuses bflbm_shape_sample,
+ *    _reset and _read.
+ *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_shape_read, _count,
+ *    _geometry and _destroy still work, bflbm_shape_sample fails.
+ *  - bflbm_shape_read synchronises the owner's stream; no other call of this group does.
+ *  - out of scope: rings of z-slabs (droplet ensembles are small boxes), and a droplet that diffuses across the periodic
+ *    boundary: the centre is the ensemble trace's, which does not unwrap (the rays themselves wrap). */
+typedef struct bflbm_shape bflbm_shape;
+int bflbm_shape_create(bflbm_ctx* c, int field, double level, int direction, const double* centre_or_null /* [3] */, double threshold,
+                       int ndir, const double* dirs /* [ndir][3] */, double step, int nsteps, int every, long long capacity, bflbm_shape** out);
+int bflbm_batch_shape_create(bflbm_batch* b, int field, double level, int direction, const double* centre_or_null /* [3] */, double threshold,
+                             int ndir, const double* dirs /* [ndir][3] */, double step, int nsteps, int every, long long capacity, bflbm_shape** out);
+int bflbm_shape_destroy(bflbm_shape* t);
+int bflbm_shape_sample(bflbm_shape* t);                 /* record the resident state now (e.g. frame 0) */
+int bflbm_shape_reset(bflbm_shape* t);                  /* forget the samples, restart the every-counter */
+int bflbm_shape_count(const bflbm_shape* t, long long* nsamples, int* nreplicas);
+int bflbm_shape_geometry(const bflbm_shape* t, int* ndir, int* nsteps, int* nsegments /* of the ray kernel */,
+                         int* segment_len /* pairs (k-1, k) per segment; the last segment may hold fewer */);
+int bflbm_shape_read(bflbm_shape* t, long long first, long long count,
+                     double* r     /* [count][nreplicas][3 + ndir] */,
+                     long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
+
 /* ---- Ensemble structure factors: S(k) of every replica of a batch in one batched pass (the reference's live job
  * accumulates structure factors every out_SF_step steps, main_run_job.cpp:299-310, :342-349; Mixture.ipynb reads them).
  * One accumulator serves the whole batch.  A frame enqueues, on the batch's stream and without a host synchronisation,
