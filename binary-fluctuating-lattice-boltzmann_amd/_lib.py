@@ -153,6 +153,15 @@ SIGNATURES = {
     "bflbm_spectrum_geometry": (ctypes.c_int, [_vp, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_longlong), _P(ctypes.c_int)]),
     "bflbm_spectrum_bins": (ctypes.c_int, [_vp, _vp, _vp]),
     "bflbm_spectrum_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp]),
+    "bflbm_modes_create": (ctypes.c_int, [_vp, ctypes.c_int, _P(ctypes.c_int), ctypes.c_int, ctypes.c_int, _P(ctypes.c_int), ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_batch_modes_create": (ctypes.c_int, [_vp, ctypes.c_int, _P(ctypes.c_int), ctypes.c_int, ctypes.c_int, _P(ctypes.c_int), ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_modes_destroy": (ctypes.c_int, [_vp]),
+    "bflbm_modes_sample": (ctypes.c_int, [_vp]),
+    "bflbm_modes_reset": (ctypes.c_int, [_vp]),
+    "bflbm_modes_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
+    "bflbm_modes_geometry": (ctypes.c_int, [_vp, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int)]),
+    "bflbm_modes_phases": (ctypes.c_int, [ctypes.c_int, _vp]),
+    "bflbm_modes_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp]),
     "bflbm_batch_get_hydrovs": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "bflbm_batch_get_hydrovsbar": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "bflbm_set_ref_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(Fab)]),

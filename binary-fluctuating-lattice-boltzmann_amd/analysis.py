@@ -343,6 +343,39 @@ def domain_length(q, s_mean):
 # ---- the same observables from the device-reduced raw moments (BinaryLBM.droplet_moments) ----------------
 # m[0:10] = sum rho {1, x, y, z, xx, xy, xz, yy, yz, zz} in cell indices, m[10:20] trapezoid-weighted.
 
+def fourier_modes(field_zyx, modes):
+    """a^(m) of include/bflbm.h, "Mode traces", in numpy: field_zyx[..., nz, ny, nx] real, modes[nmodes, 3] integer
+    (mx, my, mz), any integers; returns complex128 [..., nmodes] = fftn(field)[mz % nz, my % ny, mx % nx].  np.exp
+    phases and numpy's summation order: equal to the library's records up to rounding, not bit for bit."""
+    a = np.asarray(field_zyx, dtype=np.float64)
+    m = np.asarray(modes)
+    if a.ndim < 3 or m.ndim != 2 or m.shape[1] != 3 or not np.issubdtype(m.dtype, np.integer):
+        raise ValueError(f"fourier_modes: field[..., nz, ny, nx] and integer modes[nmodes, 3], got {a.shape} and {m.shape} of {m.dtype}")
+    nz, ny, nx = a.shape[-3:]
+    if len(m) == 0:
+        return np.empty(a.shape[:-3] + (0,), dtype=np.complex128)
+    ex, ey, ez = [np.exp(-2j * np.pi * (((m[:, d] % n)[None, :] * np.arange(n)[:, None]) % n) / n)     # [n, nmodes]
+                  for d, n in enumerate((nx, ny, nz))]
+    rows = np.ascontiguousarray(a).reshape(-1, nx)
+    t = (rows @ ex.real + 1j * (rows @ ex.imag)).reshape(a.shape[:-1] + (len(m),))      # x summed: [..., nz, ny, nmodes]
+    t = (t * ey).sum(axis=-2)                              # y summed: [..., nz, nmodes]
+    return (t * ez).sum(axis=-2)
+
+
+def time_correlation(a, b=None, max_lag=None):
+    """C[lag] = mean over t of a[t + lag] conj(b[t]), lag = 0 .. max_lag, along the leading axis (b None: a itself; max_lag
+    None: len(a) - 1); the other axes pass through.  Every lag averages over the len(a) - lag pairs it has."""
+    a = np.asarray(a)
+    b = a if b is None else np.asarray(b)
+    if a.shape != b.shape or a.ndim < 1 or len(a) < 1:
+        raise ValueError(f"time_correlation: two series of one shape with a leading time axis, got {a.shape} and {b.shape}")
+    nt = len(a)
+    max_lag = nt - 1 if max_lag is None else int(max_lag)
+    if not 0 <= max_lag < nt:
+        raise ValueError(f"time_correlation: max_lag {max_lag} outside 0 .. {nt - 1}")
+    return np.stack([(a[lag:] * np.conj(b[:nt - lag])).mean(axis=0) for lag in range(max_lag + 1)])
+
+
 def com_from_moments(m, n, weighted=False):
     """Centre of mass in unit-box cell-centre coordinates; weighted=True is the reference's C++ getCenterOfMass
     (trapezoid weights, LBM_hydrovs.H:62-113), False the notebooks' plain sum."""

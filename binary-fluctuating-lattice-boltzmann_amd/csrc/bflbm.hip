@@ -1738,3 +1738,4 @@ int bflbm_fused_plan_query(const int n[3], int nreplicas, int noise, int compute
 #include "bflbm_batch_sf.h"
 #include "bflbm_spectrum.h"
 #include "bflbm_spectrum_ring.h"
+#include "bflbm_modes.h"

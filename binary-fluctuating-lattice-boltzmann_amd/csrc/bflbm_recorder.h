@@ -1,5 +1,5 @@
 // bflbm_recorder.h -- the one lifecycle of everything that records from an owner's resident state: ensemble traces
-// (bflbm_trace.h), interface traces (bflbm_iface.h), shape traces (bflbm_shape.h), spectrum traces (bflbm_spectrum.h) and ensemble structure factors
+// (bflbm_trace.h), interface traces (bflbm_iface.h), shape traces (bflbm_shape.h), spectrum traces (bflbm_spectrum.h), mode traces (bflbm_modes.h) and ensemble structure factors
 // (bflbm_batch_sf.h).  A recorder is
 // attached to a lone context, a batch or a ring of more than one slab, is served after every step on the owner's stream(s)
 // in creation order, survives its owner detached (readable, no longer fed) and is destroyed by its own call (DESIGN.md,

@@ -346,6 +346,54 @@ class SpectrumTrace(_Recorder):
             return np.where(count > 0, sums / count, np.nan)
 
 
+class ModeTrace(_Recorder):
+    """The complex Fourier amplitudes of chosen hydrodynamic variables at chosen integer wavevectors, for every replica,
+    recorded on the device every `every` steps through the owner (a lone single-slab BinaryLBM or a BatchLBM) and read
+    once: include/bflbm.h, "Mode traces".  What time correlations are made of (analysis.time_correlation).  Made by
+    owner.mode_trace(); an owner may carry several.  Closing the owner detaches the trace: it stays readable until its
+    own close()."""
+    _abi = "bflbm_modes"
+
+    def __init__(self, owner, create, variables, modes, every, capacity, lb_hydrovars):
+        from . import plotfile
+        self.lb = bool(lb_hydrovars)
+        names = plotfile.variable_names(NHYDROBAR if self.lb else NHYDRO)
+        items = [variables] if isinstance(variables, (str, int, np.integer)) else list(variables)
+        for v in items:
+            if isinstance(v, str) and v not in names:
+                raise ValueError(f"mode_trace: variable {v!r}, expected one of {names} or an index")
+        self.variables = [names.index(v) if isinstance(v, str) else int(v) for v in items]
+        m = np.asarray(modes)
+        if m.ndim != 2 or m.shape[1] != 3 or not np.issubdtype(m.dtype, np.integer):
+            raise ValueError(f"mode_trace: modes is an integer array [nmodes, 3], got shape {m.shape} of {m.dtype}")
+        self.modes = np.ascontiguousarray(m, dtype=np.int32)
+        nv, nm = len(self.variables), len(self.modes)
+        va = (ctypes.c_int * max(nv, 1))(*self.variables)
+        super().__init__(owner, create, nv, va, int(self.lb), nm, self.modes.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                         int(every), int(capacity))
+
+    def _owner_closing(self):
+        """The owner's close(): the library detaches the trace; its samples stay readable until close()."""
+        _unregister(self.owner, self)
+
+    def geometry(self):
+        """(variables, wavevectors, tiles per plane, sites per tile): what the library built."""
+        v = [ctypes.c_int() for _ in range(4)]
+        check(self.lib.bflbm_modes_geometry(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def read(self, first=0, count=None):
+        """(steps[count, B] int64, amp[count, B, nvars, nmodes] complex128) of the samples first ... first + count - 1
+        (count None: all from `first`); synchronises the owner's stream."""
+        n, b = self._count()
+        count = n - int(first) if count is None else int(count)
+        nv, nm = self.geometry()[:2]
+        steps = np.empty((max(count, 0), b), dtype=np.int64)
+        amp = np.empty((max(count, 0), b, nv, nm), dtype=np.complex128)
+        check(self.lib.bflbm_modes_read(self._h, int(first), count, _ptr(amp), _ptr(steps)))
+        return steps, amp
+
+
 # kernel schedules of include/bflbm.h (bflbm_set_schedule): "fused" = plane march with the ring densities pulled
 # (bit-exact), "handover" = plane march with the ring densities handed over from the previous step (tolerance)
 SCHEDULES = {"two_pass": 0, "fused": 1, "fused_exact": 1, "auto": 2, "handover": 3}
@@ -585,6 +633,12 @@ class BinaryLBM(_DropletMixin):
         variables binned into shells in |q| (kind "shell") or into |k| along one axis ("x", "y", "z"): SpectrumTrace.
         Variable names form the pairs of structfact.StructFact; a list of index pairs (a, b) is taken as it is."""
         return SpectrumTrace(self, "bflbm_spectrum_create", var_names_or_pairs, kind, every, capacity, lb_hydrovars, zero_avg, var_scaling)
+
+    def mode_trace(self, variables, modes, every=1, capacity=64, lb_hydrovars=False):
+        """Record, after every `every`-th step, the Fourier amplitudes of hydrovs (lb_hydrovars: hydrovsbar) variables,
+        given by name (plotfile.variable_names) or index, at the integer wavevectors modes[nmodes, 3] = (mx, my, mz):
+        ModeTrace.  `capacity` samples of nvars x nmodes complex numbers are allocated at creation."""
+        return ModeTrace(self, "bflbm_modes_create", variables, modes, every, capacity, lb_hydrovars)
 
     def com_sums(self):
         s = (ctypes.c_double * 4)()
@@ -951,6 +1005,11 @@ class BatchLBM:
         """Record every replica's binned structure factors (BinaryLBM.spectrum_trace) after every `every`-th batch step,
         with one observation launch, one batched transform and two binning launches per sample."""
         return SpectrumTrace(self, "bflbm_batch_spectrum_create", var_names_or_pairs, kind, every, capacity, lb_hydrovars, zero_avg, var_scaling)
+
+    def mode_trace(self, variables, modes, every=1, capacity=64, lb_hydrovars=False):
+        """Record every replica's Fourier amplitudes (BinaryLBM.mode_trace) after every `every`-th batch step, with one
+        observation launch, one projection launch and one finishing launch per sample."""
+        return ModeTrace(self, "bflbm_batch_modes_create", variables, modes, every, capacity, lb_hydrovars)
 
     def structfact(self, var_names, **kw):
         """One structure-factor accumulator for the whole batch (structfact.BatchStructFact; every=k attaches it)."""

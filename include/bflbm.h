@@ -588,6 +588,73 @@ int bflbm_spectrum_read(bflbm_spectrum* t, long long first, long long count,
                         double* sums  /* [count][nreplicas][npairs][nbins] */,
                         long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
 
+/* ---- Mode traces: the complex Fourier amplitudes of chosen hydrodynamic variables at chosen wavevectors, recorded on the
+ * device as a time series and read once at the end.  The spectrum traces above keep Re(a^ conj(b^)) summed over bins,
+ * which drops the phase and mixes the wavevectors; time correlations (the intermediate scattering function
+ * <a^(k, t+s) conj(a^(k, t))>, the dynamic structure factor, the decay rates that give viscosity, sound attenuation and
+ * diffusion, the Onsager-regression check; Correlation.ipynb) need a^(k, t) of single wavevectors at consecutive steps.
+ * A mode trace is attached to one lone single-slab context or one replica batch, like a spectrum trace.
+ *  - definition (stated here and nowhere else).  For a real field a on the periodic nx x ny x nz lattice and an integer
+ *    wavevector m = (mx, my, mz), any integers, reduced mod n per axis:
+ *      a^(m) = sum over (x, y, z) of a(x, y, z) E(m; x, y, z),   E = e^{-2 pi i (mx x / nx + my y / ny + mz z / nz)},
+ *    the unnormalised DFT of bflbm_sf_* with numpy's fftn sign: a^(m) == fftn(a)[mz % nz, my % ny, mx % nx] up to rounding.
+ *    The phases come from one table per axis, T_n[j] = (cos(2 pi j / n), -sin(2 pi j / n)), j = 0 .. n-1, built once on
+ *    the host at creation and exposed by bflbm_modes_phases (host only, needs no device).  The angle is reduced to an
+ *    octant in integers: entries with 4 j % n == 0 are exactly (+-1, +-0) or (+-0, +-1), every entry is within 2^-52 of
+ *    the real value, and T_n[n - j] == conj(T_n[j]) exactly (the device keeps T_nx and T_ny as their lower halves).
+ *    The term of a site is a * ((T_nx[jx] * T_ny[jy]) * T_nz[jz]) with jx = ((mx mod nx) x) mod nx, jy and jz likewise,
+ *    every complex product written re = ar br - ai bi, im = ar bi + ai br and left unfused (-ffp-contract=off).  The
+ *    factor T_nz[jz] is applied to a plane's sum, not per site: a site adds a * (T_nx[jx] * T_ny[jy]), real times complex.
+ *  - order of the sums, fixed by the box, the wavevector list and the variable list alone.  A dense plane z (sites
+ *    s = y nx + x) is cut into tiles of 2048 consecutive sites, the last one short (bflbm_modes_geometry reports both
+ *    numbers).  Per (replica, z, tile, variable, wavevector): thread t of 256 starts from 0 and adds the terms of the
+ *    tile's sites t, t + 256, ..., t + 1792 in that order (a site past the plane adds 0); the 256 sums are added by
+ *    the binary tree v[t] += v[t + w], w = 128, 64, ..., 1.  Then per (replica, variable, wavevector): the tiles of a
+ *    plane are added in tile order starting from 0, the plane's sum is multiplied by T_nz[jz], and the planes are added
+ *    in the sequence z = 0 .. nz-1 starting from 0, as the last step.  No atomics.  A record does not depend on the
+ *    number of replicas, `every`, the capacity, the schedule, what else is attached, or lone context versus replica.
+ *  - sample: [replica][var][mode][2] doubles (re, im).  `vars` index hydrovs; with lb_hydrovars != 0 they index
+ *    hydrovsbar (the spectrum trace's convention).  1..8 distinct variables, 1..64 wavevectors, fixed at creation.
+ *  - how a sample is taken, on the owner's stream and without a host synchronisation: the accumulators' observation, as
+ *    the spectrum trace's first step (a batch: one launch over all replicas, only the chosen variables, into a buffer of
+ *    the trace; a lone context: into its scratch state buffer), the projection kernel (grid tiles x nz x replicas; a
+ *    site's values are loaded once, the x and y tables sit in LDS) and the finishing launch (grid (var, mode) x
+ *    replicas, the planes spread over the threads first).  Boxes with (nx/2 + 1) + (ny/2 + 1) > 2304 are refused: their
+ *    tables do not fit the projection kernel's LDS (36864 + 3072 nvars bytes, 61440 with 8 variables: 2304 table
+ *    entries and the tree's two exchange buffers of 2 nvars x 128 and 2 nvars x 64 doubles; the kernel is compiled once
+ *    per number of variables;
+ *    the finishing kernel uses 4096).  The tile size, the one-wavevector groups and the split of the finish are untimed
+ *    heuristics.
+ *  - what is touched on the owner: what the spectrum trace's observation touches.  Observing hydrovs rewrites rho / phi
+ *    by the density pass where they are stale; a lone context's scratch state buffer is overwritten.  The resident
+ *    state, the step counters and everything the owner computes are unchanged.
+ *  - sampling rule, capacity, step labels, order among the recorders of one owner: those of the other traces ("mode
+ *    trace full").  An owner may carry any number of mode traces.
+ *  - refused at creation (non-zero return, a message naming the call, nothing allocated): null arguments, counts outside
+ *    the limits, a repeated variable, a variable outside its set, every < 1, capacity < 1, a capacity beyond 1 TB of
+ *    records, the table limit above, nz > 65535, a replica view (use bflbm_batch_modes_create), a context with
+ *    nranks > 1, an open step, a failed allocation (the message gives the bytes of each buffer).  An open step also
+ *    refuses bflbm_modes_sample, _reset and _read.  Rings are not served yet; the planes are the last sum so that a ring
+ *    of z-slabs can follow.
+ *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_modes_read, _count,
+ *    _geometry and _destroy still work, bflbm_modes_sample fails.
+ *  - creation uploads the tables with blocking copies.  After it only bflbm_modes_read and bflbm_modes_destroy
+ *    synchronise the owner's stream. */
+typedef struct bflbm_modes bflbm_modes;
+int bflbm_modes_create(bflbm_ctx* c, int nvars, const int* vars, int lb_hydrovars, int nmodes, const int* modes /* [nmodes][3] */,
+                       int every, long long capacity, bflbm_modes** out);
+int bflbm_batch_modes_create(bflbm_batch* b, int nvars, const int* vars, int lb_hydrovars, int nmodes, const int* modes /* [nmodes][3] */,
+                             int every, long long capacity, bflbm_modes** out);
+int bflbm_modes_destroy(bflbm_modes* t);
+int bflbm_modes_sample(bflbm_modes* t);                    /* record the resident state now (e.g. frame 0) */
+int bflbm_modes_reset(bflbm_modes* t);                     /* forget the samples, restart the every-counter */
+int bflbm_modes_count(const bflbm_modes* t, long long* nsamples, int* nreplicas);
+int bflbm_modes_geometry(const bflbm_modes* t, int* nvars, int* nmodes, int* tiles_per_plane, int* tile_sites);
+int bflbm_modes_phases(int n, double* table /* [n][2] */); /* T_n; host only */
+int bflbm_modes_read(bflbm_modes* t, long long first, long long count,
+                     double* amp /* [count][nreplicas][nvars][nmodes][2] */,
+                     long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
+
 /* Materialise the per-step fields the reference keeps in MultiFabs, for the state
  * after the last completed step:
  *   hydrovsbar comps 0..8  (LBM_hydrovars_density, LBM_binary.H:315-354)
