@@ -162,6 +162,14 @@ SIGNATURES = {
     "bflbm_modes_geometry": (ctypes.c_int, [_vp, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int)]),
     "bflbm_modes_phases": (ctypes.c_int, [ctypes.c_int, _vp]),
     "bflbm_modes_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp]),
+    "bflbm_fstat_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), ctypes.c_int, _P(_vp)]),
+    "bflbm_batch_fstat_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), ctypes.c_int, _P(_vp)]),
+    "bflbm_ring_fstat_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), ctypes.c_int, _P(_vp)]),
+    "bflbm_fstat_destroy": (ctypes.c_int, [_vp]),
+    "bflbm_fstat_sample": (ctypes.c_int, [_vp]),
+    "bflbm_fstat_reset": (ctypes.c_int, [_vp]),
+    "bflbm_fstat_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
+    "bflbm_fstat_get": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
     "bflbm_batch_get_hydrovs": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "bflbm_batch_get_hydrovsbar": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "bflbm_set_ref_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(Fab)]),

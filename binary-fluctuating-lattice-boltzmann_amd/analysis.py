@@ -376,6 +376,51 @@ def time_correlation(a, b=None, max_lag=None):
     return np.stack([(a[lag:] * np.conj(b[:nt - lag])).mean(axis=0) for lag in range(max_lag + 1)])
 
 
+def field_statistics(frames, pairs=()):
+    """Field statistics of include/bflbm.h in numpy, operation for operation: frames[N][nvars][nz][ny][nx] in recording
+    order (one replica), pairs of variable slots (a, b).  Returns a dict of `first`[nvars, ...], `sum`[nvars, ...] (the
+    sequential sum), `prod`[npairs, ...] (sum over the frames, from +0.0, of the product of the deviations from the first
+    frame), `mean` = sum * (1.0 / N) and `cov` = prod * (1.0 / N) - (mean[a] - first[a]) * (mean[b] - first[b]), and `N`."""
+    x = np.asarray(frames, dtype=np.float64)
+    if x.ndim < 2 or len(x) < 1:
+        raise ValueError(f"field_statistics: frames[N >= 1][nvars][...], got shape {x.shape}")
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    for a, b in pairs:
+        if not (0 <= a < x.shape[1] and 0 <= b < x.shape[1]):
+            raise ValueError(f"field_statistics: pair ({a}, {b}) outside the {x.shape[1]} variables")
+    n = len(x)
+    first = x[0].copy()
+    total = x[0].copy()
+    prod = np.zeros((len(pairs),) + x.shape[2:])
+    for t in range(1, n):
+        total = total + x[t]
+        dev = x[t] - first
+        for p, (a, b) in enumerate(pairs):
+            prod[p] = prod[p] + dev[a] * dev[b]
+    inv = 1.0 / float(n)
+    mean = total * inv
+    cov = np.empty_like(prod)
+    for p, (a, b) in enumerate(pairs):
+        cov[p] = prod[p] * inv - (mean[a] - first[a]) * (mean[b] - first[b])
+    return dict(first=first, sum=total, prod=prod, mean=mean, cov=cov, N=n)
+
+
+def field_statistics_ensemble(replicas):
+    """The ensemble values of include/bflbm.h, "Field statistics", from the field_statistics of the replicas 0 ... B-1
+    (all of N frames): `mean` = the replicas' sum added in that order from 0, times 1.0 / (B N); `cov` = the replicas' cov
+    added in that order from 0, times 1.0 / B (the mean within-replica covariance)."""
+    reps = list(replicas)
+    if not reps or any(r["N"] != reps[0]["N"] for r in reps):
+        raise ValueError("field_statistics_ensemble: the statistics of B >= 1 replicas over the same number of frames")
+    total = np.zeros_like(reps[0]["sum"])
+    cov = np.zeros_like(reps[0]["cov"])
+    for r in reps:
+        total = total + r["sum"]
+        cov = cov + r["cov"]
+    b = float(len(reps))
+    return dict(mean=total * (1.0 / (b * float(reps[0]["N"]))), cov=cov * (1.0 / b))
+
+
 def com_from_moments(m, n, weighted=False):
     """Centre of mass in unit-box cell-centre coordinates; weighted=True is the reference's C++ getCenterOfMass
     (trapezoid weights, LBM_hydrovs.H:62-113), False the notebooks' plain sum."""

@@ -1,10 +1,11 @@
 // bflbm_recorder.h -- the one lifecycle of everything that records from an owner's resident state: ensemble traces
-// (bflbm_trace.h), interface traces (bflbm_iface.h), shape traces (bflbm_shape.h), spectrum traces (bflbm_spectrum.h), mode traces (bflbm_modes.h) and ensemble structure factors
-// (bflbm_batch_sf.h).  A recorder is
+// (bflbm_trace.h), interface traces (bflbm_iface.h), shape traces (bflbm_shape.h), spectrum traces (bflbm_spectrum.h), mode traces (bflbm_modes.h), ensemble structure factors
+// (bflbm_batch_sf.h) and field statistics (bflbm_fstat.h).  A recorder is
 // attached to a lone context, a batch or a ring of more than one slab, is served after every step on the owner's stream(s)
 // in creation order, survives its owner detached (readable, no longer fed) and is destroyed by its own call (DESIGN.md,
 // "Recorders").  A ring serves its recorders from bflbm_ring_step only, after the bflbm_step_finish of every slab; its
-// samples carry slab 0's step counter and its records live on slab 0's device, written on slab 0's stream.
+// samples carry slab 0's step counter and its records live on slab 0's device, written on slab 0's stream (field
+// statistics excepted: a per-site accumulator stays on the slab that owns the site).
 // Host code only.  Included by bflbm.hip once bflbm_ctx, bflbm_batch and bflbm_ring are complete (needs fail, HIP_TRY).
 #ifndef BFLBM_RECORDER_H_
 #define BFLBM_RECORDER_H_

@@ -394,6 +394,102 @@ class ModeTrace(_Recorder):
         return steps, amp
 
 
+FSTAT_SOURCES = {"hydrovs": 0, "hydrovsbar": 1, "noise": 2}
+FSTAT_WHAT = {"sum": 0, "mean": 1, "first": 2, "prod": 3, "cov": 4}
+
+
+def fstat_variable_names(source):
+    """The component names of a field-statistics source: plotfile.variable_names for hydrovs (22) and hydrovsbar (9),
+    WriteOutNoise's fa0 .. fa18, ga0 .. ga18 for the noise moments.  FieldStats also takes fn<k> / gn<k> for fa<k> / ga<k>
+    and "rhot" for component 5 (rho + phi, the equilibrium_rhot field, which VariableNames calls p_bulk)."""
+    from . import plotfile
+    if source == 2:
+        return plotfile.noise_names("f") + plotfile.noise_names("g")
+    return plotfile.variable_names(NHYDROBAR if source == 1 else NHYDRO)
+
+
+class FieldStats(_Recorder):
+    """The running mean of chosen fields at every site over the frames taken, and chosen second moments around it,
+    accumulated on the device for a lone single-slab BinaryLBM, every replica of a BatchLBM or a RingLBM:
+    include/bflbm.h, "Field statistics"; analysis.field_statistics is the same arithmetic in numpy.  Made by
+    owner.field_stats().  every = 0: fed by sample() only.  An owner may carry several.  Closing the owner detaches the
+    recorder: it stays readable until its own close()."""
+    _abi = "bflbm_fstat"
+
+    def __init__(self, owner, create, variables, pairs, source, every):
+        if source not in FSTAT_SOURCES and source not in FSTAT_SOURCES.values():
+            raise ValueError(f"field_stats: source {source!r}, expected one of {sorted(FSTAT_SOURCES)} or 0..2")
+        self.source = int(FSTAT_SOURCES.get(source, source))
+        self.names = fstat_variable_names(self.source)
+        items = [variables] if isinstance(variables, (str, int, np.integer)) else list(variables)
+        self.variables = [self._component(v) for v in items]
+        self.pairs = [(self._slot(a), self._slot(b)) for a, b in [(p, p) if isinstance(p, str) else p for p in pairs]]   # a lone name: its variance
+        nv, npairs = len(self.variables), len(self.pairs)
+        va = (ctypes.c_int * max(nv, 1))(*self.variables)
+        pa = (ctypes.c_int * max(npairs, 1))(*[p[0] for p in self.pairs])
+        pb = (ctypes.c_int * max(npairs, 1))(*[p[1] for p in self.pairs])
+        super().__init__(owner, create, self.source, nv, va, npairs, pa, pb, int(every))
+        self.shape = (owner.n[2], owner.n[1], owner.n[0])
+
+    def _component(self, v):
+        """A variable by name or by component index of the source."""
+        if not isinstance(v, str):
+            return int(v)
+        if self.source == 2 and len(v) > 2 and v[:2] in ("fn", "gn") and v[2:].isdigit():
+            v = v[0] + "a" + v[2:]
+        if self.source != 2 and v == "rhot":               # component 5, rho + phi, which VariableNames calls p_bulk
+            return 5
+        if v not in self.names:
+            raise ValueError(f"field_stats: variable {v!r}, expected one of {self.names} or an index")
+        return self.names.index(v)
+
+    def _slot(self, v):
+        """A recorded variable by name or by slot (its position in the variable list)."""
+        if not isinstance(v, str):
+            return int(v)
+        c = self._component(v)
+        if c not in self.variables:
+            raise ValueError(f"field_stats: {v!r} is not one of the recorded variables")
+        return self.variables.index(c)
+
+    def _pair(self, p):
+        """A recorded pair by index or as (a, b) of names or slots."""
+        if isinstance(p, (int, np.integer)):
+            return int(p)
+        p = (p, p) if isinstance(p, str) else p
+        key = (self._slot(p[0]), self._slot(p[1]))
+        if key not in self.pairs:
+            raise ValueError(f"field_stats: the pair {p!r} is not recorded")
+        return self.pairs.index(key)
+
+    def _owner_closing(self):
+        """The owner's close(): the library detaches the recorder; it stays readable until close()."""
+        _unregister(self.owner, self)
+
+    def _get(self, what, index, replica):
+        out = np.empty(self.shape)
+        check(self.lib.bflbm_fstat_get(self._h, FSTAT_WHAT[what], int(index), int(replica), _ptr(out)))
+        return out
+
+    def mean(self, v, replica=0):
+        """sum * (1 / N) of a variable (name or slot) [nz, ny, nx]; replica -1: the ensemble mean.  Synchronises."""
+        return self._get("mean", self._slot(v), replica)
+
+    def cov(self, p, replica=0):
+        """The covariance (divisor N) of a pair (index, or (a, b) of names or slots) [nz, ny, nx]; replica -1: the mean
+        within-replica covariance.  Synchronises."""
+        return self._get("cov", self._pair(p), replica)
+
+    def sum(self, v, replica=0):
+        return self._get("sum", self._slot(v), replica)
+
+    def first(self, v, replica=0):
+        return self._get("first", self._slot(v), replica)
+
+    def prod(self, p, replica=0):
+        return self._get("prod", self._pair(p), replica)
+
+
 # kernel schedules of include/bflbm.h (bflbm_set_schedule): "fused" = plane march with the ring densities pulled
 # (bit-exact), "handover" = plane march with the ring densities handed over from the previous step (tolerance)
 SCHEDULES = {"two_pass": 0, "fused": 1, "fused_exact": 1, "auto": 2, "handover": 3}
@@ -640,6 +736,12 @@ class BinaryLBM(_DropletMixin):
         ModeTrace.  `capacity` samples of nvars x nmodes complex numbers are allocated at creation."""
         return ModeTrace(self, "bflbm_modes_create", variables, modes, every, capacity, lb_hydrovars)
 
+    def field_stats(self, variables, pairs=(), source="hydrovs", every=0):
+        """Accumulate, at every site, the mean over frames of up to 8 variables of `source` ("hydrovs", "hydrovsbar" or
+        "noise"; names or component indices) and the covariance of up to 16 pairs of them (names or slots; a lone name is
+        its variance): FieldStats.  A frame is taken after every `every`-th step; every = 0: by sample() only."""
+        return FieldStats(self, "bflbm_fstat_create", variables, pairs, source, every)
+
     def com_sums(self):
         s = (ctypes.c_double * 4)()
         check(self.lib.bflbm_com_sums(self._h, s))
@@ -820,6 +922,11 @@ class RingLBM(_DropletMixin):
         """Record, after every `every`-th step, the binned structure factor of pairs of hydrovs (lb_hydrovars: hydrovsbar)
         variables by a slab FFT over the ring: SpectrumTrace, with the arguments of BinaryLBM.spectrum_trace."""
         return SpectrumTrace(self, "bflbm_ring_spectrum_create", var_names_or_pairs, kind, every, capacity, lb_hydrovars, zero_avg, var_scaling)
+
+    def field_stats(self, variables, pairs=(), source="hydrovs", every=0):
+        """Per-site means and covariances over frames (BinaryLBM.field_stats); every slab keeps the accumulators of its
+        own planes on its own device, the values are a lone lattice's bit for bit."""
+        return FieldStats(self, "bflbm_ring_fstat_create", variables, pairs, source, every)
 
     def _gather(self, ncomp, call):
         out = np.empty((ncomp, self.n[2], self.n[1], self.n[0]))
@@ -1010,6 +1117,11 @@ class BatchLBM:
         """Record every replica's Fourier amplitudes (BinaryLBM.mode_trace) after every `every`-th batch step, with one
         observation launch, one projection launch and one finishing launch per sample."""
         return ModeTrace(self, "bflbm_batch_modes_create", variables, modes, every, capacity, lb_hydrovars)
+
+    def field_stats(self, variables, pairs=(), source="hydrovs", every=0):
+        """Every replica's per-site means and covariances over frames (BinaryLBM.field_stats), with one observation launch
+        and one accumulation launch per frame; replica=-1 reads the ensemble values.  No "noise" source on a batch."""
+        return FieldStats(self, "bflbm_batch_fstat_create", variables, pairs, source, every)
 
     def structfact(self, var_names, **kw):
         """One structure-factor accumulator for the whole batch (structfact.BatchStructFact; every=k attaches it)."""

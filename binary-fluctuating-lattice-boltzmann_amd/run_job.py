@@ -13,7 +13,8 @@ What it mirrors (main_run_job.cpp line numbers):
     :253-270 (if_continue_from_last_frame)
   * equilibrium-state extraction at kBT == 0 :423-438: PrintConvergence (Debug.H:275-358) = ensemble mean of
     components 0, 1, 5 over the last t_window/plot_int + 1 frames -> equilibrium_{rho,phi,rhot}_alpha0_X_sizeN-N-N,
-    and its printed convergence measure (mean absolute deviation from the ensemble mean)
+    and its printed convergence measure (mean absolute deviation from the ensemble mean); --eq-device accumulates the
+    means on the GPU while the job runs (BinaryLBM.field_stats) and writes the same files from them
 Frames hold `hydrovs` (22 components, VariableNames) -- the reference's STRUCT_HYDROVARS variant; with
 --lb-hydrovars the 15-component `hydrovsbar` is written under the same names like the shipped
 STRUCT_LB_HYDROVARS build does (main_run_job.cpp:19, :321).
@@ -100,6 +101,7 @@ def main(argv=None):
     ap.add_argument("--use-ref-state", action="store_true", help="noise amplitudes from the equilibrium_* files (USE_REF_STATE)")
     ap.add_argument("--sf-device", action="store_true", help="accumulate the structure factors on the GPU (hipFFT)")
     ap.add_argument("--lb-hydrovars", action="store_true", help="write hydrovsbar (15 comps) like STRUCT_LB_HYDROVARS")
+    ap.add_argument("--eq-device", action="store_true", help="form the equilibrium_* means on the GPU (field statistics) instead of from the frames read back")
     ap.add_argument("--root", default=".")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
@@ -184,8 +186,22 @@ def main(argv=None):
               else pkg.structfact.StructFact(sf_names))
     sf_start = last - a.plot_sf_window                                      # :330
     out_step = a.step_continue + 2 * a.nsteps // 10 if noise else a.step_continue    # :89
+    eq_window = None                                                        # the frames PrintConvergence averages, :423-438
+    if not noise and a.plot_int > 0:
+        t_window = 5 * a.plot_int                                           # :95
+        eq_window = (max(last - t_window, out_step + (-out_step) % a.plot_int), last)
+    eq_stats, eq_steps = None, ()
+    if a.eq_device and eq_window is not None:
+        # the frame mean of components 0, 1, 5 at every site, accumulated on the device at exactly the frames the disk
+        # route reads back (hydrovsbar has rho, phi and the total density at the same three indices)
+        eq_stats = lbm.field_stats([0, 1, 5], source="hydrovsbar" if a.lb_hydrovars else "hydrovs", every=0)
+        eq_steps = set(range(eq_window[0], eq_window[1] + 1, a.plot_int))
+        if a.step_continue in eq_steps:
+            eq_stats.sample()
     for step in range(a.step_continue + 1, last + 1):                       # :335-387
         lbm.LBM_timestep(1)
+        if step in eq_steps:
+            eq_stats.sample()
         if a.print_int and step % a.print_int == 0 and step % (a.print_int * 50) == 0:
             print("LB step %d" % step)
         if sf is not None and step >= sf_start and step % a.out_sf_step == 0:   # :342-349
@@ -209,12 +225,13 @@ def main(argv=None):
     print("mass rho = %.17g phi = %.17g" % (rho_mass, phi_mass))
     print("Run time = %g" % (time.time() - t0))
 
-    if not noise and a.plot_int > 0:                                        # :423-438
-        t_window = 5 * a.plot_int                                           # :95
-        step1, step2 = max(last - t_window, out_step + (-out_step) % a.plot_int), last
-        for key, comp in (("rho", 0), ("phi", 1), ("rhot", 5)):
+    if eq_window is not None:                                               # :423-438
+        step1, step2 = eq_window
+        for slot, (key, comp) in enumerate((("rho", 0), ("phi", 1), ("rhot", 5))):
             mean, dev = print_convergence(pf, paths["plot_root"], step1, step2, a.plot_int, comp)
-            print("convergence(%s) = %.6e" % (key, dev))
+            print("convergence(%s) = %.6e" % (key, dev))     # an L1 deviation: two passes over the frames, the disk route's
+            if eq_stats is not None:
+                mean = eq_stats.mean(slot)
             pf.write_plotfile(paths["eq"][key], mean[None], [key + "_eq"], 0.0, 0, mgs)
     lbm.close()
     return 0

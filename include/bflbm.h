@@ -655,6 +655,83 @@ int bflbm_modes_read(bflbm_modes* t, long long first, long long count,
                      double* amp /* [count][nreplicas][nvars][nmodes][2] */,
                      long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
 
+/* ---- Field statistics: the running mean of chosen fields at every site over the frames taken, and the second moments
+ * around it, accumulated on the device (PrintConvergence, Debug.H:275-358 and main_run_job.cpp:422-438, forms the frame
+ * mean of rho, phi and rho + phi at every site and writes the equilibrium_* files the reference-state noise consumes;
+ * NoiseCovariance.ipynb cell 3 takes the per-site variance of the noise moments over 200 frames).  The mode and spectrum
+ * traces give statistics in k-space, the ensemble trace 12 numbers per lattice; this gives <x>(site) and <x y>(site).
+ * A field statistic is an accumulator in the sense of the ensemble structure factors: unbounded capacity, every = 0 means
+ * fed by bflbm_fstat_sample only.  It is attached to one lone single-slab context, one replica batch or one ring.
+ *  - definition (stated here and nowhere else).  Inputs: a source (0: hydrovs, 22 components; 1: hydrovsbar, 9
+ *    components; 2: the noise moments of bflbm_get_noise, 38 components, 0..18 of fluid f, 19..37 of fluid g), nvars in
+ *    1..8 distinct component indices of that source, and npairs in 0..16 pairs (a, b) of variable SLOTS (positions in the
+ *    variable list), a == b allowed.  For every replica and site, with x_v(t) the value of variable v in frame
+ *    t = 0 .. N-1, the frames in recording order:
+ *      first[v] = x_v(0)
+ *      sum[v]   = ((x_v(0) + x_v(1)) + x_v(2)) + ...                          a plain sequential sum
+ *      prod[p]  = sum over t, in order and starting from +0.0, of (x_a(t) - first[a]) * (x_b(t) - first[b])
+ *    the product formed first and then added, never contracted (-ffp-contract=off); frame 0 contributes +0.0.
+ *    Derived when read, N the number of frames:
+ *      mean[v] = sum[v] * (1.0 / N)              the arithmetic of PrintConvergence's mean followed by mult(1./Nsteps)
+ *      cov[p]  = prod[p] * (1.0 / N) - (mean[a] - first[a]) * (mean[b] - first[b])
+ *    The shift by the first frame is there so that a fluctuation of 1e-3 around a density of 1 does not lose six digits
+ *    in the difference of two numbers near 1; it changes no covariance in exact arithmetic.  cov is the covariance with
+ *    the divisor N.  The raw second moment about zero is cov + mean[a] mean[b], not prod / N.
+ *    Ensemble values of a batch of B replicas (replica = -1): mean is the replicas' sum added in the order 0 ... B-1
+ *    starting from 0, times 1.0 / (B N); cov is the replicas' cov, each around its own replica's mean, added in the order
+ *    0 ... B-1 starting from 0, times 1.0 / B: the mean WITHIN-replica covariance, not the covariance of the pooled
+ *    frames.  sum, first and prod have no ensemble form.
+ *    analysis.field_statistics restates all of this in numpy, operation for operation.
+ *  - how a sample is taken, on the owner's stream and without a host synchronisation: the accumulators' observation (a
+ *    lone context and every slab of a ring: into the scratch state buffer, hydrovs and noise after the density pass and
+ *    the reference-state preparation of bflbm_sf_accumulate / bflbm_ring_sf_accumulate, which sums the centre of mass on
+ *    the host while reference-state noise is active; a batch: one launch over all replicas, only the chosen variables,
+ *    into a buffer of the recorder), then ONE accumulation launch over the dense sites: a thread takes two neighbouring
+ *    sites per turn (16-byte accesses where a volume is 16-byte aligned, a scalar tail where the site count is odd),
+ *    loads the chosen variables once, updates sum, writes first on frame 0 and updates every prod.  Whether a frame is
+ *    frame 0 is decided on the host.  The kernel is compiled once per number of variables; no atomics, no LDS, no
+ *    scratch.  Every value depends on the site's own frames alone: not on the launch geometry, the number of replicas,
+ *    the slab count, `every` or what else is attached.
+ *  - storage: (2 nvars + npairs) x B x n doubles, n the sites, beside one download buffer of n doubles and a batch's dense
+ *    fields B x nvars x n.  On a ring every slab keeps the accumulators of its own planes on its own device and feeds
+ *    them on its own stream; a sample needs no event between the slabs.  This is the one recorder whose records do not
+ *    live on slab 0.
+ *  - what is touched on the owner: what the observation touches.  Observing hydrovs rewrites rho / phi by the density
+ *    pass where they are stale; a context's scratch state buffer is overwritten (between steps it holds nothing the
+ *    next step reads).  The resident state, the step counters and everything the owner computes are unchanged.
+ *  - sampling rule: that of the ensemble structure factors.  every >= 1: a frame after each step through the owner
+ *    (bflbm_step and the split-step calls, bflbm_batch_step, bflbm_ring_step) at which the count of steps since creation or
+ *    reset is a multiple of `every`; recorders are served in creation order.  bflbm_fstat_sample takes a frame of the
+ *    resident state now and does not move the count.  bflbm_fstat_reset sets N = 0 and restarts the count: the next frame
+ *    is frame 0 again and overwrites every accumulator.  An owner may carry any number of field statistics.
+ *  - bflbm_fstat_get(s, what, index, replica, dst): what 0 sum, 1 mean, 2 first, 3 prod, 4 cov; index a variable slot for
+ *    0, 1, 2 and a pair index for 3, 4; replica 0 .. B-1, or -1 for the ensemble value (what 1 and 4 only; a lone context and a
+ *    ring have B = 1); dst[nz][ny][nx] of the whole
+ *    lattice.  One small kernel forms mean, cov and the ensemble values into the download buffer; a ring is gathered slab
+ *    by slab.
+ *  - refused (non-zero return, a message naming the call, before any launch, nothing allocated, the owner's recorder list
+ *    untouched): null arguments, a source outside 0..2, nvars outside 1..8, npairs outside 0..16, a component index
+ *    outside the source, a repeated variable, a pair slot outside 0..nvars-1, every < 0, source 2 on a batch (its
+ *    observation has no noise form), a replica view (use bflbm_batch_fstat_create), a context with nranks > 1, an open
+ *    step, a failed allocation (the message gives the bytes).  In bflbm_fstat_get: what outside 0..4, an index or replica
+ *    out of range, replica -1 with what other than 1 and 4, N = 0.  An open step also refuses _sample, _reset and _get.
+ *  - lifetime: the recorder owns its buffers.  Destroying the owner first detaches it: bflbm_fstat_get, _count, _reset
+ *    and _destroy still work, bflbm_fstat_sample fails.
+ *  - only bflbm_fstat_get and bflbm_fstat_destroy synchronise the owner's stream (a ring: every slab's).
+ *  - a ring of one slab gets the lone recorder of its only context. */
+typedef struct bflbm_fstat bflbm_fstat;
+int bflbm_fstat_create(bflbm_ctx* c, int source, int nvars, const int* vars, int npairs, const int* pair_a /* or NULL if npairs == 0 */,
+                       const int* pair_b, int every, bflbm_fstat** out);
+int bflbm_batch_fstat_create(bflbm_batch* b, int source, int nvars, const int* vars, int npairs, const int* pair_a, const int* pair_b,
+                             int every, bflbm_fstat** out);
+int bflbm_ring_fstat_create(bflbm_ring* r, int source, int nvars, const int* vars, int npairs, const int* pair_a, const int* pair_b,
+                            int every, bflbm_fstat** out);
+int bflbm_fstat_destroy(bflbm_fstat* s);
+int bflbm_fstat_sample(bflbm_fstat* s);                    /* take a frame of the resident state now (e.g. frame 0) */
+int bflbm_fstat_reset(bflbm_fstat* s);                     /* N = 0, restart the every-count: the next frame is frame 0 */
+int bflbm_fstat_count(const bflbm_fstat* s, long long* nsamples, int* nreplicas);
+int bflbm_fstat_get(bflbm_fstat* s, int what, int index, int replica, double* dst /* [nz][ny][nx] */);
+
 /* Materialise the per-step fields the reference keeps in MultiFabs, for the state
  * after the last completed step:
  *   hydrovsbar comps 0..8  (LBM_hydrovars_density, LBM_binary.H:315-354)
