@@ -421,6 +421,129 @@ def field_statistics_ensemble(replicas):
     return dict(mean=total * (1.0 / (b * float(reps[0]["N"]))), cov=cov * (1.0 / b))
 
 
+# ---- plane profiles: the numpy restatement of the profile trace (include/bflbm.h, "Profile traces") and the pressure profile ----
+PROFILE_TILE, PROFILE_LANES, PROFILE_CHUNK = 2048, 64, 64      # what bflbm_profile_geometry reports per axis z, y, x
+
+
+def _tree(v):
+    """v[..., t] += v[..., t + w], w = n/2 ... 1, over the last axis (a power of two wide); the entry 0."""
+    v = v.copy()
+    w = v.shape[-1] // 2
+    while w:
+        v[..., :w] = v[..., :w] + v[..., w:2 * w]
+        w //= 2
+    return v[..., 0]
+
+
+def plane_profiles(fields, pairs=(), axis=2):
+    """sums[Q, n_a] of include/bflbm.h, "Profile traces", in numpy, operation for operation and in the header's order:
+    fields[nvars, nz, ny, nx], pairs a list of (a, b) variable slots, axis 0 (x), 1 (y), 2 (z) or "x", "y", "z".  Entry
+    (q, i): the sum over the lattice plane i normal to the axis of variable q, or of the product of the pair q - nvars."""
+    x = np.asarray(fields, dtype=np.float64)
+    axis = {"x": 0, "y": 1, "z": 2}.get(axis, axis)
+    if x.ndim != 4 or axis not in (0, 1, 2):
+        raise ValueError(f"plane_profiles: fields[nvars, nz, ny, nx] and an axis in 0..2, got {x.shape} and {axis!r}")
+    nv, nz, ny, nx = x.shape
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    if any(not (0 <= a < nv and 0 <= b < nv) for a, b in pairs):
+        raise ValueError(f"plane_profiles: a pair slot outside the {nv} variables: {pairs}")
+    terms = np.concatenate([x] + [(x[a] * x[b])[None] for a, b in pairs], axis=0)        # [Q, nz, ny, nx]
+    nq = len(terms)
+    if axis == 2:
+        tiles = (nx * ny + PROFILE_TILE - 1) // PROFILE_TILE
+        padded = np.zeros((nq, nz, tiles * PROFILE_TILE))
+        padded[..., :nx * ny] = terms.reshape(nq, nz, nx * ny)
+        padded = padded.reshape(nq, nz, tiles, PROFILE_TILE // 256, 256)
+        acc = np.zeros((nq, nz, tiles, 256))
+        for k in range(PROFILE_TILE // 256):               # thread t: the sites t, t + 256, ...
+            acc = acc + padded[..., k, :]
+        part = _tree(acc)                                  # [Q, nz, tiles]
+        out = np.zeros((nq, nz))
+        for t in range(tiles):
+            out = out + part[..., t]
+        return out
+    if axis == 1:
+        turns = (nx + PROFILE_LANES - 1) // PROFILE_LANES
+        padded = np.zeros((nq, nz, ny, turns * PROFILE_LANES))
+        padded[..., :nx] = terms
+        padded = padded.reshape(nq, nz, ny, turns, PROFILE_LANES)
+        acc = np.zeros((nq, nz, ny, PROFILE_LANES))
+        for k in range(turns):                             # lane l: x = l, l + 64, ...
+            acc = acc + padded[..., k, :]
+        part = _tree(acc)                                  # [Q, nz, ny]
+    else:
+        part = np.zeros((nq, nz, nx))
+        for c0 in range(0, ny, PROFILE_CHUNK):
+            chunk = np.zeros((nq, nz, nx))
+            for y in range(c0, min(c0 + PROFILE_CHUNK, ny)):
+                chunk = chunk + terms[:, :, y, :]
+            part = part + chunk                            # the chunks in order
+    out = np.zeros((nq, part.shape[-1]))
+    for z in range(nz):                                    # the planes in sequence, as the last step
+        out = out + part[:, z]
+    return out
+
+
+PRESSURE_VARIABLES = ["rho", "phi", "afx", "afy", "afz", "agx", "agy", "agz"]
+PRESSURE_PAIRS = [("rho", "phi"), ("afx", "agx"), ("afy", "agy"), ("afz", "agz")]
+
+
+def pressure_profile_inputs():
+    """(variables, pairs) a profile trace must record for pressure_profile: the 8 hydrovs variables rho, phi, af*, ag*
+    and the 4 pairs rho phi, afx agx, afy agy, afz agz, by name."""
+    return list(PRESSURE_VARIABLES), list(PRESSURE_PAIRS)
+
+
+def pressure_profile(means, names, alpha0, cs2=1.0 / 3.0, axis=2, pairs=None):
+    """The static part of the pressure tensor of Surface_Tension.ipynb (cell 2) with G = alpha0, from plane means
+    [..., Q, n_a] of a profile trace along `axis` (the normal) whose variables are `names` and whose pairs are `pairs`
+    ((a, b) of names or slots; None: those of pressure_profile_inputs, in that order):
+        p_bulk      = cs2 (<rho> + <phi>) + alpha0 cs2 <rho phi>
+        pn_minus_pt = -( <af_n ag_n> - 1/2 (<af_t1 ag_t1> + <af_t2 ag_t2>) ) / alpha0
+    with af = -cs2 alpha0 grad phi, ag = -cs2 alpha0 grad rho, so that pn_minus_pt = -alpha0 cs2^2 (d_n rho d_n phi -
+    1/2 sum_t d_t rho d_t phi).  The kinetic rho u u part is not included.  Returns (p_bulk, pn_minus_pt), each
+    [..., n_a]."""
+    m = np.asarray(means, dtype=np.float64)
+    axis = {"x": 0, "y": 1, "z": 2}.get(axis, axis)
+    if axis not in (0, 1, 2):
+        raise ValueError(f"pressure_profile: axis {axis!r}, expected 0..2")
+    if alpha0 == 0:
+        raise ValueError("pressure_profile: alpha0 == 0 (no interaction: the tensor has no gradient part)")
+    names = list(names)
+    pairs = list(PRESSURE_PAIRS if pairs is None else pairs)
+    if m.ndim < 2 or m.shape[-2] != len(names) + len(pairs):
+        raise ValueError(f"pressure_profile: means[..., Q, n_a] with Q = {len(names)} variables + {len(pairs)} pairs, got {m.shape}")
+
+    def slot(v):
+        if not isinstance(v, str):
+            return int(v)
+        if v not in names:
+            raise ValueError(f"pressure_profile: the mean of {v!r} is missing (recorded: {names})")
+        return names.index(v)
+
+    have = {tuple(sorted((slot(a), slot(b)))): len(names) + k for k, (a, b) in enumerate(pairs)}
+
+    def mean_of(a, b=None):
+        if b is None:
+            return m[..., slot(a), :]
+        key = tuple(sorted((slot(a), slot(b))))
+        if key not in have:
+            raise ValueError(f"pressure_profile: the mean of {a} {b} is missing (recorded pairs: {pairs})")
+        return m[..., have[key], :]
+
+    d = "xyz"
+    n, t1, t2 = d[axis], d[(axis + 1) % 3], d[(axis + 2) % 3]
+    p_bulk = cs2 * (mean_of("rho") + mean_of("phi")) + alpha0 * cs2 * mean_of("rho", "phi")
+    pn_minus_pt = -(mean_of("af" + n, "ag" + n) - 0.5 * (mean_of("af" + t1, "ag" + t1) + mean_of("af" + t2, "ag" + t2))) / alpha0
+    return p_bulk, pn_minus_pt
+
+
+def mechanical_surface_tension(pn_minus_pt, interfaces=2):
+    """gamma = integral (P_N - P_T) dn as the plain sum over the last axis (lattice spacing 1), divided by the number of
+    interfaces the periodic box holds (2 for a stripe)."""
+    return np.asarray(pn_minus_pt, dtype=np.float64).sum(axis=-1) / float(interfaces)
+
+
 def com_from_moments(m, n, weighted=False):
     """Centre of mass in unit-box cell-centre coordinates; weighted=True is the reference's C++ getCenterOfMass
     (trapezoid weights, LBM_hydrovs.H:62-113), False the notebooks' plain sum."""

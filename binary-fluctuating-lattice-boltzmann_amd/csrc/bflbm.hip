@@ -1740,3 +1740,4 @@ int bflbm_fused_plan_query(const int n[3], int nreplicas, int noise, int compute
 #include "bflbm_spectrum_ring.h"
 #include "bflbm_modes.h"
 #include "bflbm_fstat.h"
+#include "bflbm_profile.h"

@@ -1,0 +1,495 @@
+// bflbm_profile.h -- profile traces: the sums of chosen hydrovs or hydrovsbar components, and of chosen products of
+// them, over every lattice plane normal to one axis, recorded on the device as a time series for a lone single-slab
+// context, every replica of a batch or a ring of z-slabs (include/bflbm.h, "Profile traces": the definition and the
+// order of every sum are stated there and only there).  rho(z) and phi(z) across a flat interface and the
+// normal-minus-tangential pressure -(af_n ag_n - af_t ag_t) / alpha0, whose integral is the mechanical surface tension,
+// are plane means; without this a user downloads 22 fields per replica and sample and averages them on the host.
+// A sample is, on the owner's stream(s) and without a host synchronisation,
+//   the accumulators' observation   batch_observe_launch into the trace's [B][nsel][n] / observe_launch into the
+//                                   scratch state buffer of the context (of every slab of a ring),
+//   k_profile_planes<NV>            stage 1, grid (work items of a plane, planes, replicas): a site's variables are
+//                                   loaded once, the products are formed in registers, one partial per (q, work item):
+//                                   [replica][z][q][W], W the tiles of a plane (axis z), ny (axis y) or nx (axis x),
+//   k_profile_finish                stage 2: the tiles of a plane in order (axis z) or the planes in sequence (axes x, y),
+//                                   straight into the slot.
+// A ring: stage 1 on every slab's stream over its own planes into [nzl][q][W]; slab 0 takes the other slabs' blocks
+// with one contiguous peer copy each in global plane order (the scheme of bflbm_trace.h), the unchanged stage 2 runs on
+// slab 0.  No atomics, no scratch.  Not built on purpose: reading the populations in stage 1 to skip the dense
+// intermediate (hydrovs needs the gradient stencil the observation already has), fusing the sums into the observation
+// kernels (it would give every observer a second form), the kinetic rho u u part of the tensor as a built-in (the
+// caller's own pairs give it).
+// The lifecycle and the sample store are those of bflbm_recorder.h.  Included by bflbm.hip after bflbm_fstat.h (needs
+// bflbm_ctx, bflbm_batch, bflbm_ring, ObsSel, batch_observe_launch, observe_launch, ring_prepare_ref, FstatVars,
+// FstatPairs, fstat_pick, fstat_aligned).
+#ifndef BFLBM_PROFILE_H_
+#define BFLBM_PROFILE_H_
+
+#include <memory>
+#include <string>
+#include <vector>
+
+namespace profile_limits {
+constexpr int kMaxVars = fstat_limits::kMaxVars, kMaxPairs = fstat_limits::kMaxPairs;
+constexpr int kTile = 2048;          // axis z: sites per workgroup, 8 per thread, as the mode trace.  An untimed heuristic.
+constexpr int kPerThread = kTile / 256;
+constexpr int kLanes = 64;           // axis y: the lanes that stride a row (one wave per row)
+constexpr int kChunk = 64;           // axis x: rows per chunk of a column
+}
+
+struct bflbm_profile : bflbm_sample_store {   // d_rec [capacity][nrep][nq][na], d_stage [nrep][nz][nq][W]
+  int nx = 0, ny = 0, nz = 0;
+  long long nsites = 0;
+  int source = 0;                   // 0 hydrovs, 1 hydrovsbar
+  int axis = 2, na = 0;             // the axis and its extent
+  int nvars = 0, nq = 0;            // nq = nvars + npairs
+  int W = 0;                        // partials per (q, plane) that stage 1 leaves
+  int ncomp = 0;                    // a context: the components its observation produces
+  ObsSel sel;                       // a batch: what the observation writes
+  FstatVars vol;                    // the volume of every variable: a batch's slot, a context's component
+  FstatPairs pairs;
+  double* fields = nullptr;         // a batch: [nrep][nvars][nsites]
+  // a ring: what slab k > 0 holds on its device (slab 0 writes d_stage itself; part[0] stays empty)
+  struct Part { int device = 0; double* partial = nullptr; hipEvent_t done = nullptr; };   // [nzl][nq][W]; stage 1 is complete
+  std::vector<Part> part;
+  hipEvent_t taken = nullptr;       // slab 0 has copied every slab's block
+  bflbm_profile() : bflbm_sample_store("profile trace", "bflbm_profile") {}
+  ~bflbm_profile() override {
+    for (Part& q : part) {
+      if (!q.partial && !q.done) continue;
+      hipSetDevice(q.device);
+      if (q.partial) hipFree(q.partial);
+      if (q.done) hipEventDestroy(q.done);
+    }
+    if (fields || taken) hipSetDevice(device);
+    if (fields) hipFree(fields);
+    if (taken) hipEventDestroy(taken);
+  }
+  int record() override;
+  int record_ring();
+  int stage1(const double* dense, long long rep_stride, long long comp_stride, double* partial, int planes, int reps, hipStream_t stream) const;
+};
+
+namespace {
+
+// one site (W = 1) into the accumulators: the variables, then every pair, the product formed first and then added.  The
+// loop over the pairs is unrolled to its limit, so every accumulator has a compile-time index and stays in a register;
+// the slots are uniform and picked by selects.
+template <int NV, int W>
+__device__ __forceinline__ void profile_add(double (&acc)[NV + profile_limits::kMaxPairs][W], const double (&x)[NV][W], const FstatPairs& P) {
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+#pragma unroll
+    for (int i = 0; i < W; ++i) acc[v][i] += x[v][i];
+  }
+#pragma unroll
+  for (int p = 0; p < profile_limits::kMaxPairs; ++p) {
+    if (p < P.n) {
+      double a[W], b[W];
+      fstat_pick<NV, W>(x, P.a[p], a);
+      fstat_pick<NV, W>(x, P.b[p], b);
+#pragma unroll
+      for (int i = 0; i < W; ++i) { const double q = a[i] * b[i]; acc[NV + p][i] += q; }
+    }
+  }
+}
+
+// The values a lane adds in two consecutive turns: entries s and s + stride of p, 0 past `limit`.  The lanes 2 k and
+// 2 k + 1 sit on neighbouring entries in both turns.  Where p is 16-byte aligned and both turns lie inside, the even
+// lane loads the pair of the first turn and the odd lane the pair of the second with one 16-byte access each, and the
+// two swap halves; otherwise two 8-byte loads.  `odd`: the lane's parity, which is the parity of s.  Every lane of the
+// wave calls this together.
+__device__ __forceinline__ void profile_two_turns(const double* __restrict__ p, bool aligned, int s, int odd, int stride, int limit,
+                                                  double& first, double& second) {
+  const int se = s - odd;
+  const bool wide = aligned && se + stride + 1 < limit;
+  double2 m = make_double2(0., 0.);
+  if (wide) m = *reinterpret_cast<const double2*>(p + (odd ? se + stride : se));
+  const double got = __shfl_xor(odd ? m.x : m.y, 1);
+  if (wide) { first = odd ? got : m.x; second = odd ? m.y : got; }
+  else { first = s < limit ? p[s] : 0.; second = s + stride < limit ? p[s + stride] : 0.; }
+}
+
+// axis z, grid.x = tiles: thread t adds the sites t, t + 256, ... of its tile, the tree of block_sum over the 256 sums
+// (levels 128 and 64 through LDS, the rest by lane shifts in wave 0).  vol[v]: variable v on this plane; out: [nq][tiles].
+template <int NV>
+__device__ __forceinline__ void profile_plane_z(const double* (&vol)[NV], int plane, const FstatPairs& P, int nq,
+                                                double* __restrict__ out, double* __restrict__ sh) {
+  using namespace profile_limits;
+  constexpr int NQ = NV + kMaxPairs;
+  const int tid = (int)threadIdx.x, odd = tid & 1;
+  const int s0 = (int)blockIdx.x * kTile + tid;
+  double acc[NQ][1];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) acc[q][0] = 0.;
+  bool al[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) al[v] = fstat_aligned(vol[v]);
+#pragma unroll
+  for (int i = 0; i < kPerThread; i += 2) {
+    double x0[NV][1], x1[NV][1];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) profile_two_turns(vol[v], al[v], s0 + 256 * i, odd, 256, plane, x0[v][0], x1[v][0]);
+    profile_add<NV, 1>(acc, x0, P);
+    profile_add<NV, 1>(acc, x1, P);
+  }
+  double* __restrict__ xa = sh;                          // [NQ][128]: waves 2, 3 to waves 0, 1
+  double* __restrict__ xb = sh + NQ * 128;               // [NQ][64]: wave 1 to wave 0
+  if (tid >= 128) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) if (q < nq) xa[q * 128 + tid - 128] = acc[q][0];
+  }
+  __syncthreads();
+  if (tid < 128) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) if (q < nq) acc[q][0] += xa[q * 128 + tid];
+    if (tid >= 64) {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) if (q < nq) xb[q * 64 + tid - 64] = acc[q][0];
+    }
+  }
+  __syncthreads();
+  if (tid < 64) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      if (q < nq) {
+        double v = acc[q][0] + xb[q * 64 + tid];
+#pragma unroll
+        for (int w = 32; w > 0; w >>= 1) v += __shfl_down(v, w);
+        if (tid == 0) out[(long long)q * gridDim.x + blockIdx.x] = v;
+      }
+    }
+  }
+}
+
+// axis y, grid.x = ceil(ny / 4): one wave per row; lane l adds x = l, l + 64, ..., then the tree w = 32 .. 1 by lane
+// shifts.  out: [nq][ny].
+template <int NV>
+__device__ __forceinline__ void profile_plane_y(const double* (&vol)[NV], int nx, int ny, const FstatPairs& P, int nq,
+                                                double* __restrict__ out) {
+  using namespace profile_limits;
+  constexpr int NQ = NV + kMaxPairs;
+  const int lane = (int)threadIdx.x & 63, odd = lane & 1;
+  const int y = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+  if (y >= ny) return;                                   // the whole wave
+  double acc[NQ][1];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) acc[q][0] = 0.;
+  const double* row[NV];
+  bool al[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) { row[v] = vol[v] + (long long)y * nx; al[v] = fstat_aligned(row[v]); }
+  const int turns = (nx + kLanes - 1) / kLanes;
+  int k = 0;
+  for (; k + 1 < turns; k += 2) {
+    double x0[NV][1], x1[NV][1];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) profile_two_turns(row[v], al[v], lane + kLanes * k, odd, kLanes, nx, x0[v][0], x1[v][0]);
+    profile_add<NV, 1>(acc, x0, P);
+    profile_add<NV, 1>(acc, x1, P);
+  }
+  if (k < turns) {
+    const int x = lane + kLanes * k;
+    double x0[NV][1];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) x0[v][0] = x < nx ? row[v][x] : 0.;
+    profile_add<NV, 1>(acc, x0, P);
+  }
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    if (q < nq) {
+      double v = acc[q][0];
+#pragma unroll
+      for (int w = 32; w > 0; w >>= 1) v += __shfl_down(v, w);
+      if (lane == 0) out[(long long)q * ny + y] = v;
+    }
+  }
+}
+
+// axis x, grid.x = ceil(nx / 64): lane l owns column x = 64 blockIdx.x + l (8-byte loads, a wave reads 512 contiguous
+// bytes of a row); the four waves take the chunks c = w, w + 4, ... of 64 rows, each added sequentially in y from 0;
+// per round of four chunks the waves 1 .. 3 hand theirs to wave 0 through LDS, which adds the chunks in order.  A chunk
+// past the plane hands over +0.0, which changes no sum that started from +0.0.  out: [nq][nx].
+template <int NV>
+__device__ __forceinline__ void profile_plane_x(const double* (&vol)[NV], int nx, int ny, const FstatPairs& P, int nq,
+                                                double* __restrict__ out, double* __restrict__ sh) {
+  using namespace profile_limits;
+  constexpr int NQ = NV + kMaxPairs;
+  const int lane = (int)threadIdx.x & 63, w = (int)threadIdx.x >> 6;
+  const int x = (int)blockIdx.x * 64 + lane;
+  const int nchunks = (ny + kChunk - 1) / kChunk;
+  double total[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) total[q] = 0.;
+  for (int c0 = 0; c0 < nchunks; c0 += 4) {
+    double acc[NQ][1];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q][0] = 0.;
+    const int c = c0 + w;
+    if (c < nchunks && x < nx) {
+      const int y1 = min(ny, (c + 1) * kChunk);
+#pragma unroll 4
+      for (int y = c * kChunk; y < y1; ++y) {
+        double x0[NV][1];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) x0[v][0] = vol[v][(long long)y * nx + x];
+        profile_add<NV, 1>(acc, x0, P);
+      }
+    }
+    if (w > 0) {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) if (q < nq) sh[((w - 1) * NQ + q) * 64 + lane] = acc[q][0];
+    }
+    __syncthreads();
+    if (w == 0) {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        if (q < nq) {
+          total[q] += acc[q][0];
+#pragma unroll
+          for (int u = 0; u < 3; ++u) total[q] += sh[(u * NQ + q) * 64 + lane];
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (w == 0 && x < nx) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) if (q < nq) out[(long long)q * nx + x] = total[q];
+  }
+}
+
+// Stage 1, grid (work items of a plane, planes, replicas), 256 threads.  fields: the dense volumes, variable v of
+// replica r at fields + r rep_stride + V.vol[v] comp_stride, [planes][ny][nx]; partial: [replica][plane][nq][W].  NV, the
+// number of variables, is a template parameter: the site values and the accumulators are register arrays of that size.
+template <int NV>
+__global__ void __launch_bounds__(256) k_profile_planes(const double* __restrict__ fields, long long rep_stride, long long comp_stride,
+                                                        double* __restrict__ partial, int nx, int ny, int axis, int W,
+                                                        FstatVars V, FstatPairs P) {
+  __shared__ double sh[(NV + profile_limits::kMaxPairs) * 192];
+  const int plane = nx * ny, nq = NV + P.n;
+  const double* vol[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v)
+    vol[v] = fields + (long long)blockIdx.z * rep_stride + (long long)V.vol[v] * comp_stride + (long long)blockIdx.y * plane;
+  double* __restrict__ out = partial + ((long long)blockIdx.z * gridDim.y + blockIdx.y) * ((long long)nq * W);
+  if (axis == 2) profile_plane_z<NV>(vol, plane, P, nq, out, sh);
+  else if (axis == 1) profile_plane_y<NV>(vol, nx, ny, P, nq, out);
+  else profile_plane_x<NV>(vol, nx, ny, P, nq, out, sh);
+}
+
+// Stage 2, grid (ceil(nq na / 256), replicas): thread (q, i) adds, starting from 0, the W tiles of plane i in tile
+// order (axis z) or entry i of the planes z = 0 .. nz-1 in sequence (axes x, y).  out = the slot of replica 0.
+__global__ void __launch_bounds__(256) k_profile_finish(const double* __restrict__ partial, double* __restrict__ out,
+                                                        int axis, int nz, int nq, int W, int na) {
+  const int g = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  if (g >= nq * na) return;
+  const int q = g / na, i = g - q * na;
+  const double* __restrict__ mine = partial + (long long)blockIdx.y * nz * nq * W;
+  double s = 0.;
+  if (axis == 2) {
+    const double* __restrict__ p = mine + ((long long)i * nq + q) * W;
+    for (int t = 0; t < W; ++t) s += p[t];
+  } else {
+    const double* __restrict__ p = mine + (long long)q * W + i;
+    for (int z = 0; z < nz; ++z) s += p[(long long)z * nq * W];
+  }
+  out[((long long)blockIdx.y * nq + q) * na + i] = s;
+}
+
+// what every creation call refuses about its own arguments
+int profile_refuse_args(const char* call, int source, int axis, int nvars, const int* vars, int npairs, const int* pair_a, const int* pair_b,
+                        int every, long long capacity) {
+  using namespace profile_limits;
+  if (source < 0 || source > 1) return fail("%s: source must be 0 (hydrovs) or 1 (hydrovsbar) (got %d)", call, source);
+  if (axis < 0 || axis > 2) return fail("%s: axis must be 0 (x), 1 (y) or 2 (z) (got %d)", call, axis);
+  if (nvars < 1 || nvars > kMaxVars) return fail("%s: 1..%d variables (got %d)", call, kMaxVars, nvars);
+  if (npairs < 0 || npairs > kMaxPairs) return fail("%s: 0..%d pairs (got %d)", call, kMaxPairs, npairs);
+  if (npairs > 0 && (!pair_a || !pair_b)) return fail("%s: null argument", call);
+  const int most = source ? BFLBM_NHYDROBAR : BFLBM_NHYDRO;
+  for (int i = 0; i < nvars; ++i) {
+    if (vars[i] < 0 || vars[i] >= most) return fail("%s: variable index %d outside %s (0..%d)", call, vars[i], source ? "hydrovsbar" : "hydrovs", most - 1);
+    for (int k = 0; k < i; ++k) if (vars[k] == vars[i]) return fail("%s: variable index %d given twice", call, vars[i]);
+  }
+  for (int p = 0; p < npairs; ++p)
+    for (int slot : {pair_a[p], pair_b[p]})
+      if (slot < 0 || slot >= nvars) return fail("%s: pair %d: slot %d outside the %d variables", call, p, slot, nvars);
+  return store_refuse_cadence(call, every, capacity);
+}
+
+int profile_create(bflbm_ctx* c, bflbm_batch* b, bflbm_ring* g, int source, int axis, int nvars, const int* vars, int npairs,
+                   const int* pair_a, const int* pair_b, int every, long long capacity, bflbm_profile** out) {
+  using namespace profile_limits;
+  const char* call = b ? "bflbm_batch_profile_create" : (g ? "bflbm_ring_profile_create" : "bflbm_profile_create");
+  if (profile_refuse_args(call, source, axis, nvars, vars, npairs, pair_a, pair_b, every, capacity)) return 1;
+  if (store_refuse_owner(c, call, "bflbm_batch_profile_create", "profile trace")) return 1;
+  if ((c && c->step_open()) || (g && ring_step_open(g))) return fail("%s inside an open step", call);
+  if (b) for (const bflbm_ctx* v : b->ctx) if (v->step_open()) return fail("%s: a replica has an open step", call);
+  const Geo& G = c ? c->G : (b ? b->G : g->ctx[0]->G);
+  if (G.nz > 65535) return fail("%s: nz = %d exceeds the 65535 planes of one launch", call, G.nz);
+
+  std::unique_ptr<bflbm_profile> t(new bflbm_profile());
+  recorder_bind(t.get(), c, b, every, g);
+  t->nx = G.nx; t->ny = G.ny; t->nz = G.nz; t->nsites = (long long)G.nx * G.ny * G.nz;
+  t->source = source; t->axis = axis; t->nvars = nvars; t->nq = nvars + npairs;
+  t->na = axis == 0 ? G.nx : (axis == 1 ? G.ny : G.nz);
+  t->W = axis == 2 ? (G.nx * G.ny + kTile - 1) / kTile : t->na;
+  // the batch observation writes the chosen variables in ascending order; a context's all components up to the largest
+  t->sel.mask = 0; t->sel.nsel = 0;
+  int top = 0;
+  for (int i = 0; i < nvars; ++i) { if (b) t->sel.mask |= 1u << vars[i]; top = std::max(top, vars[i]); }
+  for (int v = 0; v < BFLBM_NHYDRO_; ++v) t->sel.slot[v] = (t->sel.mask & (1u << v)) ? t->sel.nsel++ : 0;
+  t->ncomp = source ? BFLBM_NHYDROBAR : top + 1;
+  for (int i = 0; i < kMaxVars; ++i) t->vol.vol[i] = i < nvars ? (b ? t->sel.slot[vars[i]] : vars[i]) : 0;
+  t->pairs.n = npairs;
+  for (int p = 0; p < kMaxPairs; ++p) { t->pairs.a[p] = p < npairs ? pair_a[p] : 0; t->pairs.b[p] = p < npairs ? pair_b[p] : 0; }
+
+  const size_t per = (size_t)t->nrep * t->nq * t->na;
+  const size_t plane_doubles = (size_t)t->nq * t->W, stage = (size_t)t->nrep * G.nz * plane_doubles;
+  if ((unsigned long long)capacity > ((1ULL << 40) / sizeof(double)) / per)
+    return fail("%s: capacity %lld x %d replicas x %d sums x %d planes exceeds 1 TB of records", call, capacity, t->nrep, t->nq, t->na);
+  const size_t rb = (size_t)capacity * per * sizeof(double), sb = stage * sizeof(double);
+  const size_t fb = b ? (size_t)t->nrep * nvars * (size_t)t->nsites * sizeof(double) : 0;
+  size_t pb = 0;                                             // a ring: the largest slab's block
+  hipError_t e = hipSetDevice(t->device);
+  if (e == hipSuccess) e = hipMalloc((void**)&t->d_rec, rb);
+  if (e == hipSuccess) e = hipMalloc((void**)&t->d_stage, sb);
+  if (e == hipSuccess && fb) e = hipMalloc((void**)&t->fields, fb);
+  if (e == hipSuccess && g) {
+    e = hipEventCreateWithFlags(&t->taken, hipEventDisableTiming);
+    t->part.resize(g->ctx.size());
+    for (size_t k = 1; k < g->ctx.size() && e == hipSuccess; ++k) {
+      bflbm_profile::Part& q = t->part[k];
+      q.device = g->ctx[k]->dom.device;
+      const size_t nb = (size_t)g->ctx[k]->nzl * plane_doubles * sizeof(double);
+      pb = std::max(pb, nb);
+      e = hipSetDevice(q.device);
+      if (e == hipSuccess) e = hipMalloc((void**)&q.partial, nb);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&q.done, hipEventDisableTiming);
+    }
+  }
+  if (e != hipSuccess) {                                     // the destructor frees the rest; no list was touched
+    (void)hipGetLastError();
+    hipSetDevice(t->device);
+    if (t->d_rec) hipFree(t->d_rec);
+    if (t->d_stage) hipFree(t->d_stage);
+    return fail("%s: out of device memory (records %zu + plane partials %zu + fields %zu bytes, slab partials up to %zu): %s",
+                call, rb, sb, fb, pb, hipGetErrorString(e));
+  }
+  t->capacity = capacity; t->per = per;
+  recorder_list(t.get()).push_back(t.get());
+  *out = t.release();
+  return 0;
+}
+
+}  // namespace
+
+// the stage 1 launch over `planes` planes of `reps` replicas on `stream`
+int bflbm_profile::stage1(const double* dense, long long rep_stride, long long comp_stride, double* partial, int planes, int reps,
+                          hipStream_t stream) const {
+  using namespace profile_limits;
+  const unsigned items = axis == 2 ? (unsigned)W : (axis == 1 ? (unsigned)((ny + 3) / 4) : (unsigned)((nx + 63) / 64));
+  const dim3 grid(items, (unsigned)planes, (unsigned)reps);
+#define BFLBM_PROFILE_PLANES(NV) \
+  case NV: hipLaunchKernelGGL((k_profile_planes<NV>), grid, dim3(256), 0, stream, dense, rep_stride, comp_stride, partial, nx, ny, axis, W, vol, pairs); break
+  switch (nvars) {
+    BFLBM_PROFILE_PLANES(1); BFLBM_PROFILE_PLANES(2); BFLBM_PROFILE_PLANES(3); BFLBM_PROFILE_PLANES(4);
+    BFLBM_PROFILE_PLANES(5); BFLBM_PROFILE_PLANES(6); BFLBM_PROFILE_PLANES(7); BFLBM_PROFILE_PLANES(8);
+    default: return fail("profile trace: %d variables", nvars);
+  }
+#undef BFLBM_PROFILE_PLANES
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// enqueue the observation and the two stages of the resident state into slot n; no host synchronisation
+int bflbm_profile::record() {
+  if (ring) return record_ring();
+  if (store_begin(this)) return 1;
+  const hipStream_t stream = recorder_stream(this);
+  const double* dense;
+  long long rep_stride = 0;
+  if (batch) {
+    if (batch_observe_launch(batch, source ? 0 : 2, sel, fields, "profile trace sample")) return 1;
+    dense = fields; rep_stride = (long long)sel.nsel * nsites;
+  } else {
+    if (observe_launch(ctx, source ? 0 : 2, ncomp, "profile trace sample")) return 1;
+    dense = ctx->S[1 - ctx->cur];                      // [comp][z][y][x], as bflbm_sf_accumulate reads it
+  }
+  if (stage1(dense, rep_stride, nsites, d_stage, nz, nrep, stream)) return 1;
+  hipLaunchKernelGGL(k_profile_finish, dim3((unsigned)((nq * na + 255) / 256), (unsigned)nrep), dim3(256), 0, stream,
+                     d_stage, store_slot(this), axis, nz, nq, W, na);
+  HIP_TRY(hipGetLastError());
+  store_recorded(this);
+  return 0;
+}
+
+int bflbm_profile::record_ring() {
+  if (store_begin(this)) return 1;
+  if (source != 1 && ring_prepare_ref(ring)) return 1;     // the global centre of mass: the slabs' own prepare_ref is then a no-op
+  const int n = (int)ring->ctx.size();
+  const size_t per_plane = (size_t)nq * W;
+  const long long plane = (long long)nx * ny;
+  for (int k = 0; k < n; ++k) {
+    bflbm_ctx* c = ring->ctx[k];
+    if (observe_launch(c, source ? 0 : 2, ncomp, "profile trace sample")) return 1;   // selects the slab's device
+    if (k > 0) HIP_TRY(hipStreamWaitEvent(c->stream, taken, 0));       // slab 0 may still be copying the last sample's block
+    if (stage1(c->S[1 - c->cur], 0, (long long)c->nzl * plane, k > 0 ? part[k].partial : d_stage, c->nzl, 1, c->stream)) return 1;
+    if (k > 0) HIP_TRY(hipEventRecord(part[k].done, c->stream));
+  }
+  HIP_TRY(hipSetDevice(device));
+  const hipStream_t s0 = ring->ctx[0]->stream;
+  for (int k = 1; k < n; ++k) {
+    const bflbm_ctx* c = ring->ctx[k];
+    HIP_TRY(hipStreamWaitEvent(s0, part[k].done, 0));
+    HIP_TRY(hipMemcpyPeerAsync(d_stage + (size_t)c->dom.z0 * per_plane, device, part[k].partial, part[k].device,
+                               (size_t)c->nzl * per_plane * sizeof(double), s0));
+  }
+  HIP_TRY(hipEventRecord(taken, s0));
+  hipLaunchKernelGGL(k_profile_finish, dim3((unsigned)((nq * na + 255) / 256), 1), dim3(256), 0, s0,
+                     d_stage, store_slot(this), axis, nz, nq, W, na);
+  HIP_TRY(hipGetLastError());
+  store_recorded(this);
+  return 0;
+}
+
+extern "C" {
+
+int bflbm_profile_create(bflbm_ctx* c, int source, int axis, int nvars, const int* vars, int npairs, const int* pair_a, const int* pair_b,
+                         int every, long long capacity, bflbm_profile** out) {
+  if (!c || !vars || !out) return fail("bflbm_profile_create: null argument");
+  return profile_create(c, nullptr, nullptr, source, axis, nvars, vars, npairs, pair_a, pair_b, every, capacity, out);
+}
+int bflbm_batch_profile_create(bflbm_batch* b, int source, int axis, int nvars, const int* vars, int npairs, const int* pair_a, const int* pair_b,
+                               int every, long long capacity, bflbm_profile** out) {
+  if (!b || !vars || !out) return fail("bflbm_batch_profile_create: null argument");
+  return profile_create(nullptr, b, nullptr, source, axis, nvars, vars, npairs, pair_a, pair_b, every, capacity, out);
+}
+int bflbm_ring_profile_create(bflbm_ring* r, int source, int axis, int nvars, const int* vars, int npairs, const int* pair_a, const int* pair_b,
+                              int every, long long capacity, bflbm_profile** out) {
+  if (!r || !vars || !out) return fail("bflbm_ring_profile_create: null argument");
+  if (r->ctx.size() == 1)                                  // the whole box: the lone recorder of ctx[0], served by its steps
+    return profile_create(r->ctx[0], nullptr, nullptr, source, axis, nvars, vars, npairs, pair_a, pair_b, every, capacity, out);
+  return profile_create(nullptr, nullptr, r, source, axis, nvars, vars, npairs, pair_a, pair_b, every, capacity, out);
+}
+
+int bflbm_profile_destroy(bflbm_profile* t) { return store_destroy(t); }
+int bflbm_profile_sample(bflbm_profile* t) { return store_sample(t, "bflbm_profile"); }
+int bflbm_profile_reset(bflbm_profile* t) { return store_reset(t, "bflbm_profile"); }
+int bflbm_profile_count(const bflbm_profile* t, long long* nsamples, int* nreplicas) { return store_count(t, "bflbm_profile", nsamples, nreplicas); }
+int bflbm_profile_read(bflbm_profile* t, long long first, long long count, double* sums, long long* steps) {
+  return store_read(t, "bflbm_profile", first, count, sums, steps);
+}
+
+int bflbm_profile_geometry(const bflbm_profile* t, int* nsums, int* n_axis, int* tile_sites, int* tiles_per_plane) {
+  using namespace profile_limits;
+  if (!t) return fail("bflbm_profile_geometry: null argument");
+  if (nsums) *nsums = t->nq;
+  if (n_axis) *n_axis = t->na;
+  if (tile_sites) *tile_sites = t->axis == 2 ? kTile : (t->axis == 1 ? kLanes : kChunk);
+  if (tiles_per_plane) *tiles_per_plane = t->W;
+  return 0;
+}
+
+}  // extern "C"
+
+#endif  // BFLBM_PROFILE_H_

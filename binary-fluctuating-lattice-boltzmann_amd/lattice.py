@@ -490,6 +490,86 @@ class FieldStats(_Recorder):
         return self._get("prod", self._pair(p), replica)
 
 
+PROFILE_AXES = {"x": 0, "y": 1, "z": 2}
+
+
+class ProfileTrace(_Recorder):
+    """The sums of chosen hydrovs / hydrovsbar variables, and of chosen products of them, over every lattice plane normal
+    to one axis, for every replica, recorded on the device every `every` steps through the owner (a lone single-slab
+    BinaryLBM, a BatchLBM or a RingLBM) and read once: include/bflbm.h, "Profile traces"; analysis.plane_profiles is the
+    same arithmetic in numpy, analysis.pressure_profile turns the means into the pressure profile.  Made by
+    owner.profile_trace(); an owner may carry several.  Closing the owner detaches the trace: it stays readable until its
+    own close()."""
+    _abi = "bflbm_profile"
+
+    def __init__(self, owner, create, variables, pairs, axis, source, every, capacity):
+        if source not in ("hydrovs", "hydrovsbar", 0, 1):
+            raise ValueError(f"profile_trace: source {source!r}, expected 'hydrovs' (0) or 'hydrovsbar' (1)")
+        if axis not in PROFILE_AXES and axis not in PROFILE_AXES.values():
+            raise ValueError(f"profile_trace: axis {axis!r}, expected one of {sorted(PROFILE_AXES)} or 0..2")
+        self.source = int(FSTAT_SOURCES.get(source, source))
+        self.axis = int(PROFILE_AXES.get(axis, axis))
+        self.component_names = fstat_variable_names(self.source)
+        items = [variables] if isinstance(variables, (str, int, np.integer)) else list(variables)
+        self.variables = [self._component(v) for v in items]
+        self.pairs = [(self._slot(a), self._slot(b)) for a, b in [(p, p) if isinstance(p, str) else p for p in pairs]]   # a lone name: its square
+        nv, npairs = len(self.variables), len(self.pairs)
+        va = (ctypes.c_int * max(nv, 1))(*self.variables)
+        pa = (ctypes.c_int * max(npairs, 1))(*[p[0] for p in self.pairs])
+        pb = (ctypes.c_int * max(npairs, 1))(*[p[1] for p in self.pairs])
+        super().__init__(owner, create, self.source, self.axis, nv, va, npairs, pa, pb, int(every), int(capacity))
+        self.plane_sites = owner.n[0] * owner.n[1] * owner.n[2] // owner.n[self.axis]
+
+    @property
+    def names(self):
+        """The recorded variables by name, in slot order: what analysis.pressure_profile takes."""
+        return [self.component_names[c] if 0 <= c < len(self.component_names) else str(c) for c in self.variables]
+
+    def _component(self, v):
+        """A variable by name or by component index of the source."""
+        if not isinstance(v, str):
+            return int(v)
+        if v not in self.component_names:
+            raise ValueError(f"profile_trace: variable {v!r}, expected one of {self.component_names} or an index")
+        return self.component_names.index(v)
+
+    def _slot(self, v):
+        """A recorded variable by name or by slot (its position in the variable list)."""
+        if not isinstance(v, str):
+            return int(v)
+        c = self._component(v)
+        if c not in self.variables:
+            raise ValueError(f"profile_trace: {v!r} is not one of the recorded variables")
+        return self.variables.index(c)
+
+    def _owner_closing(self):
+        """The owner's close(): the library detaches the trace; its samples stay readable until close()."""
+        _unregister(self.owner, self)
+
+    def geometry(self):
+        """(Q = variables + pairs, planes along the axis, sites of a work item, partials per (q, plane)): what the
+        library built."""
+        v = [ctypes.c_int() for _ in range(4)]
+        check(self.lib.bflbm_profile_geometry(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def read(self, first=0, count=None):
+        """(sums[count, B, Q, n_a], steps[count, B] int64) of the samples first ... first + count - 1 (count None: all
+        from `first`); the variables first, then the pairs; synchronises the owner's stream."""
+        n, b = self._count()
+        count = n - int(first) if count is None else int(count)
+        nq, na = self.geometry()[:2]
+        steps = np.empty((max(count, 0), b), dtype=np.int64)
+        sums = np.empty((max(count, 0), b, nq, na))
+        check(self.lib.bflbm_profile_read(self._h, int(first), count, _ptr(sums), steps.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        return sums, steps
+
+    def means(self, first=0, count=None):
+        """sums / (sites of a plane) [count, B, Q, n_a]: the plane averages."""
+        return self.read(first, count)[0] / float(self.plane_sites)
+
+
+
 # kernel schedules of include/bflbm.h (bflbm_set_schedule): "fused" = plane march with the ring densities pulled
 # (bit-exact), "handover" = plane march with the ring densities handed over from the previous step (tolerance)
 SCHEDULES = {"two_pass": 0, "fused": 1, "fused_exact": 1, "auto": 2, "handover": 3}
@@ -742,6 +822,12 @@ class BinaryLBM(_DropletMixin):
         its variance): FieldStats.  A frame is taken after every `every`-th step; every = 0: by sample() only."""
         return FieldStats(self, "bflbm_fstat_create", variables, pairs, source, every)
 
+    def profile_trace(self, variables, pairs=(), axis="z", source="hydrovs", every=1, capacity=64):
+        """Record, after every `every`-th step, the sums over every lattice plane normal to `axis` ("x", "y", "z") of up
+        to 8 variables of `source` ("hydrovs" or "hydrovsbar"; names or component indices) and of the products of up to
+        16 pairs of them (names or slots; a lone name is its square): ProfileTrace."""
+        return ProfileTrace(self, "bflbm_profile_create", variables, pairs, axis, source, every, capacity)
+
     def com_sums(self):
         s = (ctypes.c_double * 4)()
         check(self.lib.bflbm_com_sums(self._h, s))
@@ -927,6 +1013,11 @@ class RingLBM(_DropletMixin):
         """Per-site means and covariances over frames (BinaryLBM.field_stats); every slab keeps the accumulators of its
         own planes on its own device, the values are a lone lattice's bit for bit."""
         return FieldStats(self, "bflbm_ring_fstat_create", variables, pairs, source, every)
+
+    def profile_trace(self, variables, pairs=(), axis="z", source="hydrovs", every=1, capacity=64):
+        """Plane sums of variables and products along one axis (BinaryLBM.profile_trace): every slab sums its own planes,
+        slab 0 finishes; the record is a lone lattice's bit for bit."""
+        return ProfileTrace(self, "bflbm_ring_profile_create", variables, pairs, axis, source, every, capacity)
 
     def _gather(self, ncomp, call):
         out = np.empty((ncomp, self.n[2], self.n[1], self.n[0]))
@@ -1122,6 +1213,11 @@ class BatchLBM:
         """Every replica's per-site means and covariances over frames (BinaryLBM.field_stats), with one observation launch
         and one accumulation launch per frame; replica=-1 reads the ensemble values.  No "noise" source on a batch."""
         return FieldStats(self, "bflbm_batch_fstat_create", variables, pairs, source, every)
+
+    def profile_trace(self, variables, pairs=(), axis="z", source="hydrovs", every=1, capacity=64):
+        """Every replica's plane sums along one axis (BinaryLBM.profile_trace) after every `every`-th batch step, with one
+        observation launch, one plane launch and one finishing launch per sample."""
+        return ProfileTrace(self, "bflbm_batch_profile_create", variables, pairs, axis, source, every, capacity)
 
     def structfact(self, var_names, **kw):
         """One structure-factor accumulator for the whole batch (structfact.BatchStructFact; every=k attaches it)."""

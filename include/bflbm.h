@@ -732,6 +732,82 @@ int bflbm_fstat_reset(bflbm_fstat* s);                     /* N = 0, restart the
 int bflbm_fstat_count(const bflbm_fstat* s, long long* nsamples, int* nreplicas);
 int bflbm_fstat_get(bflbm_fstat* s, int what, int index, int replica, double* dst /* [nz][ny][nx] */);
 
+/* ---- Profile traces: the sums of chosen fields, and of chosen products of them, over every lattice plane normal to one
+ * axis, recorded on the device as a time series and read once at the end.  The profile across a flat interface is what
+ * the reference's surface-tension work starts from: surface_tension_predict.ipynb (cell 9) averages rho and phi over
+ * the planes of a stripe box and compares rho(z) with its interface ODE, and Surface_Tension.ipynb (cell 2) derives the
+ * pressure tensor P_ab = [...] delta_ab - 1/2 G cs^4 (d_a rho d_b phi + d_a phi d_b rho), whose normal-minus-tangential
+ * part integrates to the surface tension.  hydrovs carries af = -cs2 alpha0 grad phi and ag = -cs2 alpha0 grad rho, so
+ * plane sums of af_a ag_a give that integrand with no new stencil (analysis.pressure_profile).  A profile trace is
+ * attached to one lone single-slab context, one replica batch or one ring.
+ *  - definition (stated here and nowhere else).  Inputs: a source (0: hydrovs, 22 components; 1: hydrovsbar, 9
+ *    components), nvars in 1..8 distinct component indices of that source, npairs in 0..16 pairs (a, b) of variable SLOTS
+ *    (positions in the variable list), a == b allowed, and an axis (0: x, 1: y, 2: z) of extent n_a.  With
+ *    Q = nvars + npairs, entry (q, i) of a sample is the sum, over the sites of the lattice plane with coordinate i along
+ *    the axis, of x_q for q < nvars and of x_a * x_b for the pair q - nvars: the product formed first and then added,
+ *    never contracted (-ffp-contract=off).  These are sums, not means: the reader divides by the plane's site count,
+ *    nx ny nz / n_a.  analysis.plane_profiles restates this in numpy, operation for operation and in the order below.
+ *  - order of the sums, fixed by the box and the axis alone.  Every sum starts from +0.0.  Stage 1 works per lattice
+ *    plane z, whatever the axis, on the dense plane (sites s = y nx + x):
+ *      axis z: the plane is cut into tiles of 2048 consecutive sites, the last one short.  Per (q, tile): thread t of 256
+ *        adds the terms of the tile's sites t, t + 256, ..., t + 1792 in that order (a site past the plane adds 0); the
+ *        256 sums are added by the binary tree v[t] += v[t + w], w = 128, 64, ..., 1.  One partial per (q, tile).
+ *      axis y: per (q, row y of the plane): lane l of 64 adds the terms of x = l, l + 64, ... in that order; the 64 sums
+ *        are added by the tree v[l] += v[l + w], w = 32, 16, ..., 1.  One partial per (q, y).
+ *      axis x: per (q, column x of the plane): the rows are cut into chunks of 64, the last one short; a chunk's terms are
+ *        added sequentially in y, and the chunks' sums are added in chunk order.  One partial per (q, x).
+ *    Stage 2: axis z adds the tiles of a plane in tile order; axes x and y add the planes' partials in the sequence
+ *    z = 0 .. nz-1, as the last step, so that a ring of z-slabs gives the same record.  No atomics.  A record does not
+ *    depend on the number of replicas, `every`, the capacity, the schedule, the slab count, what else is attached, or
+ *    lone context versus replica.  bflbm_profile_geometry reports Q, n_a, the sites of a work item (2048 for axis z, the
+ *    64 lanes for axis y, the 64 rows of a chunk for axis x) and the partials stage 1 leaves per (q, plane): the tiles
+ *    per plane for axis z, n_a for axes x and y.
+ *  - sample: [replica][q][n_a] doubles.
+ *  - how a sample is taken, on the owner's stream and without a host synchronisation: the accumulators' observation,
+ *    exactly as the mode trace takes it (a lone context and every slab of a ring: into the scratch state buffer; a batch:
+ *    one launch over all replicas, only the chosen variables, into a buffer of the trace); the plane kernel, grid (work
+ *    items of a plane) x planes x replicas, compiled once per number of variables: a site's variables are loaded once,
+ *    the products are formed in registers with the slots picked by selects; for axes z and y two neighbouring lanes
+ *    fetch two consecutive turns with one 16-byte load each and swap halves where the volume is 16-byte aligned and
+ *    both turns lie inside the plane (row), 8-byte loads otherwise and for axis x, where a lane owns a column; the first
+ *    two levels of axis z's tree and axis x's chunk sums pass through LDS (1536 (nvars + 16) bytes), the last six
+ *    levels and axis y's tree are lane shifts; then the finishing launch, one thread per (q, i), straight into the slot
+ *    [sample][replica].  No atomics, no scratch.  The tile, lane and chunk sizes are untimed heuristics.
+ *  - a ring of z-slabs: every slab runs stage 1 on its own stream over its own planes into [nzl][Q][W], W the partials
+ *    per (q, plane) above; slab 0 takes every other slab's block with one contiguous (peer) copy after that slab's
+ *    event, in global plane order, and the unchanged stage 2 runs on slab 0 (the ensemble trace's scheme).  With the
+ *    bit-exact schedules the record equals the lone lattice's bit for bit.  A ring of one slab gets the lone recorder of
+ *    its only context.  Slabs stepped by hand are not served.
+ *  - what is touched on the owner: what the mode trace's observation touches.  Observing hydrovs rewrites rho / phi by
+ *    the density pass where they are stale; a context's scratch state buffer is overwritten.  The resident state, the
+ *    step counters and everything the owner computes are unchanged.
+ *  - sampling rule, capacity, step labels, order among the recorders of one owner: those of the other traces ("profile
+ *    trace full").  An owner may carry any number of profile traces.
+ *  - refused at creation (non-zero return, a message naming the call, before any launch, nothing allocated, the owner's
+ *    recorder list untouched): null arguments, a source outside 0..1, an axis outside 0..2, nvars outside 1..8, npairs
+ *    outside 0..16, a repeated variable, a component index outside its source, a pair slot outside 0..nvars-1,
+ *    every < 1, capacity < 1, a capacity beyond 1 TB of records, nz > 65535, a replica view (use
+ *    bflbm_batch_profile_create), a context with nranks > 1, an open step, a failed allocation (the message gives the
+ *    bytes of each buffer).  An open step also refuses bflbm_profile_sample, _reset and _read.
+ *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_profile_read, _count,
+ *    _geometry and _destroy still work, bflbm_profile_sample fails.  bflbm_profile_destroy(NULL) returns 0.
+ *  - only bflbm_profile_read and bflbm_profile_destroy synchronise the owner's stream (a ring: destroy every slab's). */
+typedef struct bflbm_profile bflbm_profile;
+int bflbm_profile_create(bflbm_ctx* c, int source, int axis, int nvars, const int* vars, int npairs,
+                         const int* pair_a /* or NULL if npairs == 0 */, const int* pair_b, int every, long long capacity, bflbm_profile** out);
+int bflbm_batch_profile_create(bflbm_batch* b, int source, int axis, int nvars, const int* vars, int npairs,
+                               const int* pair_a, const int* pair_b, int every, long long capacity, bflbm_profile** out);
+int bflbm_ring_profile_create(bflbm_ring* r, int source, int axis, int nvars, const int* vars, int npairs,
+                              const int* pair_a, const int* pair_b, int every, long long capacity, bflbm_profile** out);
+int bflbm_profile_destroy(bflbm_profile* t);
+int bflbm_profile_sample(bflbm_profile* t);                /* record the resident state now (e.g. frame 0) */
+int bflbm_profile_reset(bflbm_profile* t);                 /* forget the samples, restart the every-counter */
+int bflbm_profile_count(const bflbm_profile* t, long long* nsamples, int* nreplicas);
+int bflbm_profile_geometry(const bflbm_profile* t, int* nsums /* Q */, int* n_axis, int* tile_sites, int* tiles_per_plane);
+int bflbm_profile_read(bflbm_profile* t, long long first, long long count,
+                       double* sums /* [count][nreplicas][Q][n_a] */,
+                       long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
+
 /* Materialise the per-step fields the reference keeps in MultiFabs, for the state
  * after the last completed step:
  *   hydrovsbar comps 0..8  (LBM_hydrovars_density, LBM_binary.H:315-354)
