@@ -544,6 +544,166 @@ def mechanical_surface_tension(pn_minus_pt, interfaces=2):
     return np.asarray(pn_minus_pt, dtype=np.float64).sum(axis=-1) / float(interfaces)
 
 
+# ---- radial shells: the numpy restatement of the radial trace (include/bflbm.h, "Radial traces") and the droplet route to
+# the surface tension of Surface_Tension.ipynb (pressure inside and outside, the Shan-Chen force integral, a radius) ----
+RADIAL_TILE, RADIAL_MAX_BINS = 256, 128                     # the sites of a tile; the most shells
+
+
+def _radial_slots(nv, pairs, radials, who):
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    rads = [(-1 if w is None else int(w), tuple(int(c) for c in v)) for w, v in radials]
+    if any(not (0 <= a < nv and 0 <= b < nv) for a, b in pairs):
+        raise ValueError(f"{who}: a pair slot outside the {nv} variables: {pairs}")
+    if any(not (-1 <= w < nv) or len(v) != 3 or any(not (0 <= c < nv) for c in v) for w, v in rads):
+        raise ValueError(f"{who}: a radial term (w, (vx, vy, vz)) with a slot outside the {nv} variables (w = -1 or None: none): {rads}")
+    return pairs, rads
+
+
+def radial_shells(fields, centre, delta, nbins, pairs=(), radials=()):
+    """(counts[nbins], sums[Q, nbins]) of include/bflbm.h, "Radial traces", in numpy, operation for operation and in the
+    header's order: fields[nvars, nz, ny, nx], centre (cx, cy, cz) in cell indices (a NaN puts every site in no shell),
+    shells of width delta, pairs a list of (a, b) variable slots, radials a list of (w, (vx, vy, vz)) variable slots with
+    w = None or -1 for the bare projection.  Q = nvars + pairs + radials.  An unbuffered np.add.at over the members of a
+    tile adds them sequentially in index order, which is the order of the definition."""
+    x = np.asarray(fields, dtype=np.float64)
+    c = np.asarray(centre, dtype=np.float64)
+    delta, nbins = float(delta), int(nbins)
+    if x.ndim != 4 or c.shape != (3,):
+        raise ValueError(f"radial_shells: fields[nvars, nz, ny, nx] and a centre of 3, got {x.shape} and {c.shape}")
+    if not (np.isfinite(delta) and delta > 0) or not (1 <= nbins <= RADIAL_MAX_BINS):
+        raise ValueError(f"radial_shells: delta finite and > 0, nbins in 1..{RADIAL_MAX_BINS}, got {delta} and {nbins}")
+    nv, nz, ny, nx = x.shape
+    pairs, rads = _radial_slots(nv, pairs, radials, "radial_shells")
+    d = []
+    for a, n in enumerate((nx, ny, nz)):                   # the minimum image, per axis
+        da = np.arange(n, dtype=np.float64) - c[a]
+        h = 0.5 * float(n)
+        da = np.where(da >= h, da - float(n), np.where(da < -h, da + float(n), da))
+        d.append(da)
+    dx, dy, dz = d[0][None, None, :], d[1][None, :, None], d[2][:, None, None]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        r = np.sqrt((dx * dx + dy * dy) + dz * dz)
+        q = r / delta
+        member = q < float(nbins)                          # false for a NaN
+        shell = np.where(member, q, 0.0).astype(np.int64)
+        terms = [np.ones_like(r)] + [x[v] for v in range(nv)] + [x[a] * x[b] for a, b in pairs]
+        for w, (vx, vy, vz) in rads:
+            p = ((x[vx] * dx + x[vy] * dy) + x[vz] * dz) / r
+            p = np.where(r == 0, 0.0, p)
+            terms.append(p if w < 0 else x[w] * p)
+    terms = np.stack(terms).reshape(len(terms), nz, ny * nx)
+    member, shell = member.reshape(nz, ny * nx), shell.reshape(nz, ny * nx)
+    total = np.zeros((len(terms), nbins))
+    for z in range(nz):                                    # the planes in sequence
+        plane = np.zeros((len(terms), nbins))
+        for t0 in range(0, ny * nx, RADIAL_TILE):          # the tiles in order
+            sel = np.nonzero(member[z, t0:t0 + RADIAL_TILE])[0] + t0
+            part = np.zeros((len(terms), nbins))
+            for k in range(len(terms)):
+                np.add.at(part[k], shell[z, sel], terms[k, z, sel])
+            plane = plane + part
+        total = total + plane
+    return total[0], total[1:]
+
+
+RADIAL_VARIABLES = ["rho", "phi", "afx", "afy", "afz", "agx", "agy", "agz"]
+RADIAL_PAIRS = [("rho", "phi")]
+RADIAL_RADIALS = [("rho", ("afx", "afy", "afz")), ("phi", ("agx", "agy", "agz"))]
+
+
+def laplace_inputs():
+    """(variables, pairs, radials) a radial trace must record for the droplet route to the surface tension: the 8 hydrovs
+    variables rho, phi, af*, ag*, the pair rho phi and the radial terms rho (af . r^) and phi (ag . r^), by name."""
+    return list(RADIAL_VARIABLES), list(RADIAL_PAIRS), list(RADIAL_RADIALS)
+
+
+def _radial_row(means, names, who, a, b=None, npairs=len(RADIAL_PAIRS)):
+    """The shell means of variable a, of the pair (a, b) or of the radial term a = ("rad", k), from means[..., Q, nbins] laid
+    out as laplace_inputs() asks."""
+    names = list(names)
+    for v in (a, b):
+        if isinstance(v, str) and v not in names:
+            raise ValueError(f"{who}: the mean of {v!r} is missing (recorded: {names})")
+    if isinstance(a, tuple):
+        return means[..., len(names) + npairs + a[1], :]
+    if b is None:
+        return means[..., names.index(a), :]
+    k = [tuple(sorted(p)) for p in RADIAL_PAIRS].index(tuple(sorted((a, b))))
+    return means[..., len(names) + k, :]
+
+
+def radial_pressure(means, names, alpha0, cs2=1.0 / 3.0):
+    """p(r) = cs2 (<rho> + <phi>) + alpha0 cs2 <rho phi> per shell, [..., nbins], from the shell means [..., Q, nbins] of a
+    radial trace recorded with laplace_inputs() (`names`: its variables): the bulk pressure of Surface_Tension.ipynb
+    (cell 13: p = rhot cs2 + alpha0 cs2 rho phi) with the product averaged before it is multiplied."""
+    m = np.asarray(means, dtype=np.float64)
+    if m.ndim < 2 or m.shape[-2] != len(names) + len(RADIAL_PAIRS) + len(RADIAL_RADIALS):
+        raise ValueError(f"radial_pressure: means[..., Q, nbins] with Q = {len(names)} variables + {len(RADIAL_PAIRS)} pair + "
+                         f"{len(RADIAL_RADIALS)} radial terms, got {m.shape}")
+    rho, phi = _radial_row(m, names, "radial_pressure", "rho"), _radial_row(m, names, "radial_pressure", "phi")
+    return cs2 * (rho + phi) + alpha0 * cs2 * _radial_row(m, names, "radial_pressure", "rho", "phi")
+
+
+def _shell_mean(v, counts, sel):
+    w = np.where(sel, np.asarray(counts, dtype=np.float64), 0.0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(w > 0, np.nan_to_num(v) * w, 0.0).sum(axis=-1) / w.sum(axis=-1)
+
+
+def pressure_jump(p, counts, r, r_in, r_out):
+    """Delta p = (count-weighted mean of p over the shells with r < r_in) - (that over the shells with r >= r_out): the
+    inside minus the outside pressure of the Laplace law.  p, counts [..., nbins]; r [nbins] the shell radii; NaN where
+    either side holds no site."""
+    r = np.asarray(r, dtype=np.float64)
+    p = np.asarray(p, dtype=np.float64)
+    return _shell_mean(p, counts, r < r_in) - _shell_mean(p, counts, r >= r_out)
+
+
+def radial_force_integral(means, names, delta, n):
+    """The Shan-Chen force integrated from the edge of the box to the droplet's centre, in box units: the shell form of
+    Surface_Tension.ipynb's  sum_ix (rho afx + phi agx)[ix, nc, nc] dr,  ix = 0 .. n/2 - 1, dr = 1 / n  (cell 13;
+    tests/test_gpu_notebook_surface_tension.py, _check_system: force_rho + force_phi, compared with deltaP_SC).  The
+    notebook walks along +x from the edge at ix = 0 towards the centre at ix = nc, that is against the outward radial
+    unit vector r^, so its integrand is -(rho af + phi ag) . r^: the result here is
+        - sum over the shells with r = (k + 1/2) delta < n / 2 of (<rho af . r^> + <phi ag . r^>) delta / n
+    and carries the notebook's sign (positive for a droplet, about Delta p).  means [..., Q, nbins] as radial_pressure
+    takes them; n: the box extent along the notebook's line (the smallest extent of a box that is no cube)."""
+    m = np.asarray(means, dtype=np.float64)
+    nbins = m.shape[-1]
+    inside = (np.arange(nbins) + 0.5) * float(delta) < 0.5 * float(n)
+    f = _radial_row(m, names, "radial_force_integral", ("rad", 0)) + _radial_row(m, names, "radial_force_integral", ("rad", 1))
+    return -(np.where(inside, np.nan_to_num(f), 0.0).sum(axis=-1)) * float(delta) / float(n)
+
+
+def fit_radial_profile(r, rho_mean, counts):
+    """Count-weighted least-squares fit of rho(r) = hi - (hi - lo) / 2 (1 + tanh((r - R) / W)) to the shell means
+    rho_mean[nbins] at the radii r[nbins] (every shell stands for `counts` sites; empty shells are left out); returns
+    (hi, lo, R, W) in the units of r.  The 1-D stand-in for fit_droplet on a radial trace's record."""
+    from scipy.optimize import curve_fit
+
+    def profile(r, hi, lo, radius, width):
+        return hi - (hi - lo) / 2 * (1 + np.tanh((r - radius) / width))
+
+    r, rho, w = (np.asarray(v, dtype=np.float64) for v in (r, rho_mean, counts))
+    keep = w > 0
+    r, rho, w = r[keep], rho[keep], w[keep]
+    half = r[np.argmin(np.abs(rho - 0.5 * (rho[0] + rho[-1])))]           # start: the shell nearest to half height, one shell wide
+    p0 = [rho[0], rho[-1], half, float(r[1] - r[0]) if len(r) > 1 else 1.0]
+    popt, _ = curve_fit(profile, r, rho, p0=p0, sigma=1.0 / np.sqrt(w))
+    return tuple(popt)
+
+
+def equimolar_radius(rho_mean, counts):
+    """The radius R_e of the sphere that holds the droplet's excess mass at the inner density:
+    4/3 pi R_e^3 (hi - lo) = sum_k counts_k (rho_k - lo), hi and lo the means of the innermost and the outermost
+    non-empty shell.  In cells (a shell's sites count its volume), whatever delta is; no transcendental function."""
+    rho, w = np.asarray(rho_mean, dtype=np.float64), np.asarray(counts, dtype=np.float64)
+    keep = w > 0
+    rho, w = rho[keep], w[keep]
+    hi, lo = rho[0], rho[-1]
+    return float((3.0 * (w * (rho - lo)).sum() / (4.0 * np.pi * (hi - lo))) ** (1.0 / 3.0))
+
+
 def com_from_moments(m, n, weighted=False):
     """Centre of mass in unit-box cell-centre coordinates; weighted=True is the reference's C++ getCenterOfMass
     (trapezoid weights, LBM_hydrovs.H:62-113), False the notebooks' plain sum."""

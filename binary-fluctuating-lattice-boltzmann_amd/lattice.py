@@ -569,6 +569,99 @@ class ProfileTrace(_Recorder):
         return self.read(first, count)[0] / float(self.plane_sites)
 
 
+class RadialTrace(_Recorder):
+    """The sums of chosen hydrovs / hydrovsbar variables, of chosen products of them and of chosen projections onto the
+    outward radial unit vector over the shells of width `delta` about a droplet's centre (a fixed one, or the centre of
+    mass of the cells above a threshold), for every replica, recorded on the device every `every` steps through the owner
+    (a lone single-slab BinaryLBM or a BatchLBM) and read once: include/bflbm.h, "Radial traces"; analysis.radial_shells
+    is the same arithmetic in numpy, analysis.radial_pressure, pressure_jump, radial_force_integral, fit_radial_profile
+    and equimolar_radius turn the shell means into the Laplace-law inputs.  Made by owner.radial_trace(); an owner may
+    carry several.  Closing the owner detaches the trace: it stays readable until its own close()."""
+    _abi = "bflbm_radial"
+
+    def __init__(self, owner, create, variables, pairs, radials, centre, threshold, delta, nbins, source, every, capacity):
+        if source not in ("hydrovs", "hydrovsbar", 0, 1):
+            raise ValueError(f"radial_trace: source {source!r}, expected 'hydrovs' (0) or 'hydrovsbar' (1)")
+        self.source = int(FSTAT_SOURCES.get(source, source))
+        self.component_names = fstat_variable_names(self.source)
+        items = [variables] if isinstance(variables, (str, int, np.integer)) else list(variables)
+        self.variables = [self._component(v) for v in items]
+        self.pairs = [(self._slot(a), self._slot(b)) for a, b in [(p, p) if isinstance(p, str) else p for p in pairs]]   # a lone name: its square
+        self.radials = [(-1 if w is None else self._slot(w), tuple(self._slot(c) for c in v)) for w, v in radials]
+        if any(len(v) != 3 for _, v in self.radials):
+            raise ValueError("radial_trace: a radial term is (w, (vx, vy, vz)), w a variable or None")
+        self.delta = float(delta)
+        if not (np.isfinite(self.delta) and self.delta > 0):
+            raise ValueError(f"radial_trace: delta {delta} must be finite and > 0")
+        if nbins is None:                                  # the shells that cover half the box diagonal
+            nbins = min(128, int(np.floor(0.5 * np.sqrt(float(sum(v * v for v in owner.n))) / self.delta)) + 1)
+        nv, npairs, nrad = len(self.variables), len(self.pairs), len(self.radials)
+        va = (ctypes.c_int * max(nv, 1))(*self.variables)
+        pa = (ctypes.c_int * max(npairs, 1))(*[p[0] for p in self.pairs])
+        pb = (ctypes.c_int * max(npairs, 1))(*[p[1] for p in self.pairs])
+        rw = (ctypes.c_int * max(nrad, 1))(*[w for w, _ in self.radials])
+        rv = (ctypes.c_int * max(3 * nrad, 1))(*[c for _, v in self.radials for c in v])
+        c = None if centre is None else (ctypes.c_double * 3)(*[float(v) for v in centre])
+        thr = -np.inf if threshold is None else float(threshold)
+        super().__init__(owner, create, self.source, nv, va, npairs, pa, pb, nrad, rw, rv, c, thr, self.delta, int(nbins),
+                         int(every), int(capacity))
+
+    @property
+    def names(self):
+        """The recorded variables by name, in slot order: what analysis.radial_pressure takes."""
+        return [self.component_names[c] if 0 <= c < len(self.component_names) else str(c) for c in self.variables]
+
+    def _component(self, v):
+        """A variable by name or by component index of the source."""
+        if not isinstance(v, str):
+            return int(v)
+        if v not in self.component_names:
+            raise ValueError(f"radial_trace: variable {v!r}, expected one of {self.component_names} or an index")
+        return self.component_names.index(v)
+
+    def _slot(self, v):
+        """A recorded variable by name or by slot (its position in the variable list)."""
+        if not isinstance(v, str):
+            return int(v)
+        c = self._component(v)
+        if c not in self.variables:
+            raise ValueError(f"radial_trace: {v!r} is not one of the recorded variables")
+        return self.variables.index(c)
+
+    def _owner_closing(self):
+        """The owner's close(): the library detaches the trace; its samples stay readable until close()."""
+        _unregister(self.owner, self)
+
+    def geometry(self):
+        """(Q = variables + pairs + radial terms, shells, sites of a tile, tiles per plane): what the library built."""
+        v = [ctypes.c_int() for _ in range(4)]
+        check(self.lib.bflbm_radial_geometry(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    @property
+    def r(self):
+        """The shell radii (k + 1/2) delta, [nbins], in cells."""
+        return (np.arange(self.geometry()[1]) + 0.5) * self.delta
+
+    def read(self, first=0, count=None):
+        """(centres[count, B, 3], counts[count, B, nbins], sums[count, B, Q, nbins], steps[count, B] int64) of the samples
+        first ... first + count - 1 (count None: all from `first`): the centre used in cell indices, the sites of every
+        shell, the sums of the variables, then the pairs, then the radial terms; synchronises the owner's stream."""
+        n, b = self._count()
+        count = n - int(first) if count is None else int(count)
+        nq, nbins = self.geometry()[:2]
+        steps = np.empty((max(count, 0), b), dtype=np.int64)
+        rec = np.empty((max(count, 0), b, 3 + (1 + nq) * nbins))
+        check(self.lib.bflbm_radial_read(self._h, int(first), count, _ptr(rec), steps.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        return rec[..., :3], rec[..., 3:3 + nbins], rec[..., 3 + nbins:].reshape(rec.shape[:2] + (nq, nbins)), steps
+
+    def means(self, first=0, count=None):
+        """sums / counts [count, B, Q, nbins]: the shell averages, NaN where a shell holds no site."""
+        _, counts, sums, _ = self.read(first, count)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(counts[..., None, :] > 0, sums / counts[..., None, :], np.nan)
+
+
 
 # kernel schedules of include/bflbm.h (bflbm_set_schedule): "fused" = plane march with the ring densities pulled
 # (bit-exact), "handover" = plane march with the ring densities handed over from the previous step (tolerance)
@@ -827,6 +920,15 @@ class BinaryLBM(_DropletMixin):
         to 8 variables of `source` ("hydrovs" or "hydrovsbar"; names or component indices) and of the products of up to
         16 pairs of them (names or slots; a lone name is its square): ProfileTrace."""
         return ProfileTrace(self, "bflbm_profile_create", variables, pairs, axis, source, every, capacity)
+
+    def radial_trace(self, variables, pairs=(), radials=(), centre=None, threshold=None, delta=1.0, nbins=None, source="hydrovs",
+                     every=1, capacity=64):
+        """Record, after every `every`-th step, the sums over the shells of width `delta` (cells) about `centre` (cell
+        indices; None: the centre of mass of the cells with rho above `threshold`, None: every cell) of up to 8 variables
+        of `source` (names or component indices), of the products of up to 16 pairs of them and of up to 4 radial terms
+        (w, (vx, vy, vz)) = w (v . r^), w None for the bare projection (names or slots), with the sites of every shell:
+        RadialTrace.  nbins None: the shells that cover half the box diagonal, 128 at the most."""
+        return RadialTrace(self, "bflbm_radial_create", variables, pairs, radials, centre, threshold, delta, nbins, source, every, capacity)
 
     def com_sums(self):
         s = (ctypes.c_double * 4)()
@@ -1218,6 +1320,13 @@ class BatchLBM:
         """Every replica's plane sums along one axis (BinaryLBM.profile_trace) after every `every`-th batch step, with one
         observation launch, one plane launch and one finishing launch per sample."""
         return ProfileTrace(self, "bflbm_batch_profile_create", variables, pairs, axis, source, every, capacity)
+
+    def radial_trace(self, variables, pairs=(), radials=(), centre=None, threshold=None, delta=1.0, nbins=None, source="hydrovs",
+                     every=1, capacity=64):
+        """Every replica's shell sums about its own centre of mass, or about one fixed centre (BinaryLBM.radial_trace), after
+        every `every`-th batch step, with one observation launch, the two centre launches, one shell launch and one
+        finishing launch per sample."""
+        return RadialTrace(self, "bflbm_batch_radial_create", variables, pairs, radials, centre, threshold, delta, nbins, source, every, capacity)
 
     def structfact(self, var_names, **kw):
         """One structure-factor accumulator for the whole batch (structfact.BatchStructFact; every=k attaches it)."""

@@ -808,6 +808,88 @@ int bflbm_profile_read(bflbm_profile* t, long long first, long long count,
                        double* sums /* [count][nreplicas][Q][n_a] */,
                        long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
 
+/* ---- Radial traces: the sums of chosen fields, of chosen products of them and of chosen projections onto the outward
+ * radial unit vector, over the shells of width delta about a droplet's centre, recorded on the device as a time series
+ * and read once at the end.  Surface_Tension.ipynb's droplet route needs, per droplet, the pressure inside and outside
+ * (cell 13: p = rhot cs2 + alpha0 cs2 rho phi), the Shan-Chen force rho af + phi ag integrated from the edge to the
+ * centre, and a radius, and regresses Delta p against 1 / R; Droplet_Fluctuation.ipynb fits tanh profiles of rho(r) per
+ * frame.  Under thermal noise a single lattice line is useless; the shell average about the moving centre is what one
+ * wants, and it is a few dozen numbers (analysis.radial_pressure, pressure_jump, radial_force_integral,
+ * fit_radial_profile, equimolar_radius).  A radial trace is the profile trace turned from planes into shells; it is
+ * attached to one lone single-slab context or one replica batch (no rings: droplet ensembles are small boxes).
+ *  - definition (stated here and nowhere else).  Every operation is an IEEE double operation in the stated order, never
+ *    contracted (-ffp-contract=off).  Inputs: a source (0: hydrovs, 22 components; 1: hydrovsbar, 9 components), nvars in
+ *    1..8 distinct component indices of that source, npairs in 0..16 pairs (a, b) of variable SLOTS (positions in the
+ *    variable list), a == b allowed, nrad in 0..4 radial terms (w, vx, vy, vz) of variable slots, w a slot or -1, either a
+ *    fixed centre c[3] in cell-index coordinates (one for all replicas) or a null centre with a threshold, a shell width
+ *    delta > 0 in cells and nbins in 1..128.  The null centre is the shape trace's rule: the same kernels in the same
+ *    order, so c_a = record 1 + a / record 0 of bflbm_trace_read of the same state and threshold bit for bit, NaN where
+ *    no cell is above the threshold.
+ *    Site geometry: for the site (ix, iy, iz) and per axis a, d_a = (double)i_a - c_a; h_a = 0.5 * (double)n_a; if
+ *    d_a >= h_a then d_a = d_a - (double)n_a, else if d_a < -h_a then d_a = d_a + (double)n_a (the minimum image).
+ *    r = sqrt((dx*dx + dy*dy) + dz*dz); q = r / delta; the site belongs to shell k = (int)q if q < (double)nbins and to
+ *    no shell otherwise, a NaN q included.
+ *    Terms of a site, Q = nvars + npairs + nrad: x_q for a variable; x_a * x_b for a pair; for a radial term
+ *    p = ((x_vx*dx + x_vy*dy) + x_vz*dz) / r, p = +0.0 where r == 0, and the term is p for w = -1, else x_w * p; the
+ *    count term is 1.0.  analysis.radial_shells restates this in numpy, operation for operation and in the order below.
+ *  - order of a sum, fixed by the box alone.  Every sum starts from +0.0.  The dense plane z (sites s = y nx + x) is cut
+ *    into tiles of 256 consecutive sites, the last one short.  The partial of (term, shell, tile) adds the terms of the
+ *    tile's member sites sequentially in ascending s; the partials of a plane are added in tile order; the planes are
+ *    added in the sequence z = 0 .. nz-1.  A partial with no member site is +0.0 and no sum from +0.0 is ever -0.0, so
+ *    leaving it out changes no bit: the implementation skips empty shells and tiles.  No atomics.  A record does not
+ *    depend on the number of replicas, `every`, the capacity, the schedule, what else is attached, or lone context
+ *    versus replica.  bflbm_radial_geometry reports Q, nbins, the sites of a tile (256) and the tiles per plane.
+ *  - sample: [replica][3 + (1 + Q) nbins] doubles: the centre used (cx, cy, cz), the counts [nbins], then the sums
+ *    [Q][nbins], variables first, then pairs, then radial terms.  These are sums: the reader divides by the counts.
+ *  - how a sample is taken, on the owner's stream and without a host synchronisation: the accumulators' observation,
+ *    exactly as the profile trace takes it (a lone context: into the scratch state buffer; a batch: one launch over all
+ *    replicas, only the chosen variables, into a buffer of the trace); with a null centre the two ensemble-trace
+ *    kernels into a buffer of the trace; the shell kernel, one workgroup of 256 threads per (replica, plane), compiled
+ *    once per number of variables, which walks its tiles in order: per tile every thread loads its site's variables
+ *    (8-byte loads, a wave reads 512 contiguous bytes per variable), forms d, r, the shell and the projections and stages
+ *    the variables, the projections and the shell in LDS (2048 (nvars + 4) + 1312 bytes); the tile's lowest and highest
+ *    shell come from an integer reduction; thread t owns the items (shell, term) = divmod(t + 256 j, 1 + Q), j = 0, 1,
+ *    ..., and for those inside the tile's shell range walks the tile's sites in order and adds the members' terms,
+ *    products formed on the fly from the staged rows, then adds the tile's partial to its per-plane accumulator in a
+ *    register; one [1 + Q][nbins] block per (replica, plane) leaves the kernel; then the finishing launch, one thread per
+ *    (replica, term, shell), adds the planes in sequence straight into the slot [sample][replica] and writes the centre.
+ *    No atomics, no scratch.  The tile size and the item-to-thread map are untimed heuristics.
+ *  - what is touched on the owner: what the profile trace's observation touches.  Observing hydrovs rewrites rho / phi by
+ *    the density pass where they are stale; a context's scratch state buffer is overwritten.  The resident state, the
+ *    step counters and everything the owner computes are unchanged.
+ *  - sampling rule, capacity, step labels, order among the recorders of one owner: those of the other traces ("radial
+ *    trace full").  An owner may carry any number of radial traces.
+ *  - not covered: a droplet that diffuses across the periodic boundary.  The centre is the ensemble trace's, which does
+ *    not unwrap, while the shells use the minimum image.
+ *  - refused at creation (non-zero return, a message naming the call, before any launch, nothing allocated, the owner's
+ *    recorder list untouched): null arguments, a source outside 0..1, nvars outside 1..8, npairs outside 0..16, nrad
+ *    outside 0..4, a repeated variable, a component index outside its source, a pair or radial slot outside
+ *    0..nvars-1 (w = -1 excepted), a non-finite fixed centre, a NaN threshold with a null centre, a delta that is not
+ *    finite or <= 0, nbins outside 1..128, every < 1, capacity < 1, a capacity beyond 1 TB of records, nz > 65535, a
+ *    replica view (use bflbm_batch_radial_create), a context with nranks > 1, an open step, a failed allocation.  An
+ *    open step also refuses bflbm_radial_sample, _reset and _read.
+ *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_radial_read, _count,
+ *    _geometry and _destroy still work, bflbm_radial_sample fails.  bflbm_radial_destroy(NULL) returns 0.
+ *  - only bflbm_radial_read and bflbm_radial_destroy synchronise the owner's stream. */
+typedef struct bflbm_radial bflbm_radial;
+int bflbm_radial_create(bflbm_ctx* c, int source, int nvars, const int* vars, int npairs,
+                        const int* pair_a /* or NULL if npairs == 0 */, const int* pair_b,
+                        int nrad, const int* rad_w /* [nrad], or NULL if nrad == 0 */, const int* rad_v /* [nrad][3] */,
+                        const double* centre_or_null /* [3] */, double threshold, double delta, int nbins,
+                        int every, long long capacity, bflbm_radial** out);
+int bflbm_batch_radial_create(bflbm_batch* b, int source, int nvars, const int* vars, int npairs,
+                              const int* pair_a, const int* pair_b, int nrad, const int* rad_w, const int* rad_v,
+                              const double* centre_or_null, double threshold, double delta, int nbins,
+                              int every, long long capacity, bflbm_radial** out);
+int bflbm_radial_destroy(bflbm_radial* t);
+int bflbm_radial_sample(bflbm_radial* t);                  /* record the resident state now (e.g. frame 0) */
+int bflbm_radial_reset(bflbm_radial* t);                   /* forget the samples, restart the every-counter */
+int bflbm_radial_count(const bflbm_radial* t, long long* nsamples, int* nreplicas);
+int bflbm_radial_geometry(const bflbm_radial* t, int* nsums /* Q */, int* nbins, int* tile_sites, int* tiles_per_plane);
+int bflbm_radial_read(bflbm_radial* t, long long first, long long count,
+                      double* rec /* [count][nreplicas][3 + (1 + Q) nbins] */,
+                      long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
+
 /* Materialise the per-step fields the reference keeps in MultiFabs, for the state
  * after the last completed step:
  *   hydrovsbar comps 0..8  (LBM_hydrovars_density, LBM_binary.H:315-354)
