@@ -1729,6 +1729,7 @@ int bflbm_fused_plan_query(const int n[3], int nreplicas, int noise, int compute
 
 }  // extern "C"
 
+#include "bflbm_fieldsel.h"
 #include "bflbm_sf.h"
 #include "bflbm_sf_ring.h"
 #include "bflbm_droplet.h"

@@ -10,21 +10,12 @@
 // k_observe_batch computes, per site, what k_observe computes (the same device functions in the same order, no injected
 // noise, no reference state), so the stacked getters bflbm_batch_get_hydrovs / _hydrovsbar return the doubles of the views'.
 // The link to the batch, the every-count and the detaching are those of bflbm_recorder.h.
-// Included by bflbm.hip after bflbm_batch.h, bflbm_sf.h and bflbm_trace.h (needs bflbm_batch, FftApi, SfPairs).
+// Included by bflbm.hip after bflbm_batch.h, bflbm_fieldsel.h, bflbm_sf.h and bflbm_trace.h (needs bflbm_batch, FftApi,
+// SfPairs, ObsSel, field_select_pairs).
 #ifndef BFLBM_BATCH_SF_H_
 #define BFLBM_BATCH_SF_H_
 
 namespace {
-
-// which components an observation writes and where: component c with bit c of mask set goes to slot[c] of the replica's
-// nsel dense volumes
-struct ObsSel { unsigned mask; int nsel; int slot[BFLBM_NHYDRO_]; };
-
-ObsSel obs_first(int ncomp) {
-  ObsSel s; s.mask = 0; s.nsel = ncomp;
-  for (int c = 0; c < BFLBM_NHYDRO_; ++c) { s.slot[c] = c < ncomp ? c : 0; if (c < ncomp) s.mask |= 1u << c; }
-  return s;
-}
 
 // grid (plane blocks, nz, B): WHAT 0 hydrovsbar (LBM_binary.H:315-340), 2 hydrovs (:196-295) of replica blockIdx.z,
 // out[(r * nsel + slot) * n + site]
@@ -173,8 +164,7 @@ struct bflbm_batch_sf : bflbm_recorder {  // n: frames accumulated; every == 0: 
   int nx = 0, ny = 0, nz = 0;
   long long nsites = 0, nk = 0;     // sites, half-spectrum size
   SfPairs pairs;                    // a, b: slots of the pair's variables
-  ObsSel sel;
-  int lb = 0;                       // 0 hydrovs, 1 hydrovsbar
+  FieldSelection fs;                // the distinct variables of the pairs
   double* fields = nullptr;         // [nrep][nsel][nsites]
   double2* hat = nullptr;           // [nrep][nsel][nk]
   double2* acc = nullptr;           // [nrep][npairs][nk]
@@ -187,6 +177,18 @@ struct bflbm_batch_sf : bflbm_recorder {  // n: frames accumulated; every == 0: 
 
 namespace {
 
+// where the spectra of accepted pairs lie among the selection's, and their scales (null: 1.0)
+SfPairs sf_pairs(const ObsSel& sel, int npairs, const int* var_a, const int* var_b, const double* scale) {
+  SfPairs P;
+  P.n = npairs;
+  for (int p = 0; p < 32; ++p) {
+    P.a[p] = p < npairs ? sel.slot[var_a[p]] : 0;
+    P.b[p] = p < npairs ? sel.slot[var_b[p]] : 0;
+    P.scale[p] = (p < npairs && scale) ? scale[p] : 1.0;
+  }
+  return P;
+}
+
 void batch_sf_free(bflbm_batch_sf* s) {
   if (s->plan) g_fft.destroy(s->plan);
   for (void* p : {(void*)s->fields, (void*)s->hat, (void*)s->acc, (void*)s->expand}) if (p) hipFree(p);
@@ -196,11 +198,11 @@ void batch_sf_free(bflbm_batch_sf* s) {
 // enqueue one frame of the resident state of every replica; no host synchronisation
 int batch_sf_frame(bflbm_batch_sf* s, const char* call) {
   bflbm_batch* b = s->batch;
-  if (batch_observe_launch(b, s->lb ? 0 : 2, s->sel, s->fields, call)) return 1;
+  if (batch_observe_launch(b, field_observe_code(s->fs.source), s->fs.sel, s->fields, call)) return 1;
   g_fft.set_stream(s->plan, b->stream);
   if (g_fft.exec_d2z(s->plan, s->fields, (hipfftDoubleComplex*)s->hat) != HIPFFT_SUCCESS) return fail("%s: hipfftExecD2Z failed", call);
   const dim3 grid((unsigned)((s->nk + 255) / 256), (unsigned)s->pairs.n, (unsigned)s->nrep);
-  hipLaunchKernelGGL(k_sf_accumulate_batch, grid, dim3(256), 0, b->stream, s->hat, s->acc, s->nk, s->sel.nsel, s->pairs, 1.0 / (double)s->nsites);
+  hipLaunchKernelGGL(k_sf_accumulate_batch, grid, dim3(256), 0, b->stream, s->hat, s->acc, s->nk, s->fs.sel.nsel, s->pairs, 1.0 / (double)s->nsites);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail("%s: accumulation launch failed: %s", call, hipGetErrorString(e));
   s->n += 1;
@@ -243,11 +245,7 @@ int bflbm_batch_sf_create(bflbm_batch* b, int npairs, const int* var_a, const in
   if (!b || !var_a || !var_b || !out) return fail("bflbm_batch_sf_create: null argument");
   if (npairs < 1 || npairs > 32) return fail("bflbm_batch_sf_create: 1..32 pairs (got %d)", npairs);
   if (every < 0) return fail("bflbm_batch_sf_create: every must be >= 0 (got %d)", every);
-  const int most = lb_hydrovars ? BFLBM_NHYDROBAR : BFLBM_NHYDRO;
-  for (int p = 0; p < npairs; ++p)
-    for (int v : {var_a[p], var_b[p]})
-      if (v < 0 || v >= most)
-        return fail("bflbm_batch_sf_create: pair %d: variable index %d outside %s (0..%d)", p, v, lb_hydrovars ? "hydrovsbar" : "hydrovs", most - 1);
+  if (field_refuse_pair_vars("bflbm_batch_sf_create", lb_hydrovars ? 1 : 0, npairs, var_a, var_b)) return 1;
   if (load_fft()) return 1;
   HIP_TRY(hipSetDevice(b->device));
   bflbm_batch_sf* s = new bflbm_batch_sf();
@@ -255,17 +253,10 @@ int bflbm_batch_sf_create(bflbm_batch* b, int npairs, const int* var_a, const in
   s->nx = b->G.nx; s->ny = b->G.ny; s->nz = b->G.nzs;
   s->nsites = (long long)s->nx * s->ny * s->nz;
   s->nk = (long long)(s->nx / 2 + 1) * s->ny * s->nz;
-  s->lb = lb_hydrovars ? 1 : 0;
-  s->sel.mask = 0; s->sel.nsel = 0;
-  for (int p = 0; p < npairs; ++p) { s->sel.mask |= 1u << var_a[p]; s->sel.mask |= 1u << var_b[p]; }
-  for (int c = 0; c < BFLBM_NHYDRO_; ++c) s->sel.slot[c] = (s->sel.mask & (1u << c)) ? s->sel.nsel++ : 0;
-  s->pairs.n = npairs;
-  for (int p = 0; p < 32; ++p) {
-    s->pairs.a[p] = p < npairs ? s->sel.slot[var_a[p]] : 0;
-    s->pairs.b[p] = p < npairs ? s->sel.slot[var_b[p]] : 0;
-    s->pairs.scale[p] = (p < npairs && scale) ? scale[p] : 1.0;
-  }
-  const size_t fb = (size_t)s->nrep * s->sel.nsel * s->nsites * sizeof(double), hb = (size_t)s->nrep * s->sel.nsel * s->nk * sizeof(double2);
+  s->fs = field_select_pairs(lb_hydrovars ? 1 : 0, npairs, var_a, var_b);
+  s->pairs = sf_pairs(s->fs.sel, npairs, var_a, var_b, scale);
+  const int nsel = s->fs.sel.nsel;
+  const size_t fb = (size_t)s->nrep * nsel * s->nsites * sizeof(double), hb = (size_t)s->nrep * nsel * s->nk * sizeof(double2);
   const size_t ab = s->acc_bytes(), eb = (size_t)npairs * s->nsites * sizeof(double);
   hipError_t e = hipMalloc((void**)&s->fields, fb);
   if (e == hipSuccess) e = hipMalloc((void**)&s->hat, hb);
@@ -277,10 +268,10 @@ int bflbm_batch_sf_create(bflbm_batch* b, int npairs, const int* var_a, const in
     return fail("bflbm_batch_sf_create: out of device memory (fields %zu + spectra %zu + accumulators %zu + download %zu bytes): %s", fb, hb, ab, eb, hipGetErrorString(e));
   }
   int dims[3] = {s->nz, s->ny, s->nx};
-  if (g_fft.plan_many(&s->plan, 3, dims, nullptr, 1, (int)s->nsites, nullptr, 1, (int)s->nk, HIPFFT_D2Z, s->nrep * s->sel.nsel) != HIPFFT_SUCCESS) {
+  if (g_fft.plan_many(&s->plan, 3, dims, nullptr, 1, (int)s->nsites, nullptr, 1, (int)s->nk, HIPFFT_D2Z, s->nrep * nsel) != HIPFFT_SUCCESS) {
     s->plan = nullptr;
     batch_sf_free(s);
-    return fail("bflbm_batch_sf_create: hipfftPlanMany failed for %d transforms of %d x %d x %d", (int)b->ctx.size() * s->sel.nsel, b->G.nx, b->G.ny, b->G.nzs);
+    return fail("bflbm_batch_sf_create: hipfftPlanMany failed for %d transforms of %d x %d x %d", (int)b->ctx.size() * nsel, b->G.nx, b->G.ny, b->G.nzs);
   }
   g_fft.set_stream(s->plan, b->stream);
   e = hipMemsetAsync(s->acc, 0, ab, b->stream);

@@ -13,9 +13,9 @@
 // Not built on purpose: the L1 deviation of PrintConvergence (two passes over stored frames), a noise source on batches
 // (k_observe_batch has no noise form), windows that forget old frames, fusing the accumulation into the observation
 // kernels (it would give every observer a second form).
-// The lifecycle is that of bflbm_recorder.h; capacity is unbounded, every = 0 is fed by hand only.  Included by bflbm.hip
-// after bflbm_modes.h (needs bflbm_ctx, bflbm_batch, bflbm_ring, ObsSel, batch_observe_launch, observe_launch,
-// ring_prepare_ref).
+// The lifecycle is that of bflbm_recorder.h, the selection that of bflbm_fieldsel.h; capacity is unbounded, every = 0 is
+// fed by hand only.  Included by bflbm.hip after bflbm_modes.h (needs bflbm_ctx, bflbm_batch, bflbm_ring, FieldSelection,
+// FstatVars, FstatPairs, fields_observe, field_dispatch_nv, ring_prepare_ref).
 #ifndef BFLBM_FSTAT_H_
 #define BFLBM_FSTAT_H_
 
@@ -24,13 +24,8 @@
 #include <vector>
 
 namespace fstat_limits {
-constexpr int kMaxVars = 8, kMaxPairs = 16;
 constexpr int kMaxBlocks = 2048;     // the grid of the accumulation: at most this many workgroups, which stride the rest
 }
-
-// where the variables lie among the dense volumes of the observation, and the pairs as variable slots; by value
-struct FstatVars { int vol[fstat_limits::kMaxVars]; };
-struct FstatPairs { int n; int a[fstat_limits::kMaxPairs]; int b[fstat_limits::kMaxPairs]; };
 
 // the accumulators of one owner part: the lone context, the batch, or one slab of a ring
 struct FstatPart {
@@ -43,15 +38,11 @@ struct FstatPart {
 
 struct bflbm_fstat : bflbm_recorder {   // n: frames taken
   int nx = 0, ny = 0, nz = 0;
-  int source = 0;                   // 0 hydrovs, 1 hydrovsbar, 2 noise
-  int nvars = 0;
-  int ncomp = 0;                    // a context: the components its observation produces
-  ObsSel sel;                       // a batch: what the observation writes
-  FstatVars vol;                    // the volume of every variable: a batch's slot, a context's component
+  FieldSelection fs;                // source 0 hydrovs, 1 hydrovsbar, 2 noise
   FstatPairs pairs;
   double* fields = nullptr;         // a batch: [nrep][nvars][n]
   std::vector<FstatPart> part;
-  int nvol() const { return 2 * nvars + pairs.n; }
+  int nvol() const { return 2 * fs.nvars + pairs.n; }
   bflbm_fstat() : bflbm_recorder("field statistic", "bflbm_fstat") {}
   ~bflbm_fstat() override {
     for (FstatPart& q : part) {
@@ -177,52 +168,21 @@ __global__ void __launch_bounds__(256) k_fstat_derive(const double* __restrict__
   out[s] = replica < 0 ? ens * inv_ens : one;
 }
 
-int fstat_source_size(int source) { return source == 0 ? BFLBM_NHYDRO : (source == 1 ? BFLBM_NHYDROBAR : 2 * Q); }
-const char* fstat_source_name(int source) { return source == 0 ? "hydrovs" : (source == 1 ? "hydrovsbar" : "the noise moments"); }
-
-// what every creation call refuses about its own arguments
-int fstat_refuse_args(const char* call, int source, int nvars, const int* vars, int npairs, const int* pair_a, const int* pair_b, int every) {
-  using namespace fstat_limits;
-  if (source < 0 || source > 2) return fail("%s: source must be 0 (hydrovs), 1 (hydrovsbar) or 2 (noise) (got %d)", call, source);
-  if (nvars < 1 || nvars > kMaxVars) return fail("%s: 1..%d variables (got %d)", call, kMaxVars, nvars);
-  if (npairs < 0 || npairs > kMaxPairs) return fail("%s: 0..%d pairs (got %d)", call, kMaxPairs, npairs);
-  if (npairs > 0 && (!pair_a || !pair_b)) return fail("%s: null argument", call);
-  if (every < 0) return fail("%s: every must be >= 0 (got %d)", call, every);
-  const int most = fstat_source_size(source);
-  for (int i = 0; i < nvars; ++i) {
-    if (vars[i] < 0 || vars[i] >= most) return fail("%s: variable index %d outside %s (0..%d)", call, vars[i], fstat_source_name(source), most - 1);
-    for (int k = 0; k < i; ++k) if (vars[k] == vars[i]) return fail("%s: variable index %d given twice", call, vars[i]);
-  }
-  for (int p = 0; p < npairs; ++p)
-    for (int slot : {pair_a[p], pair_b[p]})
-      if (slot < 0 || slot >= nvars) return fail("%s: pair %d: slot %d outside the %d variables", call, p, slot, nvars);
-  return 0;
-}
-
 int fstat_create(bflbm_ctx* c, bflbm_batch* b, bflbm_ring* g, int source, int nvars, const int* vars, int npairs,
                  const int* pair_a, const int* pair_b, int every, bflbm_fstat** out) {
-  using namespace fstat_limits;
   const char* call = b ? "bflbm_batch_fstat_create" : (g ? "bflbm_ring_fstat_create" : "bflbm_fstat_create");
-  if (fstat_refuse_args(call, source, nvars, vars, npairs, pair_a, pair_b, every)) return 1;
+  if (field_refuse_args(call, source, 2, nvars, vars, npairs, pair_a, pair_b)) return 1;
+  if (every < 0) return fail("%s: every must be >= 0 (got %d)", call, every);
   if (store_refuse_owner(c, call, "bflbm_batch_fstat_create", "field statistic")) return 1;
   if (b && source == 2) return fail("%s: the observation of a batch has no noise form; source 2 needs a lone context or a ring", call);
-  if ((c && c->step_open()) || (g && ring_step_open(g))) return fail("%s inside an open step", call);
-  if (b) for (const bflbm_ctx* v : b->ctx) if (v->step_open()) return fail("%s: a replica has an open step", call);
+  if (recorder_refuse_open(c, b, g, call)) return 1;
   const Geo& G = c ? c->G : (b ? b->G : g->ctx[0]->G);
 
   std::unique_ptr<bflbm_fstat> t(new bflbm_fstat());
   recorder_bind(t.get(), c, b, every, g);
   t->nx = G.nx; t->ny = G.ny; t->nz = G.nz;
-  t->source = source; t->nvars = nvars;
-  // the batch observation writes the chosen variables in ascending order; a context's all components up to the largest
-  t->sel.mask = 0; t->sel.nsel = 0;
-  int top = 0;
-  for (int i = 0; i < nvars; ++i) { if (b) t->sel.mask |= 1u << vars[i]; top = std::max(top, vars[i]); }
-  for (int v = 0; v < BFLBM_NHYDRO_; ++v) t->sel.slot[v] = (t->sel.mask & (1u << v)) ? t->sel.nsel++ : 0;
-  t->ncomp = source == 0 ? top + 1 : fstat_source_size(source);
-  for (int i = 0; i < kMaxVars; ++i) t->vol.vol[i] = i < nvars ? (b ? t->sel.slot[vars[i]] : vars[i]) : 0;
-  t->pairs.n = npairs;
-  for (int p = 0; p < kMaxPairs; ++p) { t->pairs.a[p] = p < npairs ? pair_a[p] : 0; t->pairs.b[p] = p < npairs ? pair_b[p] : 0; }
+  t->fs = field_select(b != nullptr, source, nvars, vars);
+  t->pairs = field_pairs(npairs, pair_a, pair_b);
 
   const long long plane = (long long)G.nx * G.ny;
   if (g) {
@@ -257,14 +217,9 @@ int fstat_launch(const bflbm_fstat* t, const FstatPart& q, const double* src, lo
   const unsigned blocks = (unsigned)std::min<long long>((turns + 255) / 256, fstat_limits::kMaxBlocks);
   const dim3 grid(blocks, 1, (unsigned)t->nrep);
   const int first_frame = t->n == 0 ? 1 : 0;
-#define BFLBM_FSTAT_ACCUMULATE(NV) \
-  case NV: hipLaunchKernelGGL((k_fstat_accumulate<NV>), grid, dim3(256), 0, stream, src, src_rep, q.acc, q.n, t->vol, t->pairs, first_frame); break
-  switch (t->nvars) {
-    BFLBM_FSTAT_ACCUMULATE(1); BFLBM_FSTAT_ACCUMULATE(2); BFLBM_FSTAT_ACCUMULATE(3); BFLBM_FSTAT_ACCUMULATE(4);
-    BFLBM_FSTAT_ACCUMULATE(5); BFLBM_FSTAT_ACCUMULATE(6); BFLBM_FSTAT_ACCUMULATE(7); BFLBM_FSTAT_ACCUMULATE(8);
-    default: return fail("field statistic: %d variables", t->nvars);
-  }
-#undef BFLBM_FSTAT_ACCUMULATE
+  if (!field_dispatch_nv(t->fs.nvars, [&](auto nv) {
+        hipLaunchKernelGGL((k_fstat_accumulate<decltype(nv)::value>), grid, dim3(256), 0, stream, src, src_rep, q.acc, q.n, t->fs.vol, t->pairs, first_frame);
+      })) return fail("field statistic: %d variables", t->fs.nvars);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -274,19 +229,17 @@ int fstat_launch(const bflbm_fstat* t, const FstatPart& q, const double* src, lo
 // enqueue the observation and the accumulation of the resident state as frame n; no host synchronisation
 int bflbm_fstat::record() {
   const char* asker = "field statistics sample";
-  const int what = source == 0 ? 2 : (source == 1 ? 0 : 1);  // observe_launch's code
-  if (batch) {
-    if (batch_observe_launch(batch, what, sel, fields, asker)) return 1;
-    if (fstat_launch(this, part[0], fields, (long long)sel.nsel * part[0].n, batch->stream)) return 1;
-  } else if (ctx) {
-    if (observe_launch(ctx, what, ncomp, asker)) return 1;
-    if (fstat_launch(this, part[0], ctx->S[1 - ctx->cur], 0, ctx->stream)) return 1;   // [comp][z][y][x], as bflbm_sf_accumulate reads it
+  const double* dense;
+  long long rep_stride;
+  if (!ring) {
+    if (fields_observe(this, fs, fields, asker, &dense, &rep_stride)) return 1;
+    if (fstat_launch(this, part[0], dense, rep_stride, recorder_stream(this))) return 1;
   } else {
-    if (source != 1 && ring_prepare_ref(ring)) return 1;    // the global centre of mass: the slabs' own prepare_ref is then a no-op
+    if (fs.source != 1 && ring_prepare_ref(ring)) return 1; // the global centre of mass: the slabs' own prepare_ref is then a no-op
     for (size_t k = 0; k < part.size(); ++k) {
       bflbm_ctx* c = ring->ctx[k];
-      if (observe_launch(c, what, ncomp, asker)) return 1;
-      if (fstat_launch(this, part[k], c->S[1 - c->cur], 0, c->stream)) return 1;
+      if (fields_observe_slab(c, fs, asker, &dense)) return 1;
+      if (fstat_launch(this, part[k], dense, 0, c->stream)) return 1;
     }
   }
   n += 1;
@@ -345,13 +298,13 @@ int bflbm_fstat_get(bflbm_fstat* s, int what, int index, int replica, double* ds
   if (!s || !dst) return fail("bflbm_fstat_get: null argument");
   if (what < 0 || what > 4) return fail("bflbm_fstat_get: what must be 0 (sum), 1 (mean), 2 (first), 3 (prod) or 4 (cov) (got %d)", what);
   const bool of_pair = what >= 3;
-  const int most = of_pair ? s->pairs.n : s->nvars;
+  const int most = of_pair ? s->pairs.n : s->fs.nvars;
   if (index < 0 || index >= most) return fail("bflbm_fstat_get: %s %d of %d", of_pair ? "pair" : "variable slot", index, most);
   if (replica < -1 || replica >= s->nrep) return fail("bflbm_fstat_get: replica %d of %d (-1: the ensemble value)", replica, s->nrep);
   if (replica < 0 && what != 1 && what != 4) return fail("bflbm_fstat_get: only mean (1) and cov (4) have an ensemble value (what = %d)", what);
   if (s->n == 0) return fail("bflbm_fstat_get: no frame was taken yet");
   if (recorder_owner_open(s)) return fail("bflbm_fstat_get inside an open step");
-  const int nv = s->nvars, nvol = s->nvol();
+  const int nv = s->fs.nvars, nvol = s->nvol();
   const double inv_n = 1.0 / (double)s->n;
   const double inv_ens = what == 1 ? 1.0 / ((double)s->nrep * (double)s->n) : 1.0 / (double)s->nrep;
   const int a = of_pair ? s->pairs.a[index] : index, b = of_pair ? s->pairs.b[index] : index;

@@ -13,8 +13,8 @@
 // The planes are the last sum, so that a ring of z-slabs can follow the way bflbm_ring_trace_create did.  No atomics,
 // no scratch.  Not built on purpose: reading the populations in stage 1 to skip the dense intermediate; it would save
 // traffic for hydrovsbar only, whose observation is a plain moment sum.
-// The lifecycle and the sample store are those of bflbm_recorder.h.  Included by bflbm.hip after bflbm_batch_sf.h (needs
-// bflbm_ctx, bflbm_batch, ObsSel, batch_observe_launch, observe_launch).
+// The lifecycle and the sample store are those of bflbm_recorder.h, the selection that of bflbm_fieldsel.h.  Included by
+// bflbm.hip after bflbm_batch_sf.h (needs bflbm_ctx, bflbm_batch, FieldSelection, fields_observe, field_dispatch_nv).
 #ifndef BFLBM_MODES_H_
 #define BFLBM_MODES_H_
 
@@ -65,11 +65,9 @@ struct ModesStep { int mx, my, dx, dy; };
 struct bflbm_modes : bflbm_sample_store {    // d_rec [capacity][nrep][nvars][nmodes][2], d_stage [nrep][nz][tiles][nvars][nmodes][2]
   int nx = 0, ny = 0, nz = 0;
   long long nsites = 0;
-  int lb = 0;                       // 0 hydrovs, 1 hydrovsbar
-  int nvars = 0, nmodes = 0, tiles = 0;
-  ObsSel sel;                       // a batch: what the observation writes
-  ModesVars vars;                   // the volume of every variable: a batch's slot, a lone context's component
-  int ncomp = 0;                    // a lone context: the components its observation produces
+  FieldSelection fs;                // source 0 hydrovs, 1 hydrovsbar
+  int nmodes = 0, tiles = 0;
+  ModesVars vars;                   // fs.nvars and fs.vol as the projection kernel takes them
   double* fields = nullptr;         // a batch: [nrep][nsel][nsites]
   double2* d_tab = nullptr;         // T_nx[0 .. nx/2], T_ny[0 .. ny/2], T_nz[0 .. nz-1]
   ModesStep* d_step = nullptr;      // [nmodes]
@@ -214,27 +212,15 @@ __global__ void __launch_bounds__(256) k_modes_finish(const double* __restrict__
   }
 }
 
-// what every creation call refuses about its own arguments
-int modes_refuse_args(const char* call, int nvars, const int* vars, int lb_hydrovars, int nmodes, int every, long long capacity) {
-  using namespace modes_tables;
-  if (nvars < 1 || nvars > kMaxVars) return fail("%s: 1..%d variables (got %d)", call, kMaxVars, nvars);
-  if (nmodes < 1 || nmodes > kMaxModes) return fail("%s: 1..%d wavevectors (got %d)", call, kMaxModes, nmodes);
-  const int most = lb_hydrovars ? BFLBM_NHYDROBAR : BFLBM_NHYDRO;
-  for (int i = 0; i < nvars; ++i) {
-    if (vars[i] < 0 || vars[i] >= most)
-      return fail("%s: variable index %d outside %s (0..%d)", call, vars[i], lb_hydrovars ? "hydrovsbar" : "hydrovs", most - 1);
-    for (int k = 0; k < i; ++k) if (vars[k] == vars[i]) return fail("%s: variable index %d given twice", call, vars[i]);
-  }
-  return store_refuse_cadence(call, every, capacity);
-}
-
 int modes_create(bflbm_ctx* c, bflbm_batch* b, int nvars, const int* vars, int lb_hydrovars, int nmodes, const int* modes,
                  int every, long long capacity, bflbm_modes** out) {
   using namespace modes_tables;
   const char* call = b ? "bflbm_batch_modes_create" : "bflbm_modes_create";
-  if (modes_refuse_args(call, nvars, vars, lb_hydrovars, nmodes, every, capacity)) return 1;
-  if (store_refuse_owner(c, call, "bflbm_batch_modes_create", "mode trace")) return 1;
-  if (c && c->step_open()) return fail("%s inside an open step", call);
+  const int source = lb_hydrovars ? 1 : 0;
+  if (field_refuse_args(call, source, 1, nvars, vars, 0, nullptr, nullptr)) return 1;
+  if (nmodes < 1 || nmodes > kMaxModes) return fail("%s: 1..%d wavevectors (got %d)", call, kMaxModes, nmodes);
+  if (store_refuse_cadence(call, every, capacity) || store_refuse_owner(c, call, "bflbm_batch_modes_create", "mode trace")) return 1;
+  if (recorder_refuse_open(c, b, nullptr, call)) return 1;
   const Geo& G = c ? c->G : b->G;
   const int nx = G.nx, ny = G.ny, nz = G.nz;
   const int hx = nx / 2 + 1, hy = ny / 2 + 1;
@@ -247,16 +233,12 @@ int modes_create(bflbm_ctx* c, bflbm_batch* b, int nvars, const int* vars, int l
   std::unique_ptr<bflbm_modes> t(new bflbm_modes());
   const int nrep = c ? 1 : (int)b->ctx.size();
   t->nx = nx; t->ny = ny; t->nz = nz; t->nsites = (long long)nx * ny * nz;
-  t->lb = lb_hydrovars ? 1 : 0; t->nvars = nvars; t->nmodes = nmodes;
+  t->nmodes = nmodes;
   t->tiles = (nx * ny + kTile - 1) / kTile;
-  // the batch observation writes the chosen variables in ascending order; a lone context's all components up to the largest
-  t->sel.mask = 0; t->sel.nsel = 0;
-  int top = 0;
-  for (int i = 0; i < nvars; ++i) { t->sel.mask |= 1u << vars[i]; top = std::max(top, vars[i]); }
-  for (int v = 0; v < BFLBM_NHYDRO_; ++v) t->sel.slot[v] = (t->sel.mask & (1u << v)) ? t->sel.nsel++ : 0;
-  t->ncomp = t->lb ? BFLBM_NHYDROBAR : top + 1;
+  t->fs = field_select(b != nullptr, source, nvars, vars);
+  static_assert(kMaxVars == fstat_limits::kMaxVars, "ModesVars holds the selection's volumes");
   t->vars.n = nvars;
-  for (int i = 0; i < kMaxVars; ++i) t->vars.vol[i] = i < nvars ? (b ? t->sel.slot[vars[i]] : vars[i]) : 0;
+  std::copy(t->fs.vol.vol, t->fs.vol.vol + kMaxVars, t->vars.vol);
 
   std::vector<double> tab((size_t)2 * (hx + hy + nz)), full;
   const int dims[3] = {nx, ny, nz};
@@ -306,25 +288,14 @@ int bflbm_modes::record() {
   if (store_begin(this)) return 1;
   const hipStream_t stream = recorder_stream(this);
   const double* dense;
-  long long rep_stride = 0;
-  if (batch) {
-    if (batch_observe_launch(batch, lb ? 0 : 2, sel, fields, "mode trace sample")) return 1;
-    dense = fields; rep_stride = (long long)sel.nsel * nsites;
-  } else {
-    if (observe_launch(ctx, lb ? 0 : 2, ncomp, "mode trace sample")) return 1;
-    dense = ctx->S[1 - ctx->cur];                      // [comp][z][y][x], as bflbm_sf_accumulate reads it
-  }
+  long long rep_stride;
+  if (fields_observe(this, fs, fields, "mode trace sample", &dense, &rep_stride)) return 1;
   const dim3 grid((unsigned)tiles, (unsigned)nz, (unsigned)nrep);
-#define BFLBM_MODES_PROJECT(NV) \
-  case NV: hipLaunchKernelGGL((k_modes_project<NV>), grid, dim3(256), 0, stream, dense, rep_stride, nsites, d_tab, d_step, d_stage, nx, ny, nmodes, vars); break
-  switch (nvars) {
-    BFLBM_MODES_PROJECT(1); BFLBM_MODES_PROJECT(2); BFLBM_MODES_PROJECT(3); BFLBM_MODES_PROJECT(4);
-    BFLBM_MODES_PROJECT(5); BFLBM_MODES_PROJECT(6); BFLBM_MODES_PROJECT(7); BFLBM_MODES_PROJECT(8);
-    default: return fail("mode trace: %d variables", nvars);
-  }
-#undef BFLBM_MODES_PROJECT
+  if (!field_dispatch_nv(fs.nvars, [&](auto nv) {
+        hipLaunchKernelGGL((k_modes_project<decltype(nv)::value>), grid, dim3(256), 0, stream, dense, rep_stride, nsites, d_tab, d_step, d_stage, nx, ny, nmodes, vars);
+      })) return fail("mode trace: %d variables", fs.nvars);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_modes_finish, dim3((unsigned)(nvars * nmodes), (unsigned)nrep), dim3(256), 0, stream,
+  hipLaunchKernelGGL(k_modes_finish, dim3((unsigned)(fs.nvars * nmodes), (unsigned)nrep), dim3(256), 0, stream,
                      d_stage, d_tab + (nx / 2 + 1) + (ny / 2 + 1), d_mz, store_slot(this), nz, tiles, nmodes);
   HIP_TRY(hipGetLastError());
   store_recorded(this);
@@ -354,7 +325,7 @@ int bflbm_modes_read(bflbm_modes* t, long long first, long long count, double* a
 
 int bflbm_modes_geometry(const bflbm_modes* t, int* nvars, int* nmodes, int* tiles_per_plane, int* tile_sites) {
   if (!t) return fail("bflbm_modes_geometry: null argument");
-  if (nvars) *nvars = t->nvars;
+  if (nvars) *nvars = t->fs.nvars;
   if (nmodes) *nmodes = t->nmodes;
   if (tiles_per_plane) *tiles_per_plane = t->tiles;
   if (tile_sites) *tile_sites = modes_tables::kTile;

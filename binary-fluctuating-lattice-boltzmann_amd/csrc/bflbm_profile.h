@@ -18,9 +18,9 @@
 // intermediate (hydrovs needs the gradient stencil the observation already has), fusing the sums into the observation
 // kernels (it would give every observer a second form), the kinetic rho u u part of the tensor as a built-in (the
 // caller's own pairs give it).
-// The lifecycle and the sample store are those of bflbm_recorder.h.  Included by bflbm.hip after bflbm_fstat.h (needs
-// bflbm_ctx, bflbm_batch, bflbm_ring, ObsSel, batch_observe_launch, observe_launch, ring_prepare_ref, FstatVars,
-// FstatPairs, fstat_pick, fstat_aligned).
+// The lifecycle and the sample store are those of bflbm_recorder.h, the selection that of bflbm_fieldsel.h.  Included by
+// bflbm.hip after bflbm_fstat.h (needs bflbm_ctx, bflbm_batch, bflbm_ring, FieldSelection, FstatVars, FstatPairs,
+// fields_observe, field_dispatch_nv, ring_prepare_ref, fstat_pick, fstat_aligned).
 #ifndef BFLBM_PROFILE_H_
 #define BFLBM_PROFILE_H_
 
@@ -39,13 +39,10 @@ constexpr int kChunk = 64;           // axis x: rows per chunk of a column
 struct bflbm_profile : bflbm_sample_store {   // d_rec [capacity][nrep][nq][na], d_stage [nrep][nz][nq][W]
   int nx = 0, ny = 0, nz = 0;
   long long nsites = 0;
-  int source = 0;                   // 0 hydrovs, 1 hydrovsbar
+  FieldSelection fs;                // source 0 hydrovs, 1 hydrovsbar
   int axis = 2, na = 0;             // the axis and its extent
-  int nvars = 0, nq = 0;            // nq = nvars + npairs
+  int nq = 0;                       // nq = nvars + npairs
   int W = 0;                        // partials per (q, plane) that stage 1 leaves
-  int ncomp = 0;                    // a context: the components its observation produces
-  ObsSel sel;                       // a batch: what the observation writes
-  FstatVars vol;                    // the volume of every variable: a batch's slot, a context's component
   FstatPairs pairs;
   double* fields = nullptr;         // a batch: [nrep][nvars][nsites]
   // a ring: what slab k > 0 holds on its device (slab 0 writes d_stage itself; part[0] stays empty)
@@ -296,52 +293,25 @@ __global__ void __launch_bounds__(256) k_profile_finish(const double* __restrict
   out[((long long)blockIdx.y * nq + q) * na + i] = s;
 }
 
-// what every creation call refuses about its own arguments
-int profile_refuse_args(const char* call, int source, int axis, int nvars, const int* vars, int npairs, const int* pair_a, const int* pair_b,
-                        int every, long long capacity) {
-  using namespace profile_limits;
-  if (source < 0 || source > 1) return fail("%s: source must be 0 (hydrovs) or 1 (hydrovsbar) (got %d)", call, source);
-  if (axis < 0 || axis > 2) return fail("%s: axis must be 0 (x), 1 (y) or 2 (z) (got %d)", call, axis);
-  if (nvars < 1 || nvars > kMaxVars) return fail("%s: 1..%d variables (got %d)", call, kMaxVars, nvars);
-  if (npairs < 0 || npairs > kMaxPairs) return fail("%s: 0..%d pairs (got %d)", call, kMaxPairs, npairs);
-  if (npairs > 0 && (!pair_a || !pair_b)) return fail("%s: null argument", call);
-  const int most = source ? BFLBM_NHYDROBAR : BFLBM_NHYDRO;
-  for (int i = 0; i < nvars; ++i) {
-    if (vars[i] < 0 || vars[i] >= most) return fail("%s: variable index %d outside %s (0..%d)", call, vars[i], source ? "hydrovsbar" : "hydrovs", most - 1);
-    for (int k = 0; k < i; ++k) if (vars[k] == vars[i]) return fail("%s: variable index %d given twice", call, vars[i]);
-  }
-  for (int p = 0; p < npairs; ++p)
-    for (int slot : {pair_a[p], pair_b[p]})
-      if (slot < 0 || slot >= nvars) return fail("%s: pair %d: slot %d outside the %d variables", call, p, slot, nvars);
-  return store_refuse_cadence(call, every, capacity);
-}
-
 int profile_create(bflbm_ctx* c, bflbm_batch* b, bflbm_ring* g, int source, int axis, int nvars, const int* vars, int npairs,
                    const int* pair_a, const int* pair_b, int every, long long capacity, bflbm_profile** out) {
   using namespace profile_limits;
   const char* call = b ? "bflbm_batch_profile_create" : (g ? "bflbm_ring_profile_create" : "bflbm_profile_create");
-  if (profile_refuse_args(call, source, axis, nvars, vars, npairs, pair_a, pair_b, every, capacity)) return 1;
-  if (store_refuse_owner(c, call, "bflbm_batch_profile_create", "profile trace")) return 1;
-  if ((c && c->step_open()) || (g && ring_step_open(g))) return fail("%s inside an open step", call);
-  if (b) for (const bflbm_ctx* v : b->ctx) if (v->step_open()) return fail("%s: a replica has an open step", call);
+  if (field_refuse_args(call, source, 1, nvars, vars, npairs, pair_a, pair_b)) return 1;
+  if (axis < 0 || axis > 2) return fail("%s: axis must be 0 (x), 1 (y) or 2 (z) (got %d)", call, axis);
+  if (store_refuse_cadence(call, every, capacity) || store_refuse_owner(c, call, "bflbm_batch_profile_create", "profile trace")) return 1;
+  if (recorder_refuse_open(c, b, g, call)) return 1;
   const Geo& G = c ? c->G : (b ? b->G : g->ctx[0]->G);
   if (G.nz > 65535) return fail("%s: nz = %d exceeds the 65535 planes of one launch", call, G.nz);
 
   std::unique_ptr<bflbm_profile> t(new bflbm_profile());
   recorder_bind(t.get(), c, b, every, g);
   t->nx = G.nx; t->ny = G.ny; t->nz = G.nz; t->nsites = (long long)G.nx * G.ny * G.nz;
-  t->source = source; t->axis = axis; t->nvars = nvars; t->nq = nvars + npairs;
+  t->axis = axis; t->nq = nvars + npairs;
   t->na = axis == 0 ? G.nx : (axis == 1 ? G.ny : G.nz);
   t->W = axis == 2 ? (G.nx * G.ny + kTile - 1) / kTile : t->na;
-  // the batch observation writes the chosen variables in ascending order; a context's all components up to the largest
-  t->sel.mask = 0; t->sel.nsel = 0;
-  int top = 0;
-  for (int i = 0; i < nvars; ++i) { if (b) t->sel.mask |= 1u << vars[i]; top = std::max(top, vars[i]); }
-  for (int v = 0; v < BFLBM_NHYDRO_; ++v) t->sel.slot[v] = (t->sel.mask & (1u << v)) ? t->sel.nsel++ : 0;
-  t->ncomp = source ? BFLBM_NHYDROBAR : top + 1;
-  for (int i = 0; i < kMaxVars; ++i) t->vol.vol[i] = i < nvars ? (b ? t->sel.slot[vars[i]] : vars[i]) : 0;
-  t->pairs.n = npairs;
-  for (int p = 0; p < kMaxPairs; ++p) { t->pairs.a[p] = p < npairs ? pair_a[p] : 0; t->pairs.b[p] = p < npairs ? pair_b[p] : 0; }
+  t->fs = field_select(b != nullptr, source, nvars, vars);
+  t->pairs = field_pairs(npairs, pair_a, pair_b);
 
   const size_t per = (size_t)t->nrep * t->nq * t->na;
   const size_t plane_doubles = (size_t)t->nq * t->W, stage = (size_t)t->nrep * G.nz * plane_doubles;
@@ -389,14 +359,9 @@ int bflbm_profile::stage1(const double* dense, long long rep_stride, long long c
   using namespace profile_limits;
   const unsigned items = axis == 2 ? (unsigned)W : (axis == 1 ? (unsigned)((ny + 3) / 4) : (unsigned)((nx + 63) / 64));
   const dim3 grid(items, (unsigned)planes, (unsigned)reps);
-#define BFLBM_PROFILE_PLANES(NV) \
-  case NV: hipLaunchKernelGGL((k_profile_planes<NV>), grid, dim3(256), 0, stream, dense, rep_stride, comp_stride, partial, nx, ny, axis, W, vol, pairs); break
-  switch (nvars) {
-    BFLBM_PROFILE_PLANES(1); BFLBM_PROFILE_PLANES(2); BFLBM_PROFILE_PLANES(3); BFLBM_PROFILE_PLANES(4);
-    BFLBM_PROFILE_PLANES(5); BFLBM_PROFILE_PLANES(6); BFLBM_PROFILE_PLANES(7); BFLBM_PROFILE_PLANES(8);
-    default: return fail("profile trace: %d variables", nvars);
-  }
-#undef BFLBM_PROFILE_PLANES
+  if (!field_dispatch_nv(fs.nvars, [&](auto nv) {
+        hipLaunchKernelGGL((k_profile_planes<decltype(nv)::value>), grid, dim3(256), 0, stream, dense, rep_stride, comp_stride, partial, nx, ny, axis, W, fs.vol, pairs);
+      })) return fail("profile trace: %d variables", fs.nvars);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -407,14 +372,8 @@ int bflbm_profile::record() {
   if (store_begin(this)) return 1;
   const hipStream_t stream = recorder_stream(this);
   const double* dense;
-  long long rep_stride = 0;
-  if (batch) {
-    if (batch_observe_launch(batch, source ? 0 : 2, sel, fields, "profile trace sample")) return 1;
-    dense = fields; rep_stride = (long long)sel.nsel * nsites;
-  } else {
-    if (observe_launch(ctx, source ? 0 : 2, ncomp, "profile trace sample")) return 1;
-    dense = ctx->S[1 - ctx->cur];                      // [comp][z][y][x], as bflbm_sf_accumulate reads it
-  }
+  long long rep_stride;
+  if (fields_observe(this, fs, fields, "profile trace sample", &dense, &rep_stride)) return 1;
   if (stage1(dense, rep_stride, nsites, d_stage, nz, nrep, stream)) return 1;
   hipLaunchKernelGGL(k_profile_finish, dim3((unsigned)((nq * na + 255) / 256), (unsigned)nrep), dim3(256), 0, stream,
                      d_stage, store_slot(this), axis, nz, nq, W, na);
@@ -425,15 +384,16 @@ int bflbm_profile::record() {
 
 int bflbm_profile::record_ring() {
   if (store_begin(this)) return 1;
-  if (source != 1 && ring_prepare_ref(ring)) return 1;     // the global centre of mass: the slabs' own prepare_ref is then a no-op
+  if (fs.source != 1 && ring_prepare_ref(ring)) return 1;  // the global centre of mass: the slabs' own prepare_ref is then a no-op
   const int n = (int)ring->ctx.size();
   const size_t per_plane = (size_t)nq * W;
   const long long plane = (long long)nx * ny;
   for (int k = 0; k < n; ++k) {
     bflbm_ctx* c = ring->ctx[k];
-    if (observe_launch(c, source ? 0 : 2, ncomp, "profile trace sample")) return 1;   // selects the slab's device
+    const double* dense;
+    if (fields_observe_slab(c, fs, "profile trace sample", &dense)) return 1;         // selects the slab's device
     if (k > 0) HIP_TRY(hipStreamWaitEvent(c->stream, taken, 0));       // slab 0 may still be copying the last sample's block
-    if (stage1(c->S[1 - c->cur], 0, (long long)c->nzl * plane, k > 0 ? part[k].partial : d_stage, c->nzl, 1, c->stream)) return 1;
+    if (stage1(dense, 0, (long long)c->nzl * plane, k > 0 ? part[k].partial : d_stage, c->nzl, 1, c->stream)) return 1;
     if (k > 0) HIP_TRY(hipEventRecord(part[k].done, c->stream));
   }
   HIP_TRY(hipSetDevice(device));

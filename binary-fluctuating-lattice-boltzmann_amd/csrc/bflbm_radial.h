@@ -9,8 +9,8 @@
 // A sample is, on the owner's stream and without a host synchronisation,
 //   the accumulators' observation   batch_observe_launch into the trace's [B][nsel][n] / observe_launch into the scratch
 //                                   state buffer of the context, as the profile trace takes it,
-//   with a null centre              k_trace_moments(_batch) + k_trace_finish of bflbm_trace.h into the trace's own
-//                                   [nrep][12], as bflbm_shape.h does: the centre is Trace.com() of the state bit for bit,
+//   with a null centre              trace_moments_launch of bflbm_trace.h into the trace's own [nrep][12], as
+//                                   bflbm_shape.h does: the centre is Trace.com() of the state bit for bit,
 //   k_radial_shells<NV>             grid (planes, replicas): the workgroup walks the tiles of 256 sites of its plane in
 //                                   order.  Per tile every thread loads its site's variables once, forms the image
 //                                   vector, r, the shell and the projections and stages variables, projections and shell
@@ -25,9 +25,9 @@
 //                                   slot, three more write the centre.
 // No atomics, no scratch.  The loads are 8 bytes per lane (a wave reads 512 contiguous bytes of a variable): a lane owns
 // one site of a tile, so a 16-byte load would need the lane-pair exchange of bflbm_profile.h over two tiles at once.
-// The lifecycle and the sample store are those of bflbm_recorder.h.  Included by bflbm.hip after bflbm_profile.h (needs
-// bflbm_ctx, bflbm_batch, ObsSel, batch_observe_launch, observe_launch, FstatVars, fstat_pick, k_trace_moments,
-// k_trace_moments_batch, k_trace_finish, kNTrace, shape_centre).
+// The lifecycle and the sample store are those of bflbm_recorder.h, the selection that of bflbm_fieldsel.h.  Included by
+// bflbm.hip after bflbm_profile.h (needs bflbm_ctx, bflbm_batch, FieldSelection, FstatVars, fields_observe,
+// field_dispatch_nv, fstat_pick, trace_moments_launch, kNTrace, shape_centre).
 #ifndef BFLBM_RADIAL_H_
 #define BFLBM_RADIAL_H_
 
@@ -52,12 +52,9 @@ struct RadialRads { int n; int v[radial_limits::kMaxRad][3]; };
 struct bflbm_radial : bflbm_sample_store {
   Geo G;
   long long nsites = 0;
-  int source = 0;                   // 0 hydrovs, 1 hydrovsbar
-  int nvars = 0, nq = 0, nbins = 0; // nq = nvars + npairs + nrad
+  FieldSelection fs;                // source 0 hydrovs, 1 hydrovsbar
+  int nq = 0, nbins = 0;            // nq = nvars + npairs + nrad
   int W = 0;                        // tiles per plane
-  int ncomp = 0;                    // a context: the components its observation produces
-  ObsSel sel;                       // a batch: what the observation writes
-  FstatVars vol;                    // the volume of every variable: a batch's slot, a context's component
   RadialTerms terms;
   RadialRads rads;
   bool com = false;                 // the centre is the centre of mass of the cells above `threshold`
@@ -207,19 +204,9 @@ int radial_create(bflbm_ctx* c, bflbm_batch* b, int source, int nvars, const int
                   int every, long long capacity, bflbm_radial** out) {
   using namespace radial_limits;
   const char* call = b ? "bflbm_batch_radial_create" : "bflbm_radial_create";
-  if (source < 0 || source > 1) return fail("%s: source must be 0 (hydrovs) or 1 (hydrovsbar) (got %d)", call, source);
-  if (nvars < 1 || nvars > kMaxVars) return fail("%s: 1..%d variables (got %d)", call, kMaxVars, nvars);
-  if (npairs < 0 || npairs > kMaxPairs) return fail("%s: 0..%d pairs (got %d)", call, kMaxPairs, npairs);
+  if (field_refuse_args(call, source, 1, nvars, vars, npairs, pair_a, pair_b)) return 1;
   if (nrad < 0 || nrad > kMaxRad) return fail("%s: 0..%d radial terms (got %d)", call, kMaxRad, nrad);
-  if ((npairs > 0 && (!pair_a || !pair_b)) || (nrad > 0 && (!rad_w || !rad_v))) return fail("%s: null argument", call);
-  const int most = source ? BFLBM_NHYDROBAR : BFLBM_NHYDRO;
-  for (int i = 0; i < nvars; ++i) {
-    if (vars[i] < 0 || vars[i] >= most) return fail("%s: variable index %d outside %s (0..%d)", call, vars[i], source ? "hydrovsbar" : "hydrovs", most - 1);
-    for (int k = 0; k < i; ++k) if (vars[k] == vars[i]) return fail("%s: variable index %d given twice", call, vars[i]);
-  }
-  for (int p = 0; p < npairs; ++p)
-    for (int slot : {pair_a[p], pair_b[p]})
-      if (slot < 0 || slot >= nvars) return fail("%s: pair %d: slot %d outside the %d variables", call, p, slot, nvars);
+  if (nrad > 0 && (!rad_w || !rad_v)) return fail("%s: null argument", call);
   for (int u = 0; u < nrad; ++u) {
     if (rad_w[u] < -1 || rad_w[u] >= nvars) return fail("%s: radial term %d: weight slot %d outside the %d variables (-1: none)", call, u, rad_w[u], nvars);
     for (int a = 0; a < 3; ++a)
@@ -231,24 +218,18 @@ int radial_create(bflbm_ctx* c, bflbm_batch* b, int source, int nvars, const int
   if (!(std::isfinite(delta) && delta > 0.)) return fail("%s: delta must be finite and > 0 (got %g)", call, delta);
   if (nbins < 1 || nbins > kMaxBins) return fail("%s: 1..%d shells (got %d)", call, kMaxBins, nbins);
   if (store_refuse_cadence(call, every, capacity) || store_refuse_owner(c, call, "bflbm_batch_radial_create", "radial trace")) return 1;
-  if (b) for (const bflbm_ctx* v : b->ctx) if (v->step_open()) return fail("%s: a replica has an open step", call);
+  if (recorder_refuse_open(c, b, nullptr, call)) return 1;
   const Geo& G = c ? c->G : b->G;
   if (G.nz > 65535) return fail("%s: nz = %d exceeds the 65535 planes of one launch", call, G.nz);
 
   std::unique_ptr<bflbm_radial> t(new bflbm_radial());
   const int nrep = b ? (int)b->ctx.size() : 1;
   t->G = G; t->nsites = (long long)G.nx * G.ny * G.nz;
-  t->source = source; t->nvars = nvars; t->nq = nvars + npairs + nrad; t->nbins = nbins;
+  t->nq = nvars + npairs + nrad; t->nbins = nbins;
   t->W = (G.nx * G.ny + kTile - 1) / kTile;
   t->com = !centre; t->threshold = threshold; t->delta = delta;
   if (centre) std::copy(centre, centre + 3, t->centre);
-  // the batch observation writes the chosen variables in ascending order; a context's all components up to the largest
-  t->sel.mask = 0; t->sel.nsel = 0;
-  int top = 0;
-  for (int i = 0; i < nvars; ++i) { if (b) t->sel.mask |= 1u << vars[i]; top = std::max(top, vars[i]); }
-  for (int v = 0; v < BFLBM_NHYDRO_; ++v) t->sel.slot[v] = (t->sel.mask & (1u << v)) ? t->sel.nsel++ : 0;
-  t->ncomp = source ? BFLBM_NHYDROBAR : top + 1;
-  for (int i = 0; i < kMaxVars; ++i) t->vol.vol[i] = i < nvars ? (b ? t->sel.slot[vars[i]] : vars[i]) : 0;
+  t->fs = field_select(b != nullptr, source, nvars, vars);
   RadialTerms& T = t->terms;
   T.n = 0;
   for (int k = 0; k < kMaxTerms; ++k) { T.a[k] = -1; T.b[k] = -1; }
@@ -279,33 +260,15 @@ int bflbm_radial::record() {
   if (store_begin(this)) return 1;
   const hipStream_t stream = recorder_stream(this);
   const double* dense;
-  long long rep_stride = 0;
-  if (batch) {
-    if (batch_observe_launch(batch, source ? 0 : 2, sel, d_fields(), "radial trace sample")) return 1;
-    dense = d_fields(); rep_stride = (long long)sel.nsel * nsites;
-  } else {
-    if (observe_launch(ctx, source ? 0 : 2, ncomp, "radial trace sample")) return 1;
-    dense = ctx->S[1 - ctx->cur];                      // [comp][z][y][x], as the profile trace reads it
-  }
-  if (com) {
-    const dim3 sites((unsigned)nbx(), (unsigned)G.nz, (unsigned)nrep);
-    if (batch) hipLaunchKernelGGL(k_trace_moments_batch, sites, dim3(256), 0, stream, batch->d_rec, d_sums(), G, (int)batch->k, threshold);
-    else hipLaunchKernelGGL(k_trace_moments, sites, dim3(256), 0, stream, ctx->S[ctx->cur], d_sums(), G, threshold);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_trace_finish, dim3((unsigned)nrep), dim3(256), 0, stream, d_sums(), d_moments(), (int)nbx(), G.nz);
-    HIP_TRY(hipGetLastError());
-  }
+  long long rep_stride;
+  if (fields_observe(this, fs, d_fields(), "radial trace sample", &dense, &rep_stride)) return 1;
+  if (com && trace_moments_launch(ctx, batch, G, nrep, threshold, d_sums(), d_moments(), stream)) return 1;
   const double* moments = com ? d_moments() : nullptr;
   const dim3 grid((unsigned)G.nz, (unsigned)nrep);
-#define BFLBM_RADIAL_SHELLS(NV) \
-  case NV: hipLaunchKernelGGL((k_radial_shells<NV>), grid, dim3(256), 0, stream, dense, rep_stride, nsites, moments, d_planes(), \
-                              G.nx, G.ny, G.nz, centre[0], centre[1], centre[2], delta, nbins, vol, terms, rads); break
-  switch (nvars) {
-    BFLBM_RADIAL_SHELLS(1); BFLBM_RADIAL_SHELLS(2); BFLBM_RADIAL_SHELLS(3); BFLBM_RADIAL_SHELLS(4);
-    BFLBM_RADIAL_SHELLS(5); BFLBM_RADIAL_SHELLS(6); BFLBM_RADIAL_SHELLS(7); BFLBM_RADIAL_SHELLS(8);
-    default: return fail("radial trace: %d variables", nvars);
-  }
-#undef BFLBM_RADIAL_SHELLS
+  if (!field_dispatch_nv(fs.nvars, [&](auto nv) {
+        hipLaunchKernelGGL((k_radial_shells<decltype(nv)::value>), grid, dim3(256), 0, stream, dense, rep_stride, nsites, moments, d_planes(),
+                           G.nx, G.ny, G.nz, centre[0], centre[1], centre[2], delta, nbins, fs.vol, terms, rads);
+      })) return fail("radial trace: %d variables", fs.nvars);
   HIP_TRY(hipGetLastError());
   const int blk = (int)block();
   hipLaunchKernelGGL(k_radial_finish, dim3((unsigned)((3 + blk + 255) / 256), (unsigned)nrep), dim3(256), 0, stream,

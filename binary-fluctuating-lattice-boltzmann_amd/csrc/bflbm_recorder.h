@@ -6,6 +6,7 @@
 // "Recorders").  A ring serves its recorders from bflbm_ring_step only, after the bflbm_step_finish of every slab; its
 // samples carry slab 0's step counter and its records live on slab 0's device, written on slab 0's stream (field
 // statistics excepted: a per-site accumulator stays on the slab that owns the site).
+// The layer above it, what the kinds that read observed fields share, is bflbm_fieldsel.h.
 // Host code only.  Included by bflbm.hip once bflbm_ctx, bflbm_batch and bflbm_ring are complete (needs fail, HIP_TRY).
 #ifndef BFLBM_RECORDER_H_
 #define BFLBM_RECORDER_H_

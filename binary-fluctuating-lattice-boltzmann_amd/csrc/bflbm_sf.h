@@ -9,7 +9,7 @@
 // k_sf_accumulate adds a^ conj(b^)/N for every pair.  k_sf_expand produces the mean over the frames as
 // the full fft-shifted spectrum (Hermitian completion; k = 0 optionally removed) for download.
 // hipFFT is resolved with dlopen at first use: libbflbm.so itself does not depend on it.
-// Included by bflbm.hip inside its extern "C" block's translation unit (needs bflbm_ctx).
+// Included by bflbm.hip inside its extern "C" block's translation unit (needs bflbm_ctx, field_observe_code).
 #ifndef BFLBM_SF_H_
 #define BFLBM_SF_H_
 
@@ -174,7 +174,7 @@ int bflbm_sf_accumulate(bflbm_sf* s, int lb_hydrovars, int reset) {
   if (!s) return fail("null argument");
   bflbm_ctx* c = s->c;
   if (lb_hydrovars && s->nvar_fields > BFLBM_NHYDROBAR) return fail("bflbm_sf_accumulate: pair variables outside hydrovsbar");
-  if (observe_launch(c, lb_hydrovars ? 0 : 2, lb_hydrovars ? BFLBM_NHYDROBAR : s->nvar_fields, "structure factor")) return 1;
+  if (observe_launch(c, field_observe_code(lb_hydrovars ? 1 : 0), lb_hydrovars ? BFLBM_NHYDROBAR : s->nvar_fields, "structure factor")) return 1;
   if (reset && bflbm_sf_reset(s)) return 1;
   g_fft.set_stream(s->plan, c->stream);              // the context's stream may have been replaced (bflbm_set_stream) since the plan was made
   double* fields = c->S[1 - c->cur];                 // dense [comp][z][y][x]

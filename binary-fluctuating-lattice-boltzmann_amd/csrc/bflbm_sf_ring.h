@@ -161,7 +161,7 @@ int bflbm_ring_sf_accumulate(bflbm_ring_sf* s, int lb_hydrovars, int reset) {
   // 1. observe + 2-D transforms of the own planes
   for (int k = 0; k < n; ++k) {
     bflbm_ctx* c = r->ctx[k];
-    if (observe_launch(c, lb_hydrovars ? 0 : 2, lb_hydrovars ? BFLBM_NHYDROBAR : s->nvar_fields, "structure factor")) return 1;
+    if (observe_launch(c, field_observe_code(lb_hydrovars ? 1 : 0), lb_hydrovars ? BFLBM_NHYDROBAR : s->nvar_fields, "structure factor")) return 1;
     double* fields = c->S[1 - c->cur];
     g_fft.set_stream(s->slab[k].plan2d, c->stream);
     const long long nloc = (long long)c->nzl * c->G.dplane;

@@ -5,14 +5,14 @@
 // surface per frame on the host and expands its radius in spherical harmonics; the projection of the radii onto Y_lm is
 // a small host product (analysis.shape_modes).  It is the interface trace turned from columns into rays.
 // Stages, all on the owner's stream, no atomics, no LDS of their own, nothing of the owner written:
-//   1. with a null centre: k_trace_moments(_batch) + k_trace_finish of bflbm_trace.h into the recorder's own [nrep][12],
+//   1. with a null centre: trace_moments_launch of bflbm_trace.h into the recorder's own [nrep][12],
 //      so the centre is Trace.com() of the same state bit for bit;
 //   2. k_shape_density(_batch): the chosen field's density of every site into the recorder's own padded [nrep][nzs][plane]
 //      (152 B read, 8 B written per site), so that a sample point costs 8 doubles and not 8 x 19 populations;
 //   3. k_shape_rays: one ray per lane, the pairs (k-1, k) split into segments, every work item writes its first candidate;
 //   4. k_shape_finish: per ray the first non-NaN candidate in segment order, and the centre, into the sample's slot.
 // The lifecycle and the sample store are those of bflbm_recorder.h.  Included by bflbm.hip after bflbm_iface.h (needs
-// bflbm_ctx, bflbm_batch, device_cus, k_trace_moments, k_trace_moments_batch, k_trace_finish).
+// bflbm_ctx, bflbm_batch, device_cus, trace_moments_launch).
 #ifndef BFLBM_SHAPE_H_
 #define BFLBM_SHAPE_H_
 
@@ -227,14 +227,8 @@ int bflbm_shape::record() {
   const unsigned nbx = (unsigned)((G.plane + 255) / 256);
   const dim3 sites(nbx, (unsigned)G.nz, (unsigned)nrep);
   const hipStream_t stream = recorder_stream(this);
-  if (batch && batch_sync_table(batch)) return 1;                        // a sample between steps (frame 0): the records may be stale
-  if (com) {
-    if (batch) hipLaunchKernelGGL(k_trace_moments_batch, sites, dim3(256), 0, stream, batch->d_rec, d_sums(), G, (int)batch->k, threshold);
-    else hipLaunchKernelGGL(k_trace_moments, sites, dim3(256), 0, stream, ctx->S[ctx->cur], d_sums(), G, threshold);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_trace_finish, dim3((unsigned)nrep), dim3(256), 0, stream, d_sums(), d_moments(), (int)nbx, G.nz);
-    HIP_TRY(hipGetLastError());
-  }
+  if (batch && batch_sync_table(batch)) return 1;                        // for k_shape_density_batch: between steps (frame 0) the records may be stale
+  if (com && trace_moments_launch(ctx, batch, G, nrep, threshold, d_sums(), d_moments(), stream)) return 1;
   if (batch) hipLaunchKernelGGL(k_shape_density_batch, sites, dim3(256), 0, stream, batch->d_rec, d_density(), G, (int)batch->k, field);
   else hipLaunchKernelGGL(k_shape_density, sites, dim3(256), 0, stream, ctx->S[ctx->cur], d_density(), G, field);
   HIP_TRY(hipGetLastError());

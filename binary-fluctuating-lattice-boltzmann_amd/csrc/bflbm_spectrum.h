@@ -14,8 +14,9 @@
 // depends on the spectra and the chunk table alone.  No atomics, no LDS beyond the tree, no scratch.
 // A ring of z-slabs takes its samples by a slab FFT with one sorted list per slab (spectrum_tables::build_slab here, the
 // rest in bflbm_spectrum_ring.h); the handle, the per-handle calls and the two binning kernels are the ones below.
-// The lifecycle and the sample store are those of bflbm_recorder.h.  Included by bflbm.hip after bflbm_batch_sf.h (needs
-// bflbm_ctx, bflbm_batch, block_sum, FftApi, SfPairs, ObsSel, batch_observe_launch, observe_launch).
+// The lifecycle and the sample store are those of bflbm_recorder.h, the selection that of bflbm_fieldsel.h.  Included by
+// bflbm.hip after bflbm_batch_sf.h (needs bflbm_ctx, bflbm_batch, block_sum, FftApi, SfPairs, sf_pairs, FieldSelection,
+// field_select_pairs, fields_observe).
 #ifndef BFLBM_SPECTRUM_H_
 #define BFLBM_SPECTRUM_H_
 
@@ -168,12 +169,10 @@ struct bflbm_spectrum : bflbm_sample_store {  // d_rec [capacity][nrep][npairs][
   int nx = 0, ny = 0, nz = 0;
   long long nsites = 0, nk = 0;     // sites, half-spectrum size
   int kind = 0, zero_avg = 0;
-  int lb = 0;                       // 0 hydrovs, 1 hydrovsbar
   SfPairs pairs;                    // a, b: where the pair's spectra lie in `hat` of one replica
-  ObsSel sel;                       // a batch: what the observation writes
+  FieldSelection fs;                // the distinct variables of the pairs; source 0 hydrovs, 1 hydrovsbar
   std::vector<int> vars;            // a lone context: the distinct variables, in the order of their spectra
-  int nspec = 0;                    // spectra per replica: sel.nsel of a batch, vars.size() of a lone context
-  int ncomp = 0;                    // a lone context: the components its observation produces
+  int nspec = 0;                    // spectra per replica: fs.sel.nsel of a batch, vars.size() of a lone context
   int nbins = 0, max_chunks_per_bin = 0;
   long long nchunks = 0;
   std::vector<long long> count;     // [nbins]
@@ -250,11 +249,7 @@ __global__ void __launch_bounds__(256) k_spectrum_finish(const double* __restric
 int spectrum_refuse_args(const char* call, int npairs, const int* var_a, const int* var_b, int lb_hydrovars, int kind,
                          int every, long long capacity) {
   if (npairs < 1 || npairs > 32) return fail("%s: 1..32 pairs (got %d)", call, npairs);
-  const int most = lb_hydrovars ? BFLBM_NHYDROBAR : BFLBM_NHYDRO;
-  for (int p = 0; p < npairs; ++p)
-    for (int v : {var_a[p], var_b[p]})
-      if (v < 0 || v >= most)
-        return fail("%s: pair %d: variable index %d outside %s (0..%d)", call, p, v, lb_hydrovars ? "hydrovsbar" : "hydrovs", most - 1);
+  if (field_refuse_pair_vars(call, lb_hydrovars ? 1 : 0, npairs, var_a, var_b)) return 1;
   if (kind < 0 || kind > 3) return fail("%s: kind must be 0 (shells), 1, 2 or 3 (axis x, y, z) (got %d)", call, kind);
   return store_refuse_cadence(call, every, capacity);
 }
@@ -272,22 +267,12 @@ int spectrum_refuse_box(const char* call, int kind, const Geo& G, uint64_t* L) {
 void spectrum_select(bflbm_spectrum* t, const Geo& G, int npairs, const int* var_a, const int* var_b, const double* scale,
                      int lb_hydrovars, int kind, int zero_avg) {
   t->nx = G.nx; t->ny = G.ny; t->nz = G.nz; t->nk = (long long)(G.nx / 2 + 1) * G.ny * G.nz; t->nsites = (long long)G.nx * G.ny * G.nz;
-  t->kind = kind; t->zero_avg = zero_avg ? 1 : 0; t->lb = lb_hydrovars ? 1 : 0;
-  // the slots of the batch observation, or the rank among the distinct variables
-  t->sel.mask = 0; t->sel.nsel = 0;
-  for (int p = 0; p < npairs; ++p) { t->sel.mask |= 1u << var_a[p]; t->sel.mask |= 1u << var_b[p]; }
-  for (int v = 0; v < BFLBM_NHYDRO_; ++v) {
-    t->sel.slot[v] = (t->sel.mask & (1u << v)) ? t->sel.nsel++ : 0;
-    if (t->sel.mask & (1u << v)) t->vars.push_back(v);
-  }
-  t->nspec = t->sel.nsel;                                  // the same order either way: the variables ascending
-  t->ncomp = t->lb ? BFLBM_NHYDROBAR : t->vars.back() + 1;
-  t->pairs.n = npairs;
-  for (int p = 0; p < 32; ++p) {
-    t->pairs.a[p] = p < npairs ? t->sel.slot[var_a[p]] : 0;
-    t->pairs.b[p] = p < npairs ? t->sel.slot[var_b[p]] : 0;
-    t->pairs.scale[p] = (p < npairs && scale) ? scale[p] : 1.0;
-  }
+  t->kind = kind; t->zero_avg = zero_avg ? 1 : 0;
+  // the slots of the batch observation, or the rank among the distinct variables: the same order, the variables ascending
+  t->fs = field_select_pairs(lb_hydrovars ? 1 : 0, npairs, var_a, var_b);
+  for (int v = 0; v < BFLBM_NHYDRO_; ++v) if (t->fs.sel.mask & (1u << v)) t->vars.push_back(v);
+  t->nspec = t->fs.sel.nsel;
+  t->pairs = sf_pairs(t->fs.sel, npairs, var_a, var_b, scale);
 }
 
 int spectrum_create(bflbm_ctx* c, bflbm_batch* b, int npairs, const int* var_a, const int* var_b, const double* scale,
@@ -297,7 +282,7 @@ int spectrum_create(bflbm_ctx* c, bflbm_batch* b, int npairs, const int* var_a, 
   uint64_t L = 0;
   if (spectrum_refuse_args(call, npairs, var_a, var_b, lb_hydrovars, kind, every, capacity)) return 1;
   if (store_refuse_owner(c, call, "bflbm_batch_spectrum_create", "spectrum trace")) return 1;
-  if (c && c->step_open()) return fail("%s inside an open step", call);
+  if (recorder_refuse_open(c, b, nullptr, call)) return 1;
   if (spectrum_refuse_box(call, kind, G, &L)) return 1;
   const int nx = G.nx, ny = G.ny, nz = G.nz;
   const long long nk = (long long)(nx / 2 + 1) * ny * nz;
@@ -356,14 +341,14 @@ int bflbm_spectrum::record() {
   if (store_begin(this)) return 1;
   const hipStream_t stream = recorder_stream(this);
   g_fft.set_stream(plan, stream);                      // the owner's stream may have been replaced since the last sample
+  const double* dense;
+  long long rep_stride;
+  if (fields_observe(this, fs, fields, "spectrum trace sample", &dense, &rep_stride)) return 1;
   if (batch) {
-    if (batch_observe_launch(batch, lb ? 0 : 2, sel, fields, "spectrum trace sample")) return 1;
     if (g_fft.exec_d2z(plan, fields, (hipfftDoubleComplex*)hat) != HIPFFT_SUCCESS) return fail("spectrum trace: hipfftExecD2Z failed");
   } else {
-    if (observe_launch(ctx, lb ? 0 : 2, ncomp, "spectrum trace sample")) return 1;
-    double* dense = ctx->S[1 - ctx->cur];              // [comp][z][y][x], as bflbm_sf_accumulate reads it
     for (size_t v = 0; v < vars.size(); ++v)
-      if (g_fft.exec_d2z(plan, dense + (long long)vars[v] * nsites, (hipfftDoubleComplex*)(hat + (long long)v * nk)) != HIPFFT_SUCCESS)
+      if (g_fft.exec_d2z(plan, const_cast<double*>(dense) + (long long)vars[v] * nsites, (hipfftDoubleComplex*)(hat + (long long)v * nk)) != HIPFFT_SUCCESS)
         return fail("spectrum trace: hipfftExecD2Z failed");
   }
   if (nchunks > 0) {

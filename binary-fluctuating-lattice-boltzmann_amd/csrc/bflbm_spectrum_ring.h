@@ -15,7 +15,8 @@
 // What the next sample overwrites while another stream may still read it waits the other way round: a slab's 2-D
 // transforms for every other slab's `collected`, a slab's sums for slab 0's `combined`.  A record depends on the spectra,
 // the slabs' tables and the slab count alone.  No atomics, no LDS beyond the tree of k_spectrum_bin, no scratch.
-// Included by bflbm.hip after bflbm_spectrum.h (needs bflbm_ring, ring_prepare_ref, ring_force_copies, load_fft_many).
+// Included by bflbm.hip after bflbm_spectrum.h (needs bflbm_ring, ring_prepare_ref, ring_force_copies, load_fft_many,
+// fields_observe_slab).
 #ifndef BFLBM_SPECTRUM_RING_H_
 #define BFLBM_SPECTRUM_RING_H_
 
@@ -57,7 +58,7 @@ int spectrum_ring_create(bflbm_ring* g, int npairs, const int* var_a, const int*
   const Geo& G = g->ctx[0]->G;
   uint64_t L = 0;
   if (spectrum_refuse_args(call, npairs, var_a, var_b, lb_hydrovars, kind, every, capacity)) return 1;
-  if (ring_step_open(g)) return fail("%s inside an open step", call);
+  if (recorder_refuse_open(nullptr, nullptr, g, call)) return 1;
   if (spectrum_refuse_box(call, kind, G, &L)) return 1;
   const int nx = G.nx, ny = G.ny, nz = G.nz, nxc = nx / 2 + 1;
   if (ny < n) return fail("%s: fewer rows (ny = %d) than slabs (%d)", call, ny, n);
@@ -153,7 +154,7 @@ int bflbm_spectrum::record_ring() {
   bflbm_ring* g = ring;
   const int n = (int)g->ctx.size(), nxc = nx / 2 + 1;
   const size_t nv = vars.size();
-  if (!lb && ring_prepare_ref(g)) return 1;                // the global centre of mass: the slabs' own prepare_ref is then a no-op
+  if (fs.source != 1 && ring_prepare_ref(g)) return 1;                // the global centre of mass: the slabs' own prepare_ref is then a no-op
   const bool in_place = !ring_force_copies() && g->transport == 0;
   // 1. observe + 2-D transforms of the own planes
   for (int k = 0; k < n; ++k) {
@@ -161,8 +162,8 @@ int bflbm_spectrum::record_ring() {
     SpectrumSlab& q = slab[k];
     HIP_TRY(hipSetDevice(q.device));
     for (int d = 0; d < n; ++d) if (d != k) HIP_TRY(hipStreamWaitEvent(c->stream, slab[d].collected, 0));   // the last sample's h2 was taken
-    if (observe_launch(c, lb ? 0 : 2, ncomp, "spectrum trace sample")) return 1;
-    const double* dense = c->S[1 - c->cur];               // [comp][z local][y][x]
+    const double* dense;                                  // [comp][z local][y][x]
+    if (fields_observe_slab(c, fs, "spectrum trace sample", &dense)) return 1;
     const long long nloc = (long long)c->nzl * c->G.dplane;
     g_fft.set_stream(q.plan2d, c->stream);
     for (size_t v = 0; v < nv; ++v)

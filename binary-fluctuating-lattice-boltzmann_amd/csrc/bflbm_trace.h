@@ -13,7 +13,8 @@
 // with one contiguous (peer) copy after that slab's event, in global plane order; the same k_trace_finish then runs on
 // slab 0.  The summation order is a lone context's, so with the bit-exact schedules the record equals the lone trace's
 // bit for bit.  The next sample's stage 1 of a slab waits for the event that slab 0 has taken the last one's block.
-// Included by bflbm.hip after bflbm_droplet.h (needs bflbm_ctx, bflbm_batch, bflbm_ring, block_sum).
+// Included by bflbm.hip after bflbm_droplet.h (needs bflbm_ctx, bflbm_batch, bflbm_ring, block_sum,
+// batch_sync_table).  trace_moments_launch also serves the centre of mass of bflbm_shape.h and bflbm_radial.h.
 #ifndef BFLBM_TRACE_H_
 #define BFLBM_TRACE_H_
 
@@ -133,23 +134,31 @@ int trace_create(bflbm_ctx* c, bflbm_batch* b, bflbm_ring* g, int every, long lo
   return 0;
 }
 
+// The moments of a lone context (b null) or of the nrep replicas of a batch (c null) on `stream`: stage 1 into sums
+// [nrep][nz][plane blocks][kNTrace], stages 2 and 3 into out [nrep][kNTrace].  What the trace records and what the shape
+// and radial traces take their centre of mass from, so that it is Trace.com() of the same state bit for bit.
+int trace_moments_launch(const bflbm_ctx* c, bflbm_batch* b, const Geo& G, int nrep, double threshold, double* sums, double* out,
+                         hipStream_t stream) {
+  const dim3 grid((unsigned)((G.plane + 255) / 256), (unsigned)G.nz, (unsigned)nrep);
+  if (b) {
+    if (batch_sync_table(b)) return 1;                 // a sample between steps (frame 0): the records may be stale; a fresh table enqueues nothing
+    hipLaunchKernelGGL(k_trace_moments_batch, grid, dim3(256), 0, stream, b->d_rec, sums, G, (int)b->k, threshold);
+  } else {
+    hipLaunchKernelGGL(k_trace_moments, grid, dim3(256), 0, stream, c->S[c->cur], sums, G, threshold);
+  }
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_trace_finish, dim3((unsigned)nrep), dim3(256), 0, stream, sums, out, (int)grid.x, (int)grid.y);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
 
 // enqueue the reduction of the resident state into slot n; no host synchronisation
 int bflbm_trace::record() {
   if (ring) return record_ring();
   if (store_begin(this)) return 1;
-  const dim3 grid((unsigned)((G.plane + 255) / 256), (unsigned)G.nz, (unsigned)nrep);
-  const hipStream_t stream = recorder_stream(this);
-  if (batch) {
-    if (batch_sync_table(batch)) return 1;             // a sample between steps (frame 0): the records may be stale
-    hipLaunchKernelGGL(k_trace_moments_batch, grid, dim3(256), 0, stream, batch->d_rec, d_stage, G, (int)batch->k, threshold);
-  } else {
-    hipLaunchKernelGGL(k_trace_moments, grid, dim3(256), 0, stream, ctx->S[ctx->cur], d_stage, G, threshold);
-  }
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_trace_finish, dim3((unsigned)nrep), dim3(256), 0, stream, d_stage, store_slot(this), (int)grid.x, (int)grid.y);
-  HIP_TRY(hipGetLastError());
+  if (trace_moments_launch(ctx, batch, G, nrep, threshold, d_stage, store_slot(this), recorder_stream(this))) return 1;
   store_recorded(this);
   return 0;
 }

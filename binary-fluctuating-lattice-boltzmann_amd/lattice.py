@@ -160,6 +160,21 @@ class _Recorder:
     def count(self):
         return self._count()[0]
 
+    _geometry_types = (ctypes.c_int,) * 4
+
+    def _geometry(self):
+        """The numbers of <_abi>_geometry: every kind's geometry() says what they are."""
+        v = [t() for t in self._geometry_types]
+        check(self._call("geometry", *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def _window(self, first=0, count=None):
+        """(first, count, B, steps[count, B] int64 to fill) of a read of the samples first ... first + count - 1
+        (count None: all from `first`)."""
+        n, b = self._count()
+        count = n - int(first) if count is None else int(count)
+        return int(first), count, b, np.empty((max(count, 0), b), dtype=np.int64)
+
 
 class Trace(_Recorder):
     """Droplet moments of every replica recorded on the device every `every` steps through the owner (a lone
@@ -171,8 +186,7 @@ class Trace(_Recorder):
 
     def read(self):
         """(steps[count, B] int64, rec[count, B, 12]); synchronises the owner's stream."""
-        n, b = self._count()
-        steps = np.empty((n, b), dtype=np.int64)
+        _, n, b, steps = self._window()
         rec = np.empty((n, b, _lib.TRACE_NREC))
         check(self.lib.bflbm_trace_read(self._h, 0, n, _ptr(rec), _ptr(steps)))
         return steps, rec
@@ -201,16 +215,13 @@ class InterfaceTrace(_Recorder):
 
     def geometry(self):
         """(nx, ny, segments of the scan, pairs (z-1, z) per segment): which launch shape the library chose."""
-        v = [ctypes.c_int() for _ in range(4)]
-        check(self.lib.bflbm_iface_geometry(self._h, *[ctypes.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._geometry()
 
     def read(self):
         """(steps[count, B] int64, h[count, B, 2, ny, nx]), direction 0 rising, 1 falling, NaN where a column has no
         crossing; synchronises the owner's stream."""
-        n, b = self._count()
+        _, n, b, steps = self._window()
         nx, ny = self.geometry()[:2]
-        steps = np.empty((n, b), dtype=np.int64)
         h = np.empty((n, b, 2, ny, nx))
         check(self.lib.bflbm_iface_read(self._h, 0, n, _ptr(h), _ptr(steps)))
         return steps, h
@@ -256,16 +267,13 @@ class ShapeTrace(_Recorder):
 
     def geometry(self):
         """(ndir, nsteps, segments of the ray kernel, pairs (k-1, k) per segment): which launch shape the library chose."""
-        v = [ctypes.c_int() for _ in range(4)]
-        check(self.lib.bflbm_shape_geometry(self._h, *[ctypes.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._geometry()
 
     def read(self):
         """(steps[count, B] int64, centre[count, B, 3], r[count, B, ndir]): the centre used (cell indices x, y, z) and the
         radius along every ray, NaN where a ray has no crossing; synchronises the owner's stream."""
-        n, b = self._count()
+        _, n, b, steps = self._window()
         ndir = self.geometry()[0]
-        steps = np.empty((n, b), dtype=np.int64)
         rec = np.empty((n, b, 3 + ndir))
         check(self.lib.bflbm_shape_read(self._h, 0, n, _ptr(rec), _ptr(steps)))
         return steps, rec[..., :3], rec[..., 3:]
@@ -277,12 +285,85 @@ class ShapeTrace(_Recorder):
         return analysis.shape_modes(self.read()[2], self.dirs, self.weights, lmax)
 
 
-class SpectrumTrace(_Recorder):
+FSTAT_SOURCES = {"hydrovs": 0, "hydrovsbar": 1, "noise": 2}
+
+
+def fstat_variable_names(source):
+    """The component names of a field-statistics source: plotfile.variable_names for hydrovs (22) and hydrovsbar (9),
+    WriteOutNoise's fa0 .. fa18, ga0 .. ga18 for the noise moments.  FieldStats also takes fn<k> / gn<k> for fa<k> / ga<k>
+    and "rhot" for component 5 (rho + phi, the equilibrium_rhot field, which VariableNames calls p_bulk)."""
+    from . import plotfile
+    if source == 2:
+        return plotfile.noise_names("f") + plotfile.noise_names("g")
+    return plotfile.variable_names(NHYDROBAR if source == 1 else NHYDRO)
+
+
+def _ints(values):
+    """A ctypes int array of the values, of one entry at least: the library refuses a null pointer."""
+    values = list(values)
+    return (ctypes.c_int * max(len(values), 1))(*values)
+
+
+class _FieldRecorder(_Recorder):
+    """What the recorders that read observed fields share (csrc/bflbm_fieldsel.h is the library's side of it): a source,
+    variables of it by name or component index, pairs of recorded variables by name or slot, and an owner whose close()
+    detaches the recorder, which stays readable until its own close().  `_label` starts the kind's ValueErrors,
+    `_nsources` is how many of FSTAT_SOURCES the kind takes."""
+    _label, _nsources = None, 2
+
+    def _owner_closing(self):
+        """The owner's close(): the library detaches the recorder; what it recorded stays readable until close()."""
+        _unregister(self.owner, self)
+
+    def _select(self, source, variables, pairs=()):
+        """Sets source, component_names, variables (component indices) and pairs (of slots; a lone name: with itself) and
+        returns them as the library takes them: (nvars, vars, npairs, pair_a, pair_b)."""
+        accepted = {k: v for k, v in FSTAT_SOURCES.items() if v < self._nsources}
+        if source not in accepted and source not in accepted.values():
+            expected = f"one of {sorted(accepted)} or 0..2" if self._nsources == 3 else "'hydrovs' (0) or 'hydrovsbar' (1)"
+            raise ValueError(f"{self._label}: source {source!r}, expected {expected}")
+        self.source = int(accepted.get(source, source))
+        self.component_names = fstat_variable_names(self.source)
+        items = [variables] if isinstance(variables, (str, int, np.integer)) else list(variables)
+        self.variables = [self._component(v) for v in items]
+        self.pairs = [(self._slot(a), self._slot(b)) for a, b in [(p, p) if isinstance(p, str) else p for p in pairs]]
+        return (len(self.variables), _ints(self.variables), len(self.pairs),
+                _ints(p[0] for p in self.pairs), _ints(p[1] for p in self.pairs))
+
+    def _alias(self, name):
+        """A kind's own names: the component name they stand for, or the component index."""
+        return name
+
+    def _component(self, v):
+        """A variable by name or by component index of the source."""
+        v = self._alias(v) if isinstance(v, str) else int(v)
+        if not isinstance(v, str):
+            return v
+        if v not in self.component_names:
+            raise ValueError(f"{self._label}: variable {v!r}, expected one of {self.component_names} or an index")
+        return self.component_names.index(v)
+
+    def _slot(self, v):
+        """A recorded variable by name or by slot (its position in the variable list)."""
+        if not isinstance(v, str):
+            return int(v)
+        c = self._component(v)
+        if c not in self.variables:
+            raise ValueError(f"{self._label}: {v!r} is not one of the recorded variables")
+        return self.variables.index(c)
+
+    def _recorded_names(self):
+        """The recorded variables by name, in slot order."""
+        return [self.component_names[c] if 0 <= c < len(self.component_names) else str(c) for c in self.variables]
+
+
+class SpectrumTrace(_FieldRecorder):
     """The structure factor of chosen pairs of hydrodynamic variables of every sample, binned into shells in |q| or into
     |k| along one axis, recorded on the device every `every` steps through the owner (a lone single-slab BinaryLBM, a
     BatchLBM or a RingLBM) and read once: include/bflbm.h, "Spectrum traces".  Made by owner.spectrum_trace(); an owner may carry
     several.  Closing the owner detaches the trace: it stays readable until its own close()."""
     _abi = "bflbm_spectrum"
+    _geometry_types = (ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int)
 
     def __init__(self, owner, create, names_or_pairs, kind, every, capacity, lb_hydrovars, zero_avg, var_scaling):
         from . import analysis, structfact
@@ -300,14 +381,8 @@ class SpectrumTrace(_Recorder):
         if len(self.scale) != n:
             raise ValueError(f"spectrum_trace: {len(self.scale)} scalings for {n} pairs")
         self.kind, self.lb, self.zero_avg = int(analysis.SPECTRUM_KINDS.get(kind, kind)), bool(lb_hydrovars), bool(zero_avg)
-        a = (ctypes.c_int * max(n, 1))(*[p[0] for p in self.pairs])
-        b = (ctypes.c_int * max(n, 1))(*[p[1] for p in self.pairs])
         sc = (ctypes.c_double * max(n, 1))(*self.scale)
-        super().__init__(owner, create, n, a, b, sc, int(self.lb), self.kind, int(self.zero_avg), int(every), int(capacity))
-
-    def _owner_closing(self):
-        """The owner's close(): the library detaches the trace; its samples stay readable until close()."""
-        _unregister(self.owner, self)
+        super().__init__(owner, create, n, _ints(p[0] for p in self.pairs), _ints(p[1] for p in self.pairs), sc, int(self.lb), self.kind, int(self.zero_avg), int(every), int(capacity))
 
     def pair_names(self):
         names = self.names
@@ -318,9 +393,7 @@ class SpectrumTrace(_Recorder):
 
     def geometry(self):
         """(bins, pairs, chunks of the sorted index list, the most chunks any bin has): what the library built."""
-        v = [ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong(), ctypes.c_int()]
-        check(self.lib.bflbm_spectrum_geometry(self._h, *[ctypes.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._geometry()
 
     def bins(self):
         """(count[nbins] int64: full-spectrum modes per bin, q[nbins]: the bin's wave number)."""
@@ -331,9 +404,8 @@ class SpectrumTrace(_Recorder):
 
     def read(self):
         """(steps[count, B] int64, sums[count, B, npairs, nbins]); synchronises the owner's stream."""
-        n, b = self._count()
+        _, n, b, steps = self._window()
         nbins, npairs = self.geometry()[:2]
-        steps = np.empty((n, b), dtype=np.int64)
         sums = np.empty((n, b, npairs, nbins))
         check(self.lib.bflbm_spectrum_read(self._h, 0, n, _ptr(sums), _ptr(steps)))
         return steps, sums
@@ -346,111 +418,62 @@ class SpectrumTrace(_Recorder):
             return np.where(count > 0, sums / count, np.nan)
 
 
-class ModeTrace(_Recorder):
+class ModeTrace(_FieldRecorder):
     """The complex Fourier amplitudes of chosen hydrodynamic variables at chosen integer wavevectors, for every replica,
     recorded on the device every `every` steps through the owner (a lone single-slab BinaryLBM or a BatchLBM) and read
     once: include/bflbm.h, "Mode traces".  What time correlations are made of (analysis.time_correlation).  Made by
     owner.mode_trace(); an owner may carry several.  Closing the owner detaches the trace: it stays readable until its
     own close()."""
-    _abi = "bflbm_modes"
+    _abi, _label = "bflbm_modes", "mode_trace"
 
     def __init__(self, owner, create, variables, modes, every, capacity, lb_hydrovars):
-        from . import plotfile
         self.lb = bool(lb_hydrovars)
-        names = plotfile.variable_names(NHYDROBAR if self.lb else NHYDRO)
-        items = [variables] if isinstance(variables, (str, int, np.integer)) else list(variables)
-        for v in items:
-            if isinstance(v, str) and v not in names:
-                raise ValueError(f"mode_trace: variable {v!r}, expected one of {names} or an index")
-        self.variables = [names.index(v) if isinstance(v, str) else int(v) for v in items]
+        nv, va = self._select(int(self.lb), variables)[:2]
         m = np.asarray(modes)
         if m.ndim != 2 or m.shape[1] != 3 or not np.issubdtype(m.dtype, np.integer):
             raise ValueError(f"mode_trace: modes is an integer array [nmodes, 3], got shape {m.shape} of {m.dtype}")
         self.modes = np.ascontiguousarray(m, dtype=np.int32)
-        nv, nm = len(self.variables), len(self.modes)
-        va = (ctypes.c_int * max(nv, 1))(*self.variables)
+        nm = len(self.modes)
         super().__init__(owner, create, nv, va, int(self.lb), nm, self.modes.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
                          int(every), int(capacity))
 
-    def _owner_closing(self):
-        """The owner's close(): the library detaches the trace; its samples stay readable until close()."""
-        _unregister(self.owner, self)
-
     def geometry(self):
         """(variables, wavevectors, tiles per plane, sites per tile): what the library built."""
-        v = [ctypes.c_int() for _ in range(4)]
-        check(self.lib.bflbm_modes_geometry(self._h, *[ctypes.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._geometry()
 
     def read(self, first=0, count=None):
         """(steps[count, B] int64, amp[count, B, nvars, nmodes] complex128) of the samples first ... first + count - 1
         (count None: all from `first`); synchronises the owner's stream."""
-        n, b = self._count()
-        count = n - int(first) if count is None else int(count)
+        first, count, b, steps = self._window(first, count)
         nv, nm = self.geometry()[:2]
-        steps = np.empty((max(count, 0), b), dtype=np.int64)
         amp = np.empty((max(count, 0), b, nv, nm), dtype=np.complex128)
-        check(self.lib.bflbm_modes_read(self._h, int(first), count, _ptr(amp), _ptr(steps)))
+        check(self.lib.bflbm_modes_read(self._h, first, count, _ptr(amp), _ptr(steps)))
         return steps, amp
 
 
-FSTAT_SOURCES = {"hydrovs": 0, "hydrovsbar": 1, "noise": 2}
 FSTAT_WHAT = {"sum": 0, "mean": 1, "first": 2, "prod": 3, "cov": 4}
 
 
-def fstat_variable_names(source):
-    """The component names of a field-statistics source: plotfile.variable_names for hydrovs (22) and hydrovsbar (9),
-    WriteOutNoise's fa0 .. fa18, ga0 .. ga18 for the noise moments.  FieldStats also takes fn<k> / gn<k> for fa<k> / ga<k>
-    and "rhot" for component 5 (rho + phi, the equilibrium_rhot field, which VariableNames calls p_bulk)."""
-    from . import plotfile
-    if source == 2:
-        return plotfile.noise_names("f") + plotfile.noise_names("g")
-    return plotfile.variable_names(NHYDROBAR if source == 1 else NHYDRO)
-
-
-class FieldStats(_Recorder):
+class FieldStats(_FieldRecorder):
     """The running mean of chosen fields at every site over the frames taken, and chosen second moments around it,
     accumulated on the device for a lone single-slab BinaryLBM, every replica of a BatchLBM or a RingLBM:
     include/bflbm.h, "Field statistics"; analysis.field_statistics is the same arithmetic in numpy.  Made by
     owner.field_stats().  every = 0: fed by sample() only.  An owner may carry several.  Closing the owner detaches the
     recorder: it stays readable until its own close()."""
-    _abi = "bflbm_fstat"
+    _abi, _label, _nsources = "bflbm_fstat", "field_stats", 3
 
     def __init__(self, owner, create, variables, pairs, source, every):
-        if source not in FSTAT_SOURCES and source not in FSTAT_SOURCES.values():
-            raise ValueError(f"field_stats: source {source!r}, expected one of {sorted(FSTAT_SOURCES)} or 0..2")
-        self.source = int(FSTAT_SOURCES.get(source, source))
-        self.names = fstat_variable_names(self.source)
-        items = [variables] if isinstance(variables, (str, int, np.integer)) else list(variables)
-        self.variables = [self._component(v) for v in items]
-        self.pairs = [(self._slot(a), self._slot(b)) for a, b in [(p, p) if isinstance(p, str) else p for p in pairs]]   # a lone name: its variance
-        nv, npairs = len(self.variables), len(self.pairs)
-        va = (ctypes.c_int * max(nv, 1))(*self.variables)
-        pa = (ctypes.c_int * max(npairs, 1))(*[p[0] for p in self.pairs])
-        pb = (ctypes.c_int * max(npairs, 1))(*[p[1] for p in self.pairs])
-        super().__init__(owner, create, self.source, nv, va, npairs, pa, pb, int(every))
+        selection = self._select(source, variables, pairs)   # a lone name among the pairs: its variance
+        self.names = self.component_names                    # every component of the source
+        super().__init__(owner, create, self.source, *selection, int(every))
         self.shape = (owner.n[2], owner.n[1], owner.n[0])
 
-    def _component(self, v):
-        """A variable by name or by component index of the source."""
-        if not isinstance(v, str):
-            return int(v)
-        if self.source == 2 and len(v) > 2 and v[:2] in ("fn", "gn") and v[2:].isdigit():
-            v = v[0] + "a" + v[2:]
-        if self.source != 2 and v == "rhot":               # component 5, rho + phi, which VariableNames calls p_bulk
+    def _alias(self, name):
+        if self.source == 2 and len(name) > 2 and name[:2] in ("fn", "gn") and name[2:].isdigit():
+            return name[0] + "a" + name[2:]
+        if self.source != 2 and name == "rhot":            # component 5, rho + phi, which VariableNames calls p_bulk
             return 5
-        if v not in self.names:
-            raise ValueError(f"field_stats: variable {v!r}, expected one of {self.names} or an index")
-        return self.names.index(v)
-
-    def _slot(self, v):
-        """A recorded variable by name or by slot (its position in the variable list)."""
-        if not isinstance(v, str):
-            return int(v)
-        c = self._component(v)
-        if c not in self.variables:
-            raise ValueError(f"field_stats: {v!r} is not one of the recorded variables")
-        return self.variables.index(c)
+        return name
 
     def _pair(self, p):
         """A recorded pair by index or as (a, b) of names or slots."""
@@ -461,10 +484,6 @@ class FieldStats(_Recorder):
         if key not in self.pairs:
             raise ValueError(f"field_stats: the pair {p!r} is not recorded")
         return self.pairs.index(key)
-
-    def _owner_closing(self):
-        """The owner's close(): the library detaches the recorder; it stays readable until close()."""
-        _unregister(self.owner, self)
 
     def _get(self, what, index, replica):
         out = np.empty(self.shape)
@@ -493,75 +512,37 @@ class FieldStats(_Recorder):
 PROFILE_AXES = {"x": 0, "y": 1, "z": 2}
 
 
-class ProfileTrace(_Recorder):
+class ProfileTrace(_FieldRecorder):
     """The sums of chosen hydrovs / hydrovsbar variables, and of chosen products of them, over every lattice plane normal
     to one axis, for every replica, recorded on the device every `every` steps through the owner (a lone single-slab
     BinaryLBM, a BatchLBM or a RingLBM) and read once: include/bflbm.h, "Profile traces"; analysis.plane_profiles is the
     same arithmetic in numpy, analysis.pressure_profile turns the means into the pressure profile.  Made by
     owner.profile_trace(); an owner may carry several.  Closing the owner detaches the trace: it stays readable until its
     own close()."""
-    _abi = "bflbm_profile"
+    _abi, _label = "bflbm_profile", "profile_trace"
 
     def __init__(self, owner, create, variables, pairs, axis, source, every, capacity):
-        if source not in ("hydrovs", "hydrovsbar", 0, 1):
-            raise ValueError(f"profile_trace: source {source!r}, expected 'hydrovs' (0) or 'hydrovsbar' (1)")
+        selection = self._select(source, variables, pairs)   # a lone name among the pairs: its square
         if axis not in PROFILE_AXES and axis not in PROFILE_AXES.values():
             raise ValueError(f"profile_trace: axis {axis!r}, expected one of {sorted(PROFILE_AXES)} or 0..2")
-        self.source = int(FSTAT_SOURCES.get(source, source))
         self.axis = int(PROFILE_AXES.get(axis, axis))
-        self.component_names = fstat_variable_names(self.source)
-        items = [variables] if isinstance(variables, (str, int, np.integer)) else list(variables)
-        self.variables = [self._component(v) for v in items]
-        self.pairs = [(self._slot(a), self._slot(b)) for a, b in [(p, p) if isinstance(p, str) else p for p in pairs]]   # a lone name: its square
-        nv, npairs = len(self.variables), len(self.pairs)
-        va = (ctypes.c_int * max(nv, 1))(*self.variables)
-        pa = (ctypes.c_int * max(npairs, 1))(*[p[0] for p in self.pairs])
-        pb = (ctypes.c_int * max(npairs, 1))(*[p[1] for p in self.pairs])
-        super().__init__(owner, create, self.source, self.axis, nv, va, npairs, pa, pb, int(every), int(capacity))
+        super().__init__(owner, create, self.source, self.axis, *selection, int(every), int(capacity))
         self.plane_sites = owner.n[0] * owner.n[1] * owner.n[2] // owner.n[self.axis]
 
-    @property
-    def names(self):
-        """The recorded variables by name, in slot order: what analysis.pressure_profile takes."""
-        return [self.component_names[c] if 0 <= c < len(self.component_names) else str(c) for c in self.variables]
-
-    def _component(self, v):
-        """A variable by name or by component index of the source."""
-        if not isinstance(v, str):
-            return int(v)
-        if v not in self.component_names:
-            raise ValueError(f"profile_trace: variable {v!r}, expected one of {self.component_names} or an index")
-        return self.component_names.index(v)
-
-    def _slot(self, v):
-        """A recorded variable by name or by slot (its position in the variable list)."""
-        if not isinstance(v, str):
-            return int(v)
-        c = self._component(v)
-        if c not in self.variables:
-            raise ValueError(f"profile_trace: {v!r} is not one of the recorded variables")
-        return self.variables.index(c)
-
-    def _owner_closing(self):
-        """The owner's close(): the library detaches the trace; its samples stay readable until close()."""
-        _unregister(self.owner, self)
+    names = property(_FieldRecorder._recorded_names, doc="The recorded variables by name, in slot order: what analysis.pressure_profile takes.")
 
     def geometry(self):
         """(Q = variables + pairs, planes along the axis, sites of a work item, partials per (q, plane)): what the
         library built."""
-        v = [ctypes.c_int() for _ in range(4)]
-        check(self.lib.bflbm_profile_geometry(self._h, *[ctypes.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._geometry()
 
     def read(self, first=0, count=None):
         """(sums[count, B, Q, n_a], steps[count, B] int64) of the samples first ... first + count - 1 (count None: all
         from `first`); the variables first, then the pairs; synchronises the owner's stream."""
-        n, b = self._count()
-        count = n - int(first) if count is None else int(count)
+        first, count, b, steps = self._window(first, count)
         nq, na = self.geometry()[:2]
-        steps = np.empty((max(count, 0), b), dtype=np.int64)
         sums = np.empty((max(count, 0), b, nq, na))
-        check(self.lib.bflbm_profile_read(self._h, int(first), count, _ptr(sums), steps.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        check(self.lib.bflbm_profile_read(self._h, first, count, _ptr(sums), steps.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
         return sums, steps
 
     def means(self, first=0, count=None):
@@ -569,7 +550,7 @@ class ProfileTrace(_Recorder):
         return self.read(first, count)[0] / float(self.plane_sites)
 
 
-class RadialTrace(_Recorder):
+class RadialTrace(_FieldRecorder):
     """The sums of chosen hydrovs / hydrovsbar variables, of chosen products of them and of chosen projections onto the
     outward radial unit vector over the shells of width `delta` about a droplet's centre (a fixed one, or the centre of
     mass of the cells above a threshold), for every replica, recorded on the device every `every` steps through the owner
@@ -577,16 +558,10 @@ class RadialTrace(_Recorder):
     is the same arithmetic in numpy, analysis.radial_pressure, pressure_jump, radial_force_integral, fit_radial_profile
     and equimolar_radius turn the shell means into the Laplace-law inputs.  Made by owner.radial_trace(); an owner may
     carry several.  Closing the owner detaches the trace: it stays readable until its own close()."""
-    _abi = "bflbm_radial"
+    _abi, _label = "bflbm_radial", "radial_trace"
 
     def __init__(self, owner, create, variables, pairs, radials, centre, threshold, delta, nbins, source, every, capacity):
-        if source not in ("hydrovs", "hydrovsbar", 0, 1):
-            raise ValueError(f"radial_trace: source {source!r}, expected 'hydrovs' (0) or 'hydrovsbar' (1)")
-        self.source = int(FSTAT_SOURCES.get(source, source))
-        self.component_names = fstat_variable_names(self.source)
-        items = [variables] if isinstance(variables, (str, int, np.integer)) else list(variables)
-        self.variables = [self._component(v) for v in items]
-        self.pairs = [(self._slot(a), self._slot(b)) for a, b in [(p, p) if isinstance(p, str) else p for p in pairs]]   # a lone name: its square
+        selection = self._select(source, variables, pairs)   # a lone name among the pairs: its square
         self.radials = [(-1 if w is None else self._slot(w), tuple(self._slot(c) for c in v)) for w, v in radials]
         if any(len(v) != 3 for _, v in self.radials):
             raise ValueError("radial_trace: a radial term is (w, (vx, vy, vz)), w a variable or None")
@@ -595,48 +570,17 @@ class RadialTrace(_Recorder):
             raise ValueError(f"radial_trace: delta {delta} must be finite and > 0")
         if nbins is None:                                  # the shells that cover half the box diagonal
             nbins = min(128, int(np.floor(0.5 * np.sqrt(float(sum(v * v for v in owner.n))) / self.delta)) + 1)
-        nv, npairs, nrad = len(self.variables), len(self.pairs), len(self.radials)
-        va = (ctypes.c_int * max(nv, 1))(*self.variables)
-        pa = (ctypes.c_int * max(npairs, 1))(*[p[0] for p in self.pairs])
-        pb = (ctypes.c_int * max(npairs, 1))(*[p[1] for p in self.pairs])
-        rw = (ctypes.c_int * max(nrad, 1))(*[w for w, _ in self.radials])
-        rv = (ctypes.c_int * max(3 * nrad, 1))(*[c for _, v in self.radials for c in v])
+        rw, rv = _ints(w for w, _ in self.radials), _ints(c for _, v in self.radials for c in v)
         c = None if centre is None else (ctypes.c_double * 3)(*[float(v) for v in centre])
         thr = -np.inf if threshold is None else float(threshold)
-        super().__init__(owner, create, self.source, nv, va, npairs, pa, pb, nrad, rw, rv, c, thr, self.delta, int(nbins),
+        super().__init__(owner, create, self.source, *selection, len(self.radials), rw, rv, c, thr, self.delta, int(nbins),
                          int(every), int(capacity))
 
-    @property
-    def names(self):
-        """The recorded variables by name, in slot order: what analysis.radial_pressure takes."""
-        return [self.component_names[c] if 0 <= c < len(self.component_names) else str(c) for c in self.variables]
-
-    def _component(self, v):
-        """A variable by name or by component index of the source."""
-        if not isinstance(v, str):
-            return int(v)
-        if v not in self.component_names:
-            raise ValueError(f"radial_trace: variable {v!r}, expected one of {self.component_names} or an index")
-        return self.component_names.index(v)
-
-    def _slot(self, v):
-        """A recorded variable by name or by slot (its position in the variable list)."""
-        if not isinstance(v, str):
-            return int(v)
-        c = self._component(v)
-        if c not in self.variables:
-            raise ValueError(f"radial_trace: {v!r} is not one of the recorded variables")
-        return self.variables.index(c)
-
-    def _owner_closing(self):
-        """The owner's close(): the library detaches the trace; its samples stay readable until close()."""
-        _unregister(self.owner, self)
+    names = property(_FieldRecorder._recorded_names, doc="The recorded variables by name, in slot order: what analysis.radial_pressure takes.")
 
     def geometry(self):
         """(Q = variables + pairs + radial terms, shells, sites of a tile, tiles per plane): what the library built."""
-        v = [ctypes.c_int() for _ in range(4)]
-        check(self.lib.bflbm_radial_geometry(self._h, *[ctypes.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._geometry()
 
     @property
     def r(self):
@@ -647,12 +591,10 @@ class RadialTrace(_Recorder):
         """(centres[count, B, 3], counts[count, B, nbins], sums[count, B, Q, nbins], steps[count, B] int64) of the samples
         first ... first + count - 1 (count None: all from `first`): the centre used in cell indices, the sites of every
         shell, the sums of the variables, then the pairs, then the radial terms; synchronises the owner's stream."""
-        n, b = self._count()
-        count = n - int(first) if count is None else int(count)
+        first, count, b, steps = self._window(first, count)
         nq, nbins = self.geometry()[:2]
-        steps = np.empty((max(count, 0), b), dtype=np.int64)
         rec = np.empty((max(count, 0), b, 3 + (1 + nq) * nbins))
-        check(self.lib.bflbm_radial_read(self._h, int(first), count, _ptr(rec), steps.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        check(self.lib.bflbm_radial_read(self._h, first, count, _ptr(rec), steps.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
         return rec[..., :3], rec[..., 3:3 + nbins], rec[..., 3 + nbins:].reshape(rec.shape[:2] + (nq, nbins)), steps
 
     def means(self, first=0, count=None):
@@ -660,7 +602,6 @@ class RadialTrace(_Recorder):
         _, counts, sums, _ = self.read(first, count)
         with np.errstate(invalid="ignore", divide="ignore"):
             return np.where(counts[..., None, :] > 0, sums / counts[..., None, :], np.nan)
-
 
 
 # kernel schedules of include/bflbm.h (bflbm_set_schedule): "fused" = plane march with the ring densities pulled

@@ -172,6 +172,24 @@ def test_batch_record_equals_the_emulation_and_the_lattice_run_alone(pkg, n):
         lbm.close()
 
 
+def test_batch_centre_at_frame_zero_equals_the_trace(pkg):
+    """Frame 0, before any step, is when the batch's record table is stale: the radial trace's centre-of-mass launch must
+    bring the table up to date itself, whatever was sampled before it.  The box: the smallest of radial_sums.BOXES whose
+    plane is no multiple of 256 sites."""
+    n = min((b for b in rs.BOXES if (b[0] * b[1]) % 256), key=lambda b: b[0] * b[1] * b[2])
+    batch = pkg.BatchLBM(n, params=_params()[:2])
+    for v in batch.replicas:
+        _start(v, n)
+    radial = batch.radial_trace(["rho"], threshold=THRESHOLD, capacity=1)
+    moments = batch.trace(every=1, capacity=1, threshold=THRESHOLD)
+    radial.sample(); moments.sample()
+    centres, _, _, steps = radial.read()
+    com = moments.com()
+    assert steps.tolist() == [[0, 0]] and centres.shape == com.shape == (1, 2, 3)
+    assert np.isfinite(com).all() and centres.tobytes() == com.tobytes()
+    batch.close()
+
+
 # ---- 2. automatic sampling ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("owner", ["lone", "batch"])
 def test_overflow_is_refused_whole_and_reset_restarts(pkg, owner):
