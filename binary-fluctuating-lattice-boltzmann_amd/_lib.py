@@ -179,6 +179,15 @@ SIGNATURES = {
     "bflbm_profile_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
     "bflbm_profile_geometry": (ctypes.c_int, [_vp, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int)]),
     "bflbm_profile_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _P(ctypes.c_longlong)]),
+    "bflbm_hist_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int), _vp, _vp, _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_batch_hist_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int), _vp, _vp, _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_ring_hist_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int), _vp, _vp, _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_hist_destroy": (ctypes.c_int, [_vp]),
+    "bflbm_hist_sample": (ctypes.c_int, [_vp]),
+    "bflbm_hist_reset": (ctypes.c_int, [_vp]),
+    "bflbm_hist_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
+    "bflbm_hist_geometry": (ctypes.c_int, [_vp] + [_P(ctypes.c_int)] * 7),
+    "bflbm_hist_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _P(ctypes.c_longlong), _P(ctypes.c_longlong)]),
     "bflbm_radial_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
     "bflbm_batch_radial_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
     "bflbm_radial_destroy": (ctypes.c_int, [_vp]),

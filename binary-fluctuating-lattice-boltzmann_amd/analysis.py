@@ -484,6 +484,87 @@ def plane_profiles(fields, pairs=(), axis=2):
     return out
 
 
+# ---- histograms: the numpy restatement of the histogram trace (include/bflbm.h, "Histogram traces") ----
+HIST_MAX_BINS, HIST_MAX_PAIRS, HIST_MAX_COUNTERS = 4096, 4, 16384
+
+
+def histogram_blocks(nbins, pairs=()):
+    """(C, [(offset, length)]) of a sample of include/bflbm.h, "Histogram traces": per variable nbins_v bins + below,
+    above, nan; then per pair (a, b) of slots nbins_a x nbins_b cells + outside."""
+    nbins = [int(n) for n in nbins]
+    lengths = [n + 3 for n in nbins] + [nbins[int(a)] * nbins[int(b)] + 1 for a, b in pairs]
+    offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(int).tolist()
+    return offsets[-1], list(zip(offsets[:-1], lengths))
+
+
+def _bin_indices(x, lo, hi, nbins):
+    """The counter of every value within its variable's block: 0 .. nbins-1 a bin, nbins below, nbins + 1 above,
+    nbins + 2 nan."""
+    scale = np.float64(nbins) / (np.float64(hi) - np.float64(lo))
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = x - np.float64(lo)                             # the subtraction first ...
+        t = d * scale                                      # ... the multiplication second
+        nan, below, above = np.isnan(t), t < 0.0, t >= np.float64(nbins)
+    inside = ~(nan | below | above)
+    idx = np.where(inside, t, 0.0).astype(np.int64)        # truncation
+    idx[above] = nbins + 1
+    idx[below] = nbins
+    idx[nan] = nbins + 2
+    return idx
+
+
+def field_histograms(fields, lo, hi, nbins, pairs=()):
+    """counts[C] int64 of include/bflbm.h, "Histogram traces", in numpy, operation for operation (float64 subtract,
+    multiply, compare, truncate): fields[nvars, ...] of one replica, lo[nvars], hi[nvars], nbins[nvars], pairs a list of
+    (a, b) of variable slots, a != b.  The layout is histogram_blocks(nbins, pairs)."""
+    x = np.asarray(fields, dtype=np.float64)
+    nv = len(x)
+    lo, hi = np.asarray(lo, dtype=np.float64).reshape(-1), np.asarray(hi, dtype=np.float64).reshape(-1)
+    nbins = [int(n) for n in np.asarray(nbins).reshape(-1)]
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    if x.ndim < 2 or not (1 <= nv <= 8) or not (len(lo) == len(hi) == len(nbins) == nv):
+        raise ValueError(f"field_histograms: fields[1..8 variables, ...] with lo, hi, nbins per variable, got {x.shape}, {len(lo)}, {len(hi)}, {len(nbins)}")
+    for v in range(nv):
+        if not (np.isfinite(lo[v]) and np.isfinite(hi[v]) and hi[v] > lo[v]):
+            raise ValueError(f"field_histograms: variable slot {v}: the range needs finite lo < hi (got {lo[v]}, {hi[v]})")
+        if not (1 <= nbins[v] <= HIST_MAX_BINS):
+            raise ValueError(f"field_histograms: variable slot {v}: 1..{HIST_MAX_BINS} bins (got {nbins[v]})")
+        with np.errstate(over="ignore", divide="ignore"):
+            scale = np.float64(nbins[v]) / (hi[v] - lo[v])
+        if not (np.isfinite(scale) and scale > 0):
+            raise ValueError(f"field_histograms: variable slot {v}: the scale nbins / (hi - lo) = {scale} is not finite and positive")
+    if len(pairs) > HIST_MAX_PAIRS or any(not (0 <= a < nv and 0 <= b < nv) or a == b for a, b in pairs):
+        raise ValueError(f"field_histograms: 0..{HIST_MAX_PAIRS} pairs of two different slots of the {nv} variables: {pairs}")
+    total, blocks = histogram_blocks(nbins, pairs)
+    if total > HIST_MAX_COUNTERS:
+        raise ValueError(f"field_histograms: {total} counters exceed {HIST_MAX_COUNTERS}")
+    idx = [_bin_indices(x[v].reshape(-1), lo[v], hi[v], nbins[v]) for v in range(nv)]
+    out = np.zeros(total, dtype=np.int64)
+    for v in range(nv):
+        off, n = blocks[v]
+        out[off:off + n] = np.bincount(idx[v], minlength=n)
+    for p, (a, b) in enumerate(pairs):
+        off, n = blocks[nv + p]
+        both = (idx[a] < nbins[a]) & (idx[b] < nbins[b])
+        cell = np.where(both, idx[a] * nbins[b] + idx[b], n - 1)
+        out[off:off + n] = np.bincount(cell, minlength=n)
+    return out
+
+
+def histogram_moments(counts, lo, hi):
+    """(mean, variance) of the in-range counts[..., nbins] from the bin centres lo + (k + 1/2) (hi - lo) / nbins; NaN
+    where no site is in range.  Every value lies within half a bin width of its centre, so the mean is within half a
+    bin width of the mean of the in-range values."""
+    c = np.asarray(counts, dtype=np.float64)
+    n = c.shape[-1]
+    centres = float(lo) + (np.arange(n) + 0.5) * ((float(hi) - float(lo)) / n)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        total = c.sum(axis=-1)
+        mean = (c * centres).sum(axis=-1) / total
+        var = (c * (centres - mean[..., None]) ** 2).sum(axis=-1) / total
+    return mean, var
+
+
 PRESSURE_VARIABLES = ["rho", "phi", "afx", "afy", "afz", "agx", "agy", "agz"]
 PRESSURE_PAIRS = [("rho", "phi"), ("afx", "agx"), ("afy", "agy"), ("afz", "agz")]
 

@@ -1742,4 +1742,5 @@ int bflbm_fused_plan_query(const int n[3], int nreplicas, int noise, int compute
 #include "bflbm_modes.h"
 #include "bflbm_fstat.h"
 #include "bflbm_profile.h"
+#include "bflbm_hist.h"
 #include "bflbm_radial.h"

@@ -550,6 +550,96 @@ class ProfileTrace(_FieldRecorder):
         return self.read(first, count)[0] / float(self.plane_sites)
 
 
+class HistogramTrace(_FieldRecorder):
+    """The counts of the sites of chosen hydrovs / hydrovsbar / noise variables over fixed bins, and of chosen pairs of
+    them over the product of two binnings, for every replica, recorded on the device as 64-bit integers every `every`
+    steps through the owner (a lone single-slab BinaryLBM, a BatchLBM or a RingLBM; the noise source not on a batch) and
+    read once: include/bflbm.h, "Histogram traces"; analysis.field_histograms is the same rule in numpy.  `ranges` is
+    {variable: (lo, hi, nbins)} with the names of fstat_variable_names (or component indices) in recording order, `pairs`
+    a list of (a, b) of recorded variables by name or slot.  Made by owner.histogram_trace(); an owner may carry several.
+    Closing the owner detaches the trace: it stays readable until its own close()."""
+    _abi, _label, _nsources = "bflbm_hist", "histogram_trace", 3
+    _alias = FieldStats._alias
+
+    def __init__(self, owner, create, ranges, pairs, source, every, capacity):
+        items = list(ranges.items()) if hasattr(ranges, "items") else [(v, r) for v, *r in ranges]
+        if any(len(r) != 3 for _, r in items):
+            raise ValueError("histogram_trace: ranges = {variable: (lo, hi, nbins)}")
+        selection = self._select(source, [v for v, _ in items], [tuple(p) for p in pairs])
+        self.lo = np.array([float(r[0]) for _, r in items], dtype=np.float64)
+        self.hi = np.array([float(r[1]) for _, r in items], dtype=np.float64)
+        self.nbins = [int(r[2]) for _, r in items]
+        nv, va, npairs, pa, pb = selection
+        lo, hi = (self.lo, self.hi) if nv else (np.zeros(1), np.ones(1))
+        super().__init__(owner, create, self.source, nv, va, _ptr(lo), _ptr(hi), _ints(self.nbins), npairs, pa, pb, int(every), int(capacity))
+        self.sites = owner.n[0] * owner.n[1] * owner.n[2]
+
+    names = property(_FieldRecorder._recorded_names, doc="The recorded variables by name, in slot order.")
+
+    def geometry(self):
+        """(C, [(offset, length) of every block: the variables, then the pairs], sites of a work item, workgroups per
+        replica of the counting launch, 32-bit LDS counters of a workgroup): what the library built."""
+        scalars = [ctypes.c_int() for _ in range(5)]
+        off, length = (ctypes.c_int * 12)(), (ctypes.c_int * 12)()
+        c, nb, tile, groups, lds = [ctypes.byref(x) for x in scalars]
+        check(self._call("geometry", c, nb, off, length, tile, groups, lds))
+        nblocks = scalars[1].value
+        return (scalars[0].value, [(off[k], length[k]) for k in range(nblocks)]) + tuple(x.value for x in scalars[2:])
+
+    def _block(self, k):
+        return self.geometry()[1][k]
+
+    def _pair(self, p):
+        """A recorded pair by index or as (a, b) of names or slots."""
+        if isinstance(p, (int, np.integer)):
+            return int(p)
+        key = (self._slot(p[0]), self._slot(p[1]))
+        if key not in self.pairs:
+            raise ValueError(f"histogram_trace: the pair {p!r} is not recorded")
+        return self.pairs.index(key)
+
+    def read(self, first=0, count=None):
+        """(steps[count, B] int64, counts[count, B, C] int64) of the samples first ... first + count - 1 (count None: all
+        from `first`); synchronises the owner's stream."""
+        first, count, b, steps = self._window(first, count)
+        counts = np.empty((max(count, 0), b, self.geometry()[0]), dtype=np.int64)
+        as_ll = ctypes.POINTER(ctypes.c_longlong)
+        check(self.lib.bflbm_hist_read(self._h, first, count, counts.ctypes.data_as(as_ll), steps.ctypes.data_as(as_ll)))
+        return steps, counts
+
+    def hist(self, v):
+        """The bins of a variable (name or slot) [count, B, nbins_v]."""
+        off, n = self._block(self._slot(v))
+        return self.read()[1][..., off:off + n - 3]
+
+    def outliers(self, v):
+        """(below, above, nan) of a variable [count, B, 3]."""
+        off, n = self._block(self._slot(v))
+        return self.read()[1][..., off + n - 3:off + n]
+
+    def joint(self, p):
+        """(cells[count, B, na, nb], outside[count, B]) of a pair (index, or (a, b) of names or slots)."""
+        p = self._pair(p)
+        off, n = self._block(len(self.variables) + p)
+        rec = self.read()[1]
+        na, nb = self.nbins[self.pairs[p][0]], self.nbins[self.pairs[p][1]]
+        return rec[..., off:off + n - 1].reshape(rec.shape[:2] + (na, nb)), rec[..., off + n - 1]
+
+    def edges(self, v):
+        """The nbins_v + 1 bin edges lo + k (hi - lo) / nbins of a variable, for plotting: membership is by the rule of
+        include/bflbm.h, which these reproduce up to rounding."""
+        s = self._slot(v)
+        return self.lo[s] + (self.hi[s] - self.lo[s]) * np.arange(self.nbins[s] + 1) / self.nbins[s]
+
+    def pdf(self, v):
+        """The in-range counts divided by (in-range count x bin width) [count, B, nbins_v]; NaN where no site is in range."""
+        s = self._slot(v)
+        h = self.hist(s).astype(np.float64)
+        width = (self.hi[s] - self.lo[s]) / self.nbins[s]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return h / (h.sum(axis=-1, keepdims=True) * width)
+
+
 class RadialTrace(_FieldRecorder):
     """The sums of chosen hydrovs / hydrovsbar variables, of chosen products of them and of chosen projections onto the
     outward radial unit vector over the shells of width `delta` about a droplet's centre (a fixed one, or the centre of
@@ -862,6 +952,12 @@ class BinaryLBM(_DropletMixin):
         16 pairs of them (names or slots; a lone name is its square): ProfileTrace."""
         return ProfileTrace(self, "bflbm_profile_create", variables, pairs, axis, source, every, capacity)
 
+    def histogram_trace(self, ranges, pairs=(), source="hydrovs", every=1, capacity=64):
+        """Counts of the sites of chosen variables over fixed bins and of pairs of them over two binnings, recorded on the
+        device every `every` steps: ranges = {variable: (lo, hi, nbins)} of up to 8 variables of `source` ("hydrovs",
+        "hydrovsbar" or "noise"), up to 4 pairs (a, b) of them by name or slot: HistogramTrace."""
+        return HistogramTrace(self, "bflbm_hist_create", ranges, pairs, source, every, capacity)
+
     def radial_trace(self, variables, pairs=(), radials=(), centre=None, threshold=None, delta=1.0, nbins=None, source="hydrovs",
                      every=1, capacity=64):
         """Record, after every `every`-th step, the sums over the shells of width `delta` (cells) about `centre` (cell
@@ -1062,6 +1158,11 @@ class RingLBM(_DropletMixin):
         slab 0 finishes; the record is a lone lattice's bit for bit."""
         return ProfileTrace(self, "bflbm_ring_profile_create", variables, pairs, axis, source, every, capacity)
 
+    def histogram_trace(self, ranges, pairs=(), source="hydrovs", every=1, capacity=64):
+        """Bin counts of variables and pairs (BinaryLBM.histogram_trace): every slab counts its own planes, slab 0 adds
+        the slabs' totals."""
+        return HistogramTrace(self, "bflbm_ring_hist_create", ranges, pairs, source, every, capacity)
+
     def _gather(self, ncomp, call):
         out = np.empty((ncomp, self.n[2], self.n[1], self.n[0]))
         fab = make_fab((0, 0, 0), (self.n[0] - 1, self.n[1] - 1, self.n[2] - 1))
@@ -1261,6 +1362,11 @@ class BatchLBM:
         """Every replica's plane sums along one axis (BinaryLBM.profile_trace) after every `every`-th batch step, with one
         observation launch, one plane launch and one finishing launch per sample."""
         return ProfileTrace(self, "bflbm_batch_profile_create", variables, pairs, axis, source, every, capacity)
+
+    def histogram_trace(self, ranges, pairs=(), source="hydrovs", every=1, capacity=64):
+        """Every replica's bin counts (BinaryLBM.histogram_trace) after every `every`-th batch step, with one counting
+        launch over all replicas; the noise source is not available on a batch."""
+        return HistogramTrace(self, "bflbm_batch_hist_create", ranges, pairs, source, every, capacity)
 
     def radial_trace(self, variables, pairs=(), radials=(), centre=None, threshold=None, delta=1.0, nbins=None, source="hydrovs",
                      every=1, capacity=64):

@@ -808,6 +808,91 @@ int bflbm_profile_read(bflbm_profile* t, long long first, long long count,
                        double* sums /* [count][nreplicas][Q][n_a] */,
                        long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
 
+/* ---- Histogram traces: the counts of the sites of chosen fields over fixed bins, and of chosen pairs of fields over the
+ * product of two binnings, recorded on the device as a time series of 64-bit integers and read once at the end.  Every
+ * other recorder reduces a sample to sums; this one records a distribution: the single-site velocity PDF against
+ * Maxwell-Boltzmann and the PDF of the noise modes themselves, P(rho) and P(phi) turning bimodal while a mixture demixes
+ * (Mixture.ipynb, Correlation.ipynb), the occupancy of the (rho, phi) plane, and what the reference's drivers print first
+ * (compute_multifab_fluctuation, PrintDensityFluctuation, MultiFabNANCheck, Debug.H:136-228): is the field still finite,
+ * and how wide is it.  A histogram trace is attached to one lone single-slab context, one replica batch or one ring.
+ *  - definition (stated here and nowhere else).  Inputs: a source (0: hydrovs, 22 components; 1: hydrovsbar, 9
+ *    components; 2: the noise moments of bflbm_get_noise, 38 components, 0..18 of fluid f, 19..37 of fluid g; a lone
+ *    context or a ring only), nvars in 1..8 distinct component indices of that source, per variable slot v a range
+ *    lo_v < hi_v, both finite, and nbins_v in 1..4096, and npairs in 0..4 pairs (a, b) of variable SLOTS, a != b.
+ *    Binning rule for variable v and a site value x, every operation an IEEE double operation:
+ *      scale_v = (double)nbins_v / (hi_v - lo_v)        once on the host, one division; must be finite and positive
+ *      t = (x - lo_v) * scale_v                          the subtraction first, the multiplication second, never
+ *                                                        contracted or reassociated (-ffp-contract=off)
+ *      t is NaN: the site goes to the variable's `nan` counter; else t < 0: to `below`; else t >= nbins_v: to `above`;
+ *      else to bin (int)t.
+ *    So -0.0 lands in bin 0 of a range from 0, +inf in `above`, -inf in `below`, and a value just under hi_v whose t
+ *    rounds to nbins_v in `above`: that is the rule, not an error.  A pair uses its two slots' own binnings: the site
+ *    goes to cell [ia][ib] when both coordinates are in a bin, and to the pair's single `outside` counter otherwise.
+ *    analysis.field_histograms restates this in numpy, operation for operation.
+ *  - sample: per replica C 64-bit signed counts: per variable, in slot order, nbins_v bins, then below, above, nan;
+ *    then per pair nbins_a x nbins_b cells in row-major order ([ia][ib]), then outside.  C <= 16384.  Every variable
+ *    block and every pair block of a sample sums to nx ny nz.  The sums are of integers: a record does not depend on
+ *    the number of replicas, `every`, the capacity, the schedule, the slab count, what else is attached, lone context
+ *    versus replica, or the launch geometry.
+ *  - bflbm_hist_geometry reports C, the number of blocks nvars + npairs, the offset and the length of every block (the
+ *    variables first, then the pairs; arrays of nvars + npairs entries, at most 12), the sites of a work item (2048),
+ *    the workgroups per replica of the counting launch over the whole box (a slab of a ring launches its own share)
+ *    and the 32-bit LDS counters of the instantiation that serves C (4096 for C <= 4096, else 16384).
+ *  - how a sample is taken, on the owner's stream and without a host synchronisation: the accumulators' observation,
+ *    exactly as the profile trace takes it (source 2 as the field statistics take it); ONE counting launch, compiled
+ *    once per number of variables and per LDS size, grid (workgroups, 1, replicas) of 256 threads: a workgroup keeps all
+ *    C counters of its replica as 32-bit words in LDS (16384 bytes for C <= 4096, else 65536 bytes: two workgroups in a
+ *    CU's 160 KiB) and strides over the tiles of 2048 consecutive sites of the replica's dense volume; a thread takes
+ *    two neighbouring sites per turn, loads their variables once (one 16-byte access per variable where the volume is
+ *    16-byte aligned and both sites exist, 8-byte loads otherwise), derives every bin index and every pair cell from
+ *    those registers and adds 1 to each counter in LDS (one add per run of equal counters within a wave, the remedy for
+ *    a zero-noise mixture whose every lane meets the same counter, was measured and was no faster: DESIGN.md section 8);
+ *    at its end the workgroup adds every non-zero counter to the replica's 64-bit totals with one global integer add
+ *    each (this form ships; a [workgroups][C] stage buffer was not built).  The workgroups per replica are
+ *    min(tiles, max(1, 512 / replicas)), raised where a workgroup would otherwise meet 2^31 sites, so that no 32-bit
+ *    counter can wrap before it is flushed.  Then ONE finishing launch writes the totals straight into the slot
+ *    [sample][replica][C] and sets them back to zero.  No scratch.
+ *  - a ring of z-slabs: every slab counts its own planes on its own stream into its own [C] 64-bit totals and finishes
+ *    them into a block of its own; slab 0 takes each block with one (peer) copy after that slab's event and its
+ *    finishing launch adds them to its own totals into the slot (the ensemble trace's scheme, events in both directions,
+ *    no host synchronisation).  With the bit-exact schedules the record equals the lone lattice's exactly.  A ring of one
+ *    slab gets the lone recorder of its only context.  Slabs stepped by hand are not served.
+ *  - what is touched on the owner: what the profile trace's observation touches.  Observing hydrovs rewrites rho / phi by
+ *    the density pass where they are stale; a context's scratch state buffer is overwritten.  The resident state, the
+ *    step counters and everything the owner computes are unchanged.
+ *  - sampling rule, capacity, step labels, order among the recorders of one owner: those of the other traces ("histogram
+ *    trace full").  An owner may carry any number of histogram traces; other bins for a pair: a second trace.
+ *  - refused at creation (non-zero return, a message naming the call, before any launch, nothing allocated, the owner's
+ *    recorder list untouched): null arguments (the range and bin arrays included), a source outside 0..2, nvars outside
+ *    1..8, npairs outside 0..4, a repeated variable, a component index outside its source, a pair slot outside
+ *    0..nvars-1, a pair of a slot with itself, a non-finite lo or hi, hi <= lo, a scale that is not finite and positive,
+ *    nbins outside 1..4096, C > 16384, every < 1, capacity < 1, a capacity beyond 1 TB of records, source 2 on a batch
+ *    (its observation has no noise form), a replica view (use bflbm_batch_hist_create), a context with nranks > 1, an
+ *    open step, a failed allocation (the message gives the bytes of each buffer).  An open step also refuses
+ *    bflbm_hist_sample, _reset and _read.
+ *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_hist_read, _count,
+ *    _geometry and _destroy still work, bflbm_hist_sample fails.  bflbm_hist_destroy(NULL) returns 0.
+ *  - only bflbm_hist_read and bflbm_hist_destroy synchronise the owner's stream (a ring: destroy every slab's). */
+typedef struct bflbm_hist bflbm_hist;
+int bflbm_hist_create(bflbm_ctx* c, int source, int nvars, const int* vars, const double* lo /* [nvars] */, const double* hi,
+                      const int* nbins, int npairs, const int* pair_a /* or NULL if npairs == 0 */, const int* pair_b,
+                      int every, long long capacity, bflbm_hist** out);
+int bflbm_batch_hist_create(bflbm_batch* b, int source, int nvars, const int* vars, const double* lo, const double* hi,
+                            const int* nbins, int npairs, const int* pair_a, const int* pair_b,
+                            int every, long long capacity, bflbm_hist** out);
+int bflbm_ring_hist_create(bflbm_ring* r, int source, int nvars, const int* vars, const double* lo, const double* hi,
+                           const int* nbins, int npairs, const int* pair_a, const int* pair_b,
+                           int every, long long capacity, bflbm_hist** out);
+int bflbm_hist_destroy(bflbm_hist* t);
+int bflbm_hist_sample(bflbm_hist* t);                      /* record the resident state now (e.g. frame 0) */
+int bflbm_hist_reset(bflbm_hist* t);                       /* forget the samples, restart the every-counter */
+int bflbm_hist_count(const bflbm_hist* t, long long* nsamples, int* nreplicas);
+int bflbm_hist_geometry(const bflbm_hist* t, int* ncounters /* C */, int* nblocks, int* offsets /* [nvars + npairs] */,
+                        int* lengths /* [nvars + npairs] */, int* tile_sites, int* groups, int* lds_counters);
+int bflbm_hist_read(bflbm_hist* t, long long first, long long count,
+                    long long* counts /* [count][nreplicas][C] */,
+                    long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
+
 /* ---- Radial traces: the sums of chosen fields, of chosen products of them and of chosen projections onto the outward
  * radial unit vector, over the shells of width delta about a droplet's centre, recorded on the device as a time series
  * and read once at the end.  Surface_Tension.ipynb's droplet route needs, per droplet, the pressure inside and outside
