@@ -23,8 +23,7 @@
 // and a zero-noise mixture puts a whole wave into one bin; one add per run of equal counters within a wave was built and
 // measured against the plain add and lost, so the plain add ships.
 // A ring: every slab counts its own planes on its own stream into its own totals and finishes them into its own [C] block;
-// slab 0 takes each block with one peer copy after that slab's event and adds them into the slot (the scheme of
-// bflbm_trace.h, events in both directions, no host synchronisation).
+// slab 0 takes the blocks side by side into `incoming` (the ring gather of bflbm_recorder.h) and adds them into the slot.
 // Not built on purpose: automatic ranges or adaptive bins, running minima and maxima, weighted histograms, fusing the
 // counting into the observation kernels, a noise source on batches, histograms over more than two variables.
 // Host part: plain C++17 beside field_select that needs bflbm_fieldsel.h's host part and a declared int fail(const char*,
@@ -148,6 +147,7 @@ inline long long hist_groups(long long sites, int nrep) {
 #ifndef BFLBM_HIST_HOST_ONLY
 
 #include <memory>
+#include <string>
 #include <vector>
 
 struct bflbm_hist : bflbm_sample_store {     // d_rec [capacity][nrep][C] as long long, d_stage: the totals [nrep][C]
@@ -156,24 +156,18 @@ struct bflbm_hist : bflbm_sample_store {     // d_rec [capacity][nrep][C] as lon
   FieldSelection fs;                // source 0 hydrovs, 1 hydrovsbar, 2 noise
   HistLayout L;
   double* fields = nullptr;         // a batch: [nrep][nvars][nsites]
-  // a ring: what slab k > 0 holds on its device, and where slab 0 receives it (incoming [nslabs - 1][C])
-  struct Part { int device = 0; unsigned long long* totals = nullptr; long long* block = nullptr; hipEvent_t done = nullptr; };
-  std::vector<Part> part;
+  // a ring: slab k > 0 counts into slab_totals[k] [C] on its device and finishes them into its block [C] of the gather,
+  // which slab 0 receives in incoming [nslabs - 1][C]
+  RingGather gather;
+  std::vector<unsigned long long*> slab_totals;
   long long* incoming = nullptr;
-  hipEvent_t taken = nullptr;       // slab 0 has copied every slab's block
   bflbm_hist() : bflbm_sample_store("histogram trace", "bflbm_hist") {}
   ~bflbm_hist() override {
-    for (Part& q : part) {
-      if (!q.totals && !q.block && !q.done) continue;
-      hipSetDevice(q.device);
-      if (q.totals) hipFree(q.totals);
-      if (q.block) hipFree(q.block);
-      if (q.done) hipEventDestroy(q.done);
-    }
-    if (fields || incoming || taken) hipSetDevice(device);
+    for (size_t k = 1; k < slab_totals.size(); ++k)
+      if (slab_totals[k]) { hipSetDevice(gather.part[k].device); hipFree(slab_totals[k]); }
+    if (fields || incoming) hipSetDevice(device);
     if (fields) hipFree(fields);
     if (incoming) hipFree(incoming);
-    if (taken) hipEventDestroy(taken);
   }
   unsigned long long* totals() const { return reinterpret_cast<unsigned long long*>(d_stage); }
   int record() override;
@@ -291,42 +285,40 @@ int hist_create(bflbm_ctx* c, bflbm_batch* b, bflbm_ring* g, int source, int nva
   t->L = hist_layout(nvars, lo, hi, nbins, npairs, pair_a, pair_b);
 
   const size_t per = (size_t)t->nrep * t->L.C;
-  if ((unsigned long long)capacity > ((1ULL << 40) / sizeof(long long)) / per)
-    return fail("%s: capacity %lld x %d replicas x %d counters exceeds 1 TB of records", call, capacity, t->nrep, t->L.C);
-  const size_t rb = (size_t)capacity * per * sizeof(long long), sb = per * sizeof(long long);
+  const std::string shape = " x " + std::to_string(t->L.C) + " counters";
+  if (store_refuse_capacity(call, capacity, per, t->nrep, shape.c_str())) return 1;      // before the fields of a batch
+  const size_t sb = per * sizeof(long long);
   const size_t fb = b ? (size_t)t->nrep * nvars * (size_t)t->nsites * sizeof(double) : 0;
   const size_t cb = (size_t)t->L.C * sizeof(long long);      // a ring: one slab's block
   const size_t ib = g ? (g->ctx.size() - 1) * cb : 0;
   hipError_t e = hipSetDevice(t->device);
-  if (e == hipSuccess) e = hipMalloc((void**)&t->d_rec, rb);
-  if (e == hipSuccess) e = hipMalloc((void**)&t->d_stage, sb);
   if (e == hipSuccess && fb) e = hipMalloc((void**)&t->fields, fb);
-  if (e == hipSuccess) e = hipMemsetAsync(t->d_stage, 0, sb, recorder_stream(t.get()));
   if (e == hipSuccess && g) {
     e = hipMalloc((void**)&t->incoming, ib);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->taken, hipEventDisableTiming);
-    t->part.resize(g->ctx.size());
-    for (size_t k = 1; k < g->ctx.size() && e == hipSuccess; ++k) {
-      bflbm_hist::Part& q = t->part[k];
-      q.device = g->ctx[k]->dom.device;
-      e = hipSetDevice(q.device);
-      if (e == hipSuccess) e = hipMalloc((void**)&q.totals, cb);
-      if (e == hipSuccess) e = hipMalloc((void**)&q.block, cb);
-      if (e == hipSuccess) e = hipMemsetAsync(q.totals, 0, cb, g->ctx[k]->stream);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&q.done, hipEventDisableTiming);
+    if (e == hipSuccess) e = gather_create(t->gather, g, [&](int) { return cb; }, [&](int k) { return (size_t)(k - 1) * cb; });
+    if (e == hipSuccess) t->slab_totals.resize(g->ctx.size(), nullptr);
+    for (size_t k = 1; k < t->slab_totals.size() && e == hipSuccess; ++k) {   // zeroed on the slab's stream, ahead of its first count
+      e = hipSetDevice(t->gather.part[k].device);
+      if (e == hipSuccess) e = hipMalloc((void**)&t->slab_totals[k], cb);
+      if (e == hipSuccess) e = hipMemsetAsync(t->slab_totals[k], 0, cb, g->ctx[k]->stream);
     }
   }
-  if (e != hipSuccess) {                                     // the destructor frees the rest; no list was touched
+  if (e != hipSuccess) {                                     // the destructors free what was allocated
     (void)hipGetLastError();
-    hipSetDevice(t->device);
-    if (t->d_rec) hipFree(t->d_rec);
-    if (t->d_stage) hipFree(t->d_stage);
-    return fail("%s: out of device memory (records %zu + totals %zu + fields %zu bytes, slab blocks %zu each, incoming %zu): %s",
-                call, rb, sb, fb, g ? 2 * cb : (size_t)0, ib, hipGetErrorString(e));
+    return fail("%s: out of device memory (fields %zu bytes, slab blocks %zu each, incoming %zu; then records %zu x %lld + totals %zu): %s",
+                call, fb, g ? 2 * cb : (size_t)0, ib, sb, capacity, sb, hipGetErrorString(e));
   }
-  t->capacity = capacity; t->per = per;
-  recorder_list(t.get()).push_back(t.get());
-  *out = t.release();
+  if (store_attach(t.get(), c, b, call, every, capacity, per, per, shape.c_str(), g)) return 1;
+  // The totals are the store's stage buffer, so their zeroing comes after the owner's list took the trace: its failure
+  // detaches again (store_destroy), as the upload of the shape trace's directions does.
+  bflbm_hist* h = t.release();
+  e = hipMemsetAsync(h->d_stage, 0, sb, recorder_stream(h));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    store_destroy(h);
+    return fail("%s: %s", call, hipGetErrorString(e));
+  }
+  *out = h;
   return 0;
 }
 
@@ -375,21 +367,18 @@ int bflbm_hist::record_ring() {
     const double* dense;
     if (fields_observe_slab(c, fs, "histogram trace sample", &dense)) return 1;        // selects the slab's device
     const long long sites = (long long)c->nzl * plane;
-    if (count(dense, 0, sites, sites, 1, k > 0 ? part[k].totals : totals(), c->stream)) return 1;
+    if (count(dense, 0, sites, sites, 1, k > 0 ? slab_totals[k] : totals(), c->stream)) return 1;
     if (k > 0) {
-      HIP_TRY(hipStreamWaitEvent(c->stream, taken, 0));     // slab 0 may still be copying the last sample's block
-      hipLaunchKernelGGL(k_hist_finish, dim3(fin), dim3(256), 0, c->stream, part[k].totals, part[k].block, L.C, (const long long*)nullptr, 0);
+      if (gather_hold(gather, k, c->stream)) return 1;
+      hipLaunchKernelGGL(k_hist_finish, dim3(fin), dim3(256), 0, c->stream, slab_totals[k], static_cast<long long*>(gather.part[k].block), L.C,
+                         (const long long*)nullptr, 0);
       HIP_TRY(hipGetLastError());
-      HIP_TRY(hipEventRecord(part[k].done, c->stream));
+      if (gather_ready(gather, k, c->stream)) return 1;
     }
   }
   HIP_TRY(hipSetDevice(device));
   const hipStream_t s0 = ring->ctx[0]->stream;
-  for (int k = 1; k < n; ++k) {
-    HIP_TRY(hipStreamWaitEvent(s0, part[k].done, 0));
-    HIP_TRY(hipMemcpyPeerAsync(incoming + (size_t)(k - 1) * L.C, device, part[k].block, part[k].device, (size_t)L.C * sizeof(long long), s0));
-  }
-  HIP_TRY(hipEventRecord(taken, s0));
+  if (gather_take(gather, incoming, s0)) return 1;
   hipLaunchKernelGGL(k_hist_finish, dim3(fin), dim3(256), 0, s0, totals(), reinterpret_cast<long long*>(store_slot(this)), L.C,
                      (const long long*)incoming, n - 1);
   HIP_TRY(hipGetLastError());

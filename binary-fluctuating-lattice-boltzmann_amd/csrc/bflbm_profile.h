@@ -13,7 +13,7 @@
 //   k_profile_finish                stage 2: the tiles of a plane in order (axis z) or the planes in sequence (axes x, y),
 //                                   straight into the slot.
 // A ring: stage 1 on every slab's stream over its own planes into [nzl][q][W]; slab 0 takes the other slabs' blocks
-// with one contiguous peer copy each in global plane order (the scheme of bflbm_trace.h), the unchanged stage 2 runs on
+// to their planes' place in its stage buffer (the ring gather of bflbm_recorder.h), the unchanged stage 2 runs on
 // slab 0.  No atomics, no scratch.  Not built on purpose: reading the populations in stage 1 to skip the dense
 // intermediate (hydrovs needs the gradient stencil the observation already has), fusing the sums into the observation
 // kernels (it would give every observer a second form), the kinetic rho u u part of the tensor as a built-in (the
@@ -45,21 +45,10 @@ struct bflbm_profile : bflbm_sample_store {   // d_rec [capacity][nrep][nq][na],
   int W = 0;                        // partials per (q, plane) that stage 1 leaves
   FstatPairs pairs;
   double* fields = nullptr;         // a batch: [nrep][nvars][nsites]
-  // a ring: what slab k > 0 holds on its device (slab 0 writes d_stage itself; part[0] stays empty)
-  struct Part { int device = 0; double* partial = nullptr; hipEvent_t done = nullptr; };   // [nzl][nq][W]; stage 1 is complete
-  std::vector<Part> part;
-  hipEvent_t taken = nullptr;       // slab 0 has copied every slab's block
+  RingGather gather;                // a ring: slab k's block is [nzl][nq][W] (slab 0 writes d_stage itself)
   bflbm_profile() : bflbm_sample_store("profile trace", "bflbm_profile") {}
   ~bflbm_profile() override {
-    for (Part& q : part) {
-      if (!q.partial && !q.done) continue;
-      hipSetDevice(q.device);
-      if (q.partial) hipFree(q.partial);
-      if (q.done) hipEventDestroy(q.done);
-    }
-    if (fields || taken) hipSetDevice(device);
-    if (fields) hipFree(fields);
-    if (taken) hipEventDestroy(taken);
+    if (fields) { hipSetDevice(device); hipFree(fields); }
   }
   int record() override;
   int record_ring();
@@ -315,38 +304,20 @@ int profile_create(bflbm_ctx* c, bflbm_batch* b, bflbm_ring* g, int source, int 
 
   const size_t per = (size_t)t->nrep * t->nq * t->na;
   const size_t plane_doubles = (size_t)t->nq * t->W, stage = (size_t)t->nrep * G.nz * plane_doubles;
-  if ((unsigned long long)capacity > ((1ULL << 40) / sizeof(double)) / per)
-    return fail("%s: capacity %lld x %d replicas x %d sums x %d planes exceeds 1 TB of records", call, capacity, t->nrep, t->nq, t->na);
-  const size_t rb = (size_t)capacity * per * sizeof(double), sb = stage * sizeof(double);
+  const std::string shape = " x " + std::to_string(t->nq) + " sums x " + std::to_string(t->na) + " planes";
+  if (store_refuse_capacity(call, capacity, per, t->nrep, shape.c_str())) return 1;      // before the fields of a batch
   const size_t fb = b ? (size_t)t->nrep * nvars * (size_t)t->nsites * sizeof(double) : 0;
-  size_t pb = 0;                                             // a ring: the largest slab's block
+  const size_t plane_bytes = plane_doubles * sizeof(double);
   hipError_t e = hipSetDevice(t->device);
-  if (e == hipSuccess) e = hipMalloc((void**)&t->d_rec, rb);
-  if (e == hipSuccess) e = hipMalloc((void**)&t->d_stage, sb);
   if (e == hipSuccess && fb) e = hipMalloc((void**)&t->fields, fb);
-  if (e == hipSuccess && g) {
-    e = hipEventCreateWithFlags(&t->taken, hipEventDisableTiming);
-    t->part.resize(g->ctx.size());
-    for (size_t k = 1; k < g->ctx.size() && e == hipSuccess; ++k) {
-      bflbm_profile::Part& q = t->part[k];
-      q.device = g->ctx[k]->dom.device;
-      const size_t nb = (size_t)g->ctx[k]->nzl * plane_doubles * sizeof(double);
-      pb = std::max(pb, nb);
-      e = hipSetDevice(q.device);
-      if (e == hipSuccess) e = hipMalloc((void**)&q.partial, nb);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&q.done, hipEventDisableTiming);
-    }
-  }
-  if (e != hipSuccess) {                                     // the destructor frees the rest; no list was touched
+  if (e == hipSuccess && g) e = gather_create(t->gather, g, [&](int k) { return (size_t)g->ctx[k]->nzl * plane_bytes; },
+                                              [&](int k) { return (size_t)g->ctx[k]->dom.z0 * plane_bytes; });
+  if (e != hipSuccess) {                                     // the destructors free what was allocated
     (void)hipGetLastError();
-    hipSetDevice(t->device);
-    if (t->d_rec) hipFree(t->d_rec);
-    if (t->d_stage) hipFree(t->d_stage);
-    return fail("%s: out of device memory (records %zu + plane partials %zu + fields %zu bytes, slab partials up to %zu): %s",
-                call, rb, sb, fb, pb, hipGetErrorString(e));
+    return fail("%s: out of device memory (fields %zu bytes, slab partials %zu per plane; then records %zu x %lld + plane partials %zu): %s",
+                call, fb, g ? plane_bytes : (size_t)0, per * sizeof(double), capacity, stage * sizeof(double), hipGetErrorString(e));
   }
-  t->capacity = capacity; t->per = per;
-  recorder_list(t.get()).push_back(t.get());
+  if (store_attach(t.get(), c, b, call, every, capacity, per, stage, shape.c_str(), g)) return 1;
   *out = t.release();
   return 0;
 }
@@ -386,25 +357,18 @@ int bflbm_profile::record_ring() {
   if (store_begin(this)) return 1;
   if (fs.source != 1 && ring_prepare_ref(ring)) return 1;  // the global centre of mass: the slabs' own prepare_ref is then a no-op
   const int n = (int)ring->ctx.size();
-  const size_t per_plane = (size_t)nq * W;
   const long long plane = (long long)nx * ny;
   for (int k = 0; k < n; ++k) {
     bflbm_ctx* c = ring->ctx[k];
     const double* dense;
     if (fields_observe_slab(c, fs, "profile trace sample", &dense)) return 1;         // selects the slab's device
-    if (k > 0) HIP_TRY(hipStreamWaitEvent(c->stream, taken, 0));       // slab 0 may still be copying the last sample's block
-    if (stage1(dense, 0, (long long)c->nzl * plane, k > 0 ? part[k].partial : d_stage, c->nzl, 1, c->stream)) return 1;
-    if (k > 0) HIP_TRY(hipEventRecord(part[k].done, c->stream));
+    if (gather_hold(gather, k, c->stream)) return 1;
+    if (stage1(dense, 0, (long long)c->nzl * plane, gather_target(gather, k, d_stage), c->nzl, 1, c->stream)) return 1;
+    if (gather_ready(gather, k, c->stream)) return 1;
   }
   HIP_TRY(hipSetDevice(device));
   const hipStream_t s0 = ring->ctx[0]->stream;
-  for (int k = 1; k < n; ++k) {
-    const bflbm_ctx* c = ring->ctx[k];
-    HIP_TRY(hipStreamWaitEvent(s0, part[k].done, 0));
-    HIP_TRY(hipMemcpyPeerAsync(d_stage + (size_t)c->dom.z0 * per_plane, device, part[k].partial, part[k].device,
-                               (size_t)c->nzl * per_plane * sizeof(double), s0));
-  }
-  HIP_TRY(hipEventRecord(taken, s0));
+  if (gather_take(gather, d_stage, s0)) return 1;
   hipLaunchKernelGGL(k_profile_finish, dim3((unsigned)((nq * na + 255) / 256), 1), dim3(256), 0, s0,
                      d_stage, store_slot(this), axis, nz, nq, W, na);
   HIP_TRY(hipGetLastError());

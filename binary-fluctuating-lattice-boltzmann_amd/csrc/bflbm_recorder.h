@@ -1,11 +1,15 @@
 // bflbm_recorder.h -- the one lifecycle of everything that records from an owner's resident state: ensemble traces
-// (bflbm_trace.h), interface traces (bflbm_iface.h), shape traces (bflbm_shape.h), spectrum traces (bflbm_spectrum.h), mode traces (bflbm_modes.h), ensemble structure factors
-// (bflbm_batch_sf.h) and field statistics (bflbm_fstat.h).  A recorder is
-// attached to a lone context, a batch or a ring of more than one slab, is served after every step on the owner's stream(s)
-// in creation order, survives its owner detached (readable, no longer fed) and is destroyed by its own call (DESIGN.md,
-// "Recorders").  A ring serves its recorders from bflbm_ring_step only, after the bflbm_step_finish of every slab; its
-// samples carry slab 0's step counter and its records live on slab 0's device, written on slab 0's stream (field
-// statistics excepted: a per-site accumulator stays on the slab that owns the site).
+// (bflbm_trace.h), interface traces (bflbm_iface.h), shape traces (bflbm_shape.h), ensemble structure factors
+// (bflbm_batch_sf.h), spectrum traces (bflbm_spectrum.h, bflbm_spectrum_ring.h), mode traces (bflbm_modes.h), field
+// statistics (bflbm_fstat.h), profile traces (bflbm_profile.h), histogram traces (bflbm_hist.h) and radial traces
+// (bflbm_radial.h).  A recorder is attached to a lone context, a batch or a ring of more than one slab, is served after
+// every step on the owner's stream(s) in creation order, survives its owner detached (readable, no longer fed) and is
+// destroyed by its own call ("Recorders").  A ring serves its recorders from bflbm_ring_step only, after the
+// bflbm_step_finish of every slab; its samples carry slab 0's step counter and its records live on slab 0's device,
+// written on slab 0's stream (field statistics excepted: a per-site accumulator stays on the slab that owns the site).
+// Below the lifecycle, two things the kinds share: the sample store of every kind but the two accumulators (structure
+// factors, field statistics), which owns its records and its stage buffer, and the ring gather, by which the kinds that
+// reduce on every slab of a ring (moments, profile, histogram and spectrum traces) bring one block per slab to slab 0.
 // The layer above it, what the kinds that read observed fields share, is bflbm_fieldsel.h.
 // Host code only.  Included by bflbm.hip once bflbm_ctx, bflbm_batch and bflbm_ring are complete (needs fail, HIP_TRY).
 #ifndef BFLBM_RECORDER_H_
@@ -29,12 +33,42 @@ struct bflbm_recorder {
   virtual int record() = 0;        // enqueue one sample (frame) of the resident state now; no host synchronisation
 };
 
-// what the trace kinds add: `capacity` samples of `per` doubles on the device, and a stage buffer of the kind's own
+// what the trace kinds add: `capacity` samples of `per` doubles on the device, and a stage buffer of the kind's own.
+// The store owns both: store_attach allocates them, the destructor frees them.
 struct bflbm_sample_store : bflbm_recorder {
   using bflbm_recorder::bflbm_recorder;
   size_t per = 0;
   double* d_rec = nullptr;         // [capacity][per]
   double* d_stage = nullptr;       // stage 1 -> stage 2
+  ~bflbm_sample_store() override {
+    if (!d_rec && !d_stage) return;
+    hipSetDevice(device);
+    if (d_rec) hipFree(d_rec);
+    if (d_stage) hipFree(d_stage);
+  }
+};
+
+// The ring gather: how a kind that reduces on every slab of a ring brings one block per slab to slab 0 (DESIGN.md,
+// "Recorders").  Slab k > 0 writes its block on its own device and stream and records `done`; slab 0's stream waits for
+// every `done`, copies each block to its place in a buffer of slab 0 and records `taken`; before slab k overwrites its
+// block for the next sample its stream waits for `taken`.  Empty unless the owner is a ring of more than one slab.
+struct RingGather {
+  struct Part { int device = 0; void* block = nullptr; size_t bytes = 0, at = 0; hipEvent_t done = nullptr; };   // slab k > 0; part[0] stays empty
+  std::vector<Part> part;
+  int device = 0;                  // slab 0's
+  hipEvent_t taken = nullptr;      // slab 0 has copied every slab's block of the last sample
+  RingGather() = default;
+  RingGather(const RingGather&) = delete;
+  RingGather& operator=(const RingGather&) = delete;
+  ~RingGather() {
+    for (Part& q : part) {
+      if (!q.block && !q.done) continue;
+      hipSetDevice(q.device);
+      if (q.block) hipFree(q.block);
+      if (q.done) hipEventDestroy(q.done);
+    }
+    if (taken) { hipSetDevice(device); hipEventDestroy(taken); }
+  }
 };
 
 namespace {
@@ -93,7 +127,48 @@ template <class Owner> int recorders_after_step(Owner* o) {
   return 0;
 }
 
-// ---- the sample store of the two trace kinds ---------------------------------------------------------------------------
+// ---- the ring gather -----------------------------------------------------------------------------------------------------
+// The events of every slab k > 0 and its block of bytes_of(k) bytes, which lands at byte at_of(k) of the destination.
+// On failure the gather holds only what its destructor frees.  Leaves the last slab's device selected.
+template <class BytesOf, class AtOf>
+hipError_t gather_create(RingGather& G, const bflbm_ring* g, BytesOf bytes_of, AtOf at_of) {
+  G.device = g->ctx[0]->dom.device;
+  G.part.resize(g->ctx.size());
+  hipError_t e = hipSetDevice(G.device);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&G.taken, hipEventDisableTiming);
+  for (int k = 1; k < (int)G.part.size() && e == hipSuccess; ++k) {
+    RingGather::Part& q = G.part[k];
+    q.device = g->ctx[k]->dom.device; q.bytes = bytes_of(k); q.at = at_of(k);
+    e = hipSetDevice(q.device);
+    if (e == hipSuccess) e = hipMalloc(&q.block, q.bytes);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&q.done, hipEventDisableTiming);
+  }
+  return e;
+}
+// where slab k's launch writes: its block, or slab 0's own place in the destination
+template <class T> inline T* gather_target(const RingGather& G, int k, T* own) { return k > 0 ? static_cast<T*>(G.part[k].block) : own; }
+// Around the launch on slab k's stream that overwrites its block (slab 0 has none: both do nothing).  hold: slab 0 may
+// still be copying the last sample's block; a `taken` never recorded (the first sample) is complete, the wait a no-op.
+int gather_hold(const RingGather& G, int k, hipStream_t stream) {
+  if (k > 0) HIP_TRY(hipStreamWaitEvent(stream, G.taken, 0));
+  return 0;
+}
+int gather_ready(const RingGather& G, int k, hipStream_t stream) {
+  if (k > 0) HIP_TRY(hipEventRecord(G.part[k].done, stream));
+  return 0;
+}
+// on slab 0's stream, its device selected: every block to its place in dst, in slab order
+int gather_take(const RingGather& G, void* dst, hipStream_t s0) {
+  for (size_t k = 1; k < G.part.size(); ++k) {
+    const RingGather::Part& q = G.part[k];
+    HIP_TRY(hipStreamWaitEvent(s0, q.done, 0));
+    HIP_TRY(hipMemcpyPeerAsync(static_cast<char*>(dst) + q.at, G.device, q.block, q.device, q.bytes, s0));
+  }
+  HIP_TRY(hipEventRecord(G.taken, s0));
+  return 0;
+}
+
+// ---- the sample store ------------------------------------------------------------------------------------------------------
 int store_refuse_cadence(const char* call, int every, long long capacity) {
   if (every < 1) return fail("%s: every must be >= 1 (got %d)", call, every);
   if (capacity < 1) return fail("%s: capacity must be >= 1 (got %lld)", call, capacity);
@@ -106,21 +181,27 @@ int store_refuse_owner(const bflbm_ctx* c, const char* call, const char* batch_c
   return 0;
 }
 
-// allocate [capacity][per] and the stage buffer and attach the store to its owner; `shape`: what besides the replicas
-// multiplies the capacity, for the message.  On failure the store owns nothing.
+// `capacity` samples of `per` 8-byte words for `nrep` replicas; `shape`: what besides the replicas multiplies the
+// capacity, for the message.  store_attach asks; a kind that allocates much of its own before it asks first.
+int store_refuse_capacity(const char* call, long long capacity, size_t per, int nrep, const char* shape) {
+  if ((unsigned long long)capacity > ((1ULL << 40) / sizeof(double)) / per)
+    return fail("%s: capacity %lld x %d replicas%s exceeds 1 TB of records", call, capacity, nrep, shape);
+  return 0;
+}
+
+// allocate [capacity][per] and the stage buffer and attach the store to its owner.  The last step of a creation call:
+// the owner's list has the store afterwards, so what can fail comes before it (or detaches again).  On failure the
+// store's destructor frees what was allocated.
 int store_attach(bflbm_sample_store* s, bflbm_ctx* c, bflbm_batch* b, const char* call, int every, long long capacity,
                  size_t per, size_t stage_doubles, const char* shape, bflbm_ring* g = nullptr) {
   if ((c && c->step_open()) || (g && ring_step_open(g))) return fail("%s inside an open step", call);
   recorder_bind(s, c, b, every, g);
-  if ((unsigned long long)capacity > ((1ULL << 40) / sizeof(double)) / per)
-    return fail("%s: capacity %lld x %d replicas%s exceeds 1 TB of records", call, capacity, s->nrep, shape);
+  if (store_refuse_capacity(call, capacity, per, s->nrep, shape)) return 1;
   HIP_TRY(hipSetDevice(s->device));
   hipError_t e = hipMalloc((void**)&s->d_rec, (size_t)capacity * per * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void**)&s->d_stage, stage_doubles * sizeof(double));
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    if (s->d_rec) hipFree(s->d_rec);
-    s->d_rec = nullptr;
     return fail("%s: %s", call, hipGetErrorString(e));
   }
   s->capacity = capacity; s->per = per;
@@ -144,10 +225,8 @@ void store_recorded(bflbm_sample_store* s) {
 
 int store_destroy(bflbm_sample_store* s) {
   if (!s) return 0;
-  recorder_detach(s);                                  // waits for the work in flight: it writes the buffers freed below
-  hipSetDevice(s->device);
-  if (s->d_rec) hipFree(s->d_rec);
-  if (s->d_stage) hipFree(s->d_stage);
+  recorder_detach(s);                                  // waits for the work in flight: it writes the buffers the destructors free
+  hipSetDevice(s->device);                             // a kind's destructor frees its lone and batch buffers on the selected device
   delete s;
   return 0;
 }

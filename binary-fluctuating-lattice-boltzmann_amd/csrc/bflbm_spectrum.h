@@ -156,13 +156,11 @@ struct SpectrumSlab {
   uint32_t* d_list = nullptr;       // the slab's tables (spectrum_tables::build_slab)
   spectrum_tables::Chunk* d_chunks = nullptr;
   int* d_bin_first = nullptr;
-  double* partial = nullptr;        // [pair][chunk]
-  double* sum = nullptr;            // [pair][bin]; slab 0 has none: it writes block 0 of the handle's d_stage
+  double* partial = nullptr;        // [pair][chunk]; the bin sums [pair][bin] are the slab's block of the handle's gather
   SpectrumSrc* d_src = nullptr;     // [nslabs], in slab order
   bool reachable = false;           // every source is on this device or peer-mapped: k_spectrum_collect may read it in place
   hipEvent_t planes = nullptr;      // h2 is complete (recorded on the slab's stream) ...
   hipEvent_t collected = nullptr;   // ... and this slab has taken its rows of every other slab's h2
-  hipEvent_t summed = nullptr;      // sum is complete
 };
 
 struct bflbm_spectrum : bflbm_sample_store {  // d_rec [capacity][nrep][npairs][nbins], d_stage [nrep][npairs][nchunks]
@@ -186,7 +184,7 @@ struct bflbm_spectrum : bflbm_sample_store {  // d_rec [capacity][nrep][npairs][
   // a ring: d_stage is [nslabs][npairs][nbins] on slab 0's device, nchunks the slabs' total, max_chunks_per_bin the most
   // of any (slab, bin); the members from `fields` to `plan` stay empty
   std::vector<SpectrumSlab> slab;
-  hipEvent_t combined = nullptr;    // slab 0 has taken every slab's sums
+  RingGather gather;                // slab d's bin sums [npairs][nbins] into block d of d_stage (slab 0 writes block 0 itself)
   bflbm_spectrum() : bflbm_sample_store("spectrum trace", "bflbm_spectrum") {}
   ~bflbm_spectrum() override {
     if (plan) g_fft.destroy(plan);
@@ -195,11 +193,10 @@ struct bflbm_spectrum : bflbm_sample_store {  // d_rec [capacity][nrep][npairs][
       hipSetDevice(q.device);
       if (q.plan2d) g_fft.destroy(q.plan2d);
       if (q.plan1d) g_fft.destroy(q.plan1d);
-      for (void* p : {(void*)q.h2, (void*)q.zb, (void*)q.d_list, (void*)q.d_chunks, (void*)q.d_bin_first, (void*)q.partial, (void*)q.sum, (void*)q.d_src})
+      for (void* p : {(void*)q.h2, (void*)q.zb, (void*)q.d_list, (void*)q.d_chunks, (void*)q.d_bin_first, (void*)q.partial, (void*)q.d_src})
         if (p) hipFree(p);
-      for (hipEvent_t e : {q.planes, q.collected, q.summed}) if (e) hipEventDestroy(e);
+      for (hipEvent_t e : {q.planes, q.collected}) if (e) hipEventDestroy(e);
     }
-    if (combined) { hipSetDevice(device); hipEventDestroy(combined); }
   }
   int record() override;
   int record_ring();                // bflbm_spectrum_ring.h

@@ -9,11 +9,11 @@
 //                                  BFLBM_RING_COPY_FALLBACK=1 asks for copies; the strided copies of
 //                                  bflbm_ring_sf_accumulate otherwise (the same doubles); the event `collected`;
 //   3. on every slab's stream      batched Z2Z along z in place, k_spectrum_bin and k_spectrum_finish as they are with
-//                                  the slab's own tables (spectrum_tables::build_slab) into sum[pair][bin], the event `summed`;
-//   4. on slab 0's stream          after every `summed`: one small copy per slab into d_stage[slab][pair][bin], then
+//                                  the slab's own tables (spectrum_tables::build_slab) into the slab's sums [pair][bin];
+//   4. on slab 0's stream          the ring gather of bflbm_recorder.h: the slabs' sums into d_stage[slab][pair][bin], then
 //                                  k_spectrum_combine adds the slabs in the order 0 ... n-1 into the slot.
 // What the next sample overwrites while another stream may still read it waits the other way round: a slab's 2-D
-// transforms for every other slab's `collected`, a slab's sums for slab 0's `combined`.  A record depends on the spectra,
+// transforms for every other slab's `collected`, a slab's sums for the gather's `taken`.  A record depends on the spectra,
 // the slabs' tables and the slab count alone.  No atomics, no LDS beyond the tree of k_spectrum_bin, no scratch.
 // Included by bflbm.hip after bflbm_spectrum.h (needs bflbm_ring, ring_prepare_ref, ring_force_copies, load_fft_many,
 // fields_observe_slab).
@@ -72,7 +72,7 @@ int spectrum_ring_create(bflbm_ring* g, int npairs, const int* var_a, const int*
     t->nbins = T.nbins; t->count = T.count; t->q = T.q;
   }
   const size_t nv = t->vars.size();
-  t->device = g->ctx[0]->dom.device;                       // the destructor's, should a step below fail
+  const size_t per = (size_t)npairs * (size_t)t->nbins, sb = per * sizeof(double);   // a slab's bin sums: its block of the gather
   t->slab.resize((size_t)n);
   t->nchunks = 0; t->max_chunks_per_bin = 0;
   std::vector<SpectrumSrc> src((size_t)n);
@@ -91,14 +91,13 @@ int spectrum_ring_create(bflbm_ring* g, int npairs, const int* var_a, const int*
     const size_t hb = nv * (size_t)c->nzl * ny * nxc * sizeof(double2), zb = nv * (size_t)q.nk * sizeof(double2);
     const size_t lb_ = std::max<size_t>(T.list.size(), 1) * sizeof(uint32_t);
     const size_t cb = std::max<size_t>(T.chunks.size(), 1) * sizeof(spectrum_tables::Chunk), bb = T.bin_first.size() * sizeof(int);
-    const size_t pb = (size_t)npairs * std::max<size_t>(T.chunks.size(), 1) * sizeof(double), sb = (size_t)npairs * (size_t)t->nbins * sizeof(double);
+    const size_t pb = (size_t)npairs * std::max<size_t>(T.chunks.size(), 1) * sizeof(double);
     hipError_t e = hipMalloc((void**)&q.h2, hb);
     if (e == hipSuccess) e = hipMalloc((void**)&q.zb, zb);
     if (e == hipSuccess) e = hipMalloc((void**)&q.d_list, lb_);
     if (e == hipSuccess) e = hipMalloc((void**)&q.d_chunks, cb);
     if (e == hipSuccess) e = hipMalloc((void**)&q.d_bin_first, bb);
     if (e == hipSuccess) e = hipMalloc((void**)&q.partial, pb);
-    if (e == hipSuccess && d > 0) e = hipMalloc((void**)&q.sum, sb);
     if (e == hipSuccess) e = hipMalloc((void**)&q.d_src, (size_t)n * sizeof(SpectrumSrc));
     if (e != hipSuccess) {
       (void)hipGetLastError();
@@ -108,7 +107,7 @@ int spectrum_ring_create(bflbm_ring* g, int npairs, const int* var_a, const int*
     if (!T.list.empty()) HIP_TRY(hipMemcpy(q.d_list, T.list.data(), T.list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (!T.chunks.empty()) HIP_TRY(hipMemcpy(q.d_chunks, T.chunks.data(), T.chunks.size() * sizeof(spectrum_tables::Chunk), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(q.d_bin_first, T.bin_first.data(), bb, hipMemcpyHostToDevice));
-    for (hipEvent_t* ev : {&q.planes, &q.collected, &q.summed}) HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    for (hipEvent_t* ev : {&q.planes, &q.collected}) HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
     int n2[2] = { ny, nx };
     if (g_fftm.plan_many(&q.plan2d, 2, n2, nullptr, 1, ny * nx, nullptr, 1, ny * nxc, HIPFFT_D2Z, c->nzl) != HIPFFT_SUCCESS) {
       q.plan2d = nullptr;
@@ -138,9 +137,7 @@ int spectrum_ring_create(bflbm_ring* g, int npairs, const int* var_a, const int*
       q.reachable = q.reachable && ok;
     }
   }
-  HIP_TRY(hipSetDevice(t->device));
-  HIP_TRY(hipEventCreateWithFlags(&t->combined, hipEventDisableTiming));
-  const size_t per = (size_t)npairs * (size_t)t->nbins;
+  HIP_TRY(gather_create(t->gather, g, [&](int) { return sb; }, [&](int d) { return (size_t)d * sb; }));
   const std::string shape = " x " + std::to_string(npairs) + " pairs x " + std::to_string(t->nbins) + " bins";
   if (store_attach(t.get(), nullptr, nullptr, call, every, capacity, per, (size_t)n * per, shape.c_str(), g)) return 1;
   *out = t.release();
@@ -207,21 +204,16 @@ int bflbm_spectrum::record_ring() {
                          q.zb, q.d_list, q.d_chunks, q.partial, q.nk, nspec, nx, pairs, inv_n);
       HIP_TRY(hipGetLastError());
     }
-    if (d > 0) HIP_TRY(hipStreamWaitEvent(c->stream, combined, 0));                                     // the last sample's sums were taken
+    if (gather_hold(gather, d, c->stream)) return 1;
     hipLaunchKernelGGL(k_spectrum_finish, dim3((unsigned)((nbins + 255) / 256), (unsigned)pairs.n, 1), dim3(256), 0, c->stream,
-                       q.partial, q.d_bin_first, d > 0 ? q.sum : d_stage, nbins, std::max(q.nchunks, 1LL));
+                       q.partial, q.d_bin_first, gather_target(gather, d, d_stage), nbins, std::max(q.nchunks, 1LL));
     HIP_TRY(hipGetLastError());
-    if (d > 0) HIP_TRY(hipEventRecord(q.summed, c->stream));
+    if (gather_ready(gather, d, c->stream)) return 1;
   }
   // 4. slab 0 takes the sums and adds them in slab order
   HIP_TRY(hipSetDevice(device));
   const hipStream_t s0 = g->ctx[0]->stream;
-  const size_t per_slab = (size_t)pairs.n * (size_t)nbins;
-  for (int d = 1; d < n; ++d) {
-    HIP_TRY(hipStreamWaitEvent(s0, slab[d].summed, 0));
-    HIP_TRY(hipMemcpyPeerAsync(d_stage + (size_t)d * per_slab, device, slab[d].sum, slab[d].device, per_slab * sizeof(double), s0));
-  }
-  HIP_TRY(hipEventRecord(combined, s0));
+  if (gather_take(gather, d_stage, s0)) return 1;
   hipLaunchKernelGGL(k_spectrum_combine, dim3((unsigned)((nbins + 255) / 256), (unsigned)pairs.n), dim3(256), 0, s0,
                      d_stage, store_slot(this), nbins, n);
   HIP_TRY(hipGetLastError());

@@ -10,9 +10,8 @@
 // A ring of z-slabs: stage 1 runs on every slab's own stream over the slab's own planes (z the global plane index, the
 // halo planes pulled through as the slab's density pass does) into [nzl][plane blocks][kNTrace] on the slab's device;
 // slab 0 writes its planes straight into the stage buffer [nz][plane blocks][kNTrace] and takes every other slab's block
-// with one contiguous (peer) copy after that slab's event, in global plane order; the same k_trace_finish then runs on
-// slab 0.  The summation order is a lone context's, so with the bit-exact schedules the record equals the lone trace's
-// bit for bit.  The next sample's stage 1 of a slab waits for the event that slab 0 has taken the last one's block.
+// to its planes' place there by the ring gather of bflbm_recorder.h; the same k_trace_finish then runs on slab 0.  The
+// summation order is a lone context's, so with the bit-exact schedules the record equals the lone trace's bit for bit.
 // Included by bflbm.hip after bflbm_droplet.h (needs bflbm_ctx, bflbm_batch, bflbm_ring, block_sum,
 // batch_sync_table).  trace_moments_launch also serves the centre of mass of bflbm_shape.h and bflbm_radial.h.
 #ifndef BFLBM_TRACE_H_
@@ -21,19 +20,8 @@
 struct bflbm_trace : bflbm_sample_store {  // d_rec [capacity][nrep][kNTrace], d_stage [nrep][nz][plane blocks][kNTrace]
   Geo G;
   double threshold = 0.;
-  // a ring: what slab k > 0 holds on its device (slab 0 writes d_stage itself; part[0] stays empty)
-  struct Part { int device = 0; double* partial = nullptr; hipEvent_t done = nullptr; };   // [nzl][plane blocks][kNTrace]; stage 1 is complete
-  std::vector<Part> part;
-  hipEvent_t taken = nullptr;      // slab 0 has copied every slab's block
+  RingGather gather;               // a ring: slab k's block is [nzl][plane blocks][kNTrace] (slab 0 writes d_stage itself)
   bflbm_trace() : bflbm_sample_store("trace", "bflbm_trace") {}
-  ~bflbm_trace() override {
-    for (Part& q : part) {
-      hipSetDevice(q.device);
-      if (q.partial) hipFree(q.partial);
-      if (q.done) hipEventDestroy(q.done);
-    }
-    if (taken) { hipSetDevice(device); hipEventDestroy(taken); }
-  }
   int record() override;
   int record_ring();
 };
@@ -117,17 +105,9 @@ int trace_create(bflbm_ctx* c, bflbm_batch* b, bflbm_ring* g, int every, long lo
   const size_t nbx = (size_t)((t->G.plane + 255) / 256), nblocks = nbx * (size_t)t->G.nz;
   if (g) {
     if (ring_step_open(g)) return fail("%s inside an open step", call);
-    t->device = g->ctx[0]->dom.device;                   // the destructor's, should a step below fail
-    t->part.resize(g->ctx.size());
-    for (size_t k = 1; k < g->ctx.size(); ++k) {
-      bflbm_trace::Part& q = t->part[k];
-      q.device = g->ctx[k]->dom.device;
-      HIP_TRY(hipSetDevice(q.device));
-      HIP_TRY(hipMalloc((void**)&q.partial, (size_t)g->ctx[k]->nzl * nbx * kNTrace * sizeof(double)));
-      HIP_TRY(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
-    }
-    HIP_TRY(hipSetDevice(t->device));
-    HIP_TRY(hipEventCreateWithFlags(&t->taken, hipEventDisableTiming));
+    const size_t plane_bytes = nbx * kNTrace * sizeof(double);
+    HIP_TRY(gather_create(t->gather, g, [&](int k) { return (size_t)g->ctx[k]->nzl * plane_bytes; },
+                          [&](int k) { return (size_t)g->ctx[k]->dom.z0 * plane_bytes; }));
   }
   if (store_attach(t.get(), c, b, call, every, capacity, per, nblocks * per, "", g)) return 1;
   *out = t.release();
@@ -167,25 +147,18 @@ int bflbm_trace::record_ring() {
   if (store_begin(this)) return 1;
   const int n = (int)ring->ctx.size();
   const unsigned nbx = (unsigned)((G.plane + 255) / 256);
-  const size_t per_plane = (size_t)nbx * kNTrace;
   for (int k = 0; k < n; ++k) {
     bflbm_ctx* c = ring->ctx[k];
     HIP_TRY(hipSetDevice(c->dom.device));
-    if (k > 0) HIP_TRY(hipStreamWaitEvent(c->stream, taken, 0));       // slab 0 may still be copying the last sample's block
+    if (gather_hold(gather, k, c->stream)) return 1;
     hipLaunchKernelGGL(k_trace_moments, dim3(nbx, (unsigned)c->nzl, 1), dim3(256), 0, c->stream,
-                       c->S[c->cur], k > 0 ? part[k].partial : d_stage, c->G, threshold);
+                       c->S[c->cur], gather_target(gather, k, d_stage), c->G, threshold);
     HIP_TRY(hipGetLastError());
-    if (k > 0) HIP_TRY(hipEventRecord(part[k].done, c->stream));
+    if (gather_ready(gather, k, c->stream)) return 1;
   }
   HIP_TRY(hipSetDevice(device));
   const hipStream_t s0 = ring->ctx[0]->stream;
-  for (int k = 1; k < n; ++k) {
-    const bflbm_ctx* c = ring->ctx[k];
-    HIP_TRY(hipStreamWaitEvent(s0, part[k].done, 0));
-    HIP_TRY(hipMemcpyPeerAsync(d_stage + (size_t)c->dom.z0 * per_plane, device, part[k].partial, part[k].device,
-                               (size_t)c->nzl * per_plane * sizeof(double), s0));
-  }
-  HIP_TRY(hipEventRecord(taken, s0));
+  if (gather_take(gather, d_stage, s0)) return 1;
   hipLaunchKernelGGL(k_trace_finish, dim3(1), dim3(256), 0, s0, d_stage, store_slot(this), (int)nbx, G.nz);
   HIP_TRY(hipGetLastError());
   store_recorded(this);

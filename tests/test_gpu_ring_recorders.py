@@ -6,8 +6,11 @@ ring's noise does not depend on the decomposition, tests/test_gpu_slabs.py) its 
 bit.  The spectrum trace of a ring is a slab FFT with per-slab binning: it is compared with the numpy restatement
 (analysis.binned_spectrum) under the tolerance of tests/test_gpu_spectrum.py, taken over from there with its helpers:
     |device - numpy| <= 1e-11 count[bin] max_k |S_ab(k)|        per bin and pair.
+The profile and histogram traces of a ring have their definition tests in test_gpu_profile.py and test_gpu_hist.py; here
+they meet what all four kinds that gather a block per slab onto slab 0 share, the reuse of those blocks at every = 1.
 The shapes: the smallest ring (2 slabs of 4 planes), ragged slabs of 4 / 4 / 5 planes with ky rows split 2 / 2 / 2, a
 padded pitch on 4 slabs, odd nx with ky rows split 2 / 2 / 3, and a box whose axis bins take 3 chunks on every slab."""
+import functools
 import os
 import subprocess
 import sys
@@ -15,6 +18,7 @@ import sys
 import numpy as np
 import pytest
 
+from test_gpu_hist import CASES, _fields, _ranges
 from test_gpu_spectrum import KINDS, TRIO, _close, _host, _lone
 
 pytestmark = pytest.mark.gpu
@@ -164,33 +168,74 @@ def test_collect_kernel_and_copies_move_the_same_doubles(tmp_path):
 
 
 # ---- 5. determinism and reuse hazards ----------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _hist_ranges(pkg, n):
+    """{source: {variable: (lo, hi, bins)}} of test_gpu_hist.CASES, the ranges taken from a lone lattice of the rings'
+    mixture after 5 steps (the probe run of test_gpu_hist.test_ring_record_equals_the_lone_record); once per shape."""
+    probe = _lone(pkg, n, schedule="fused")
+    probe.LBM_timestep(5)
+    ranges = {s: _ranges(_fields(pkg, probe, s, list(CASES[s][0])), CASES[s][0]) for s in ("hydrovs", "noise")}
+    probe.close()
+    return ranges
+
+
+def _plane_and_bin_traces(pkg, o, capacity=16):
+    """The profile and histogram traces of _watched: a z profile (its finish reads every slab's planes) and an x profile
+    with a pair each, the histograms of hydrovs (two pair blocks) and of the noise (one pair block)."""
+    ranges = _hist_ranges(pkg, tuple(o.n))
+    return [o.profile_trace(["rho", "phi", "afz"], [("rho", "phi")], axis="z", every=1, capacity=capacity),
+            o.profile_trace(["rho", "ubx"], [("rho", "ubx")], axis="x", every=1, capacity=capacity),
+            o.histogram_trace(ranges["hydrovs"], CASES["hydrovs"][1], every=1, capacity=capacity),
+            o.histogram_trace(ranges["noise"], CASES["noise"][1], source="noise", every=1, capacity=capacity)]
+
+
 def _watched(pkg, ring, capacity=16):
+    """One recorder or more of every kind that gathers a block per slab onto slab 0, all at every = 1."""
     names = pkg.plotfile.variable_names(22)
     return [ring.trace(every=1, capacity=capacity),
             ring.spectrum_trace(names, kind="shell", every=1, capacity=capacity),
-            ring.spectrum_trace(pkg.plotfile.variable_names(9), kind="z", lb_hydrovars=True, every=1, capacity=capacity)]
+            ring.spectrum_trace(pkg.plotfile.variable_names(9), kind="z", lb_hydrovars=True, every=1, capacity=capacity)
+            ] + _plane_and_bin_traces(pkg, ring, capacity)
+
+
+def _read(tr):
+    """(steps, records) of any kind: ProfileTrace.read() hands them out the other way round."""
+    out = tr.read()
+    return out[::-1] if type(tr).__name__ == "ProfileTrace" else out
 
 
 def test_ring_records_are_deterministic(pkg):
     """every = 1: a slab's buffers of one sample are still being read by another slab's stream when the next sample is
-    due.  One call of 12 steps against a second ring stepped one call per step; the same state sampled twice by hand."""
+    due.  One call of 12 steps against a second ring stepped one call per step; the same state sampled twice by hand.
+    The profile and histogram records, the doubled hand samples first, are also a lone lattice's bit for bit (kBT = 1e-5
+    and a bit-exact schedule, as in test_gpu_profile and test_gpu_hist), so a block copied to the wrong place shows even
+    if every run copies it there."""
     nslabs, n = 3, (10, 6, 13)
     a, b = _ring(pkg, nslabs, n), _ring(pkg, nslabs, n)
     ra, rb = _watched(pkg, a), _watched(pkg, b)
-    for tr in ra + rb:
+    lone = _lone(pkg, n, schedule="fused")
+    rl = _plane_and_bin_traces(pkg, lone)
+    for tr in ra + rb + rl:
         tr.sample(); tr.sample()
     a.LBM_timestep(12)
     for _ in range(12):
         b.LBM_timestep(1)
+    lone.LBM_timestep(12)
+    for ta, tl in zip(ra[-len(rl):], rl):
+        (sa, va), (sl, vl) = _read(ta), _read(tl)
+        assert type(ta) is type(tl) and np.array_equal(sa, sl)
+        assert np.array_equal(va[:2], vl[:2]), type(ta).__name__             # the doubled hand samples of the initial state
+        assert np.array_equal(va, vl), type(ta).__name__                     # ... and every sample of the run
+    lone.close()
     for ta, tb in zip(ra, rb):
-        (sa, va), (sb, vb) = ta.read(), tb.read()
+        (sa, va), (sb, vb) = _read(ta), _read(tb)
         assert sa[:, 0].tolist() == [0, 0] + list(range(1, 13)) and np.array_equal(sa, sb)
         assert np.isfinite(va).all() and np.array_equal(va, vb)
         assert np.array_equal(va[0], va[1]) and np.abs(va[0]).max() > 0      # the same state sampled twice
         assert not np.array_equal(va[5], va[9])
     for tr in ra:
         tr.sample(); tr.sample()
-        rec = tr.read()[1]
+        rec = _read(tr)[1]
         assert np.array_equal(rec[-1], rec[-2]) and np.array_equal(rec[-1], rec[-3])   # ... and again after the run
     a.close(); b.close()
 
@@ -207,7 +252,7 @@ def test_ring_recorders_change_nothing(pkg, n, schedule):
     for u, v in zip(a.populations(), b.populations()):
         assert np.array_equal(u, v)
     for tr in recs:
-        steps, rec = tr.read()
+        steps, rec = _read(tr)
         assert steps[:, 0].tolist() == list(range(1, 13)) and np.isfinite(rec).all() and np.abs(rec).max() > 0
     a.LBM_timestep(1); b.LBM_timestep(1)                     # the step after the last sample
     assert a.steps_done == b.steps_done == 13
