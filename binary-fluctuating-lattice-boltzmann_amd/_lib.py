@@ -113,6 +113,7 @@ SIGNATURES = {
     "bflbm_batch_step": (ctypes.c_int, [_vp, ctypes.c_int]),
     "bflbm_batch_sync": (ctypes.c_int, [_vp]),
     "bflbm_fused_plan_query": (ctypes.c_int, [_P(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int)]),
+    "bflbm_sweep_plan_query": (ctypes.c_int, [_P(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int)]),
     "bflbm_trace_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, _P(_vp)]),
     "bflbm_batch_trace_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, _P(_vp)]),
     "bflbm_ring_trace_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, _P(_vp)]),

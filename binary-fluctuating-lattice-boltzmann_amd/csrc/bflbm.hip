@@ -1727,6 +1727,57 @@ int bflbm_fused_plan_query(const int n[3], int nreplicas, int noise, int compute
   return 0;
 }
 
+// The plans of the plane-marching sweeps of one step (see include/bflbm.h): the interior sweep of bflbm_step_interior and,
+// for a slab, the boundary-pair launch of bflbm_step_boundary, from handover_plan / fused_plan as launch_sweep reaches
+// them, with compute_units > 0 in place of device_cus() for this call.
+int bflbm_sweep_plan_query(const int n[3], int schedule, int noise, int slab_planes, int compute_units, int out[16]) {
+  if (!n || !out) return fail("bflbm_sweep_plan_query: null argument");
+  if (schedule != 1 && schedule != 3) return fail("bflbm_sweep_plan_query: schedule must be 1 (fused) or 3 (hand-over) (got %d)", schedule);
+  if (n[0] < 1 || n[1] < 1 || n[2] < 1) return fail("bflbm_sweep_plan_query: lattice size must be >= 1 (got %d x %d x %d)", n[0], n[1], n[2]);
+  if (slab_planes != 0 && (slab_planes < 4 || slab_planes > n[2] - 4))
+    return fail("bflbm_sweep_plan_query: slab_planes must be 0 or in 4..nz-4 (got %d of nz = %d)", slab_planes, n[2]);
+  const int nzl = slab_planes ? slab_planes : n[2];
+  if ((long long)(n[0] + 15) * n[1] * (long long)(nzl + 4) >= (1LL << 31) || (long long)(n[0] + 15) * n[1] >= (1LL << 28))
+    return fail("bflbm_sweep_plan_query: %d x %d x %d is too large for 32-bit site offsets", n[0], n[1], nzl);
+  if (compute_units < 0) return fail("bflbm_sweep_plan_query: compute_units < 0");
+  bflbm_domain d;
+  for (int a = 0; a < 3; ++a) d.n[a] = n[a];
+  d.z0 = 0; d.z1 = nzl; d.rank = 0; d.nranks = slab_planes ? 2 : 1; d.device = 0;
+  Geo G;
+  domain_geo(&d, G);
+  if (schedule == 3 && !handover_ok(G))
+    return fail("bflbm_sweep_plan_query: the hand-over kernel does not take a %d x %d lattice (a last tile column or row of one site, or less than one tile)", n[0], n[1]);
+  const int mode = noise ? 1 : 0;
+  const int lo = G.H, hi = G.H + nzl;
+  const int a = G.zwrap ? lo : lo + 2, b = G.zwrap ? hi : hi - 2;        // the interior sweep (bflbm_step_interior)
+  const int held = g_fused_ncu;
+  if (compute_units > 0) g_fused_ncu = compute_units;
+  auto plan = [&](int pa, int pb, int pair_len, FusedGrid& F) {
+    if (schedule == 3) { handover_plan(G, pa, pb, pair_len, F); return 64; }
+    return fused_plan(G, pa, pb, mode, pair_len, F);
+  };
+  FusedGrid F, Fp;
+  int TX = 0;
+  const bool interior = b > a;                                           // a slab of 4 planes is all boundary pairs
+  if (interior) TX = plan(a, b, 0, F);
+  const bool one_pair_launch = hi - lo > 4;                              // launch_sweep: one launch where the pairs are disjoint
+  if (!G.zwrap) { const int t = one_pair_launch ? plan(lo, hi, 2, Fp) : plan(lo, lo + 2, 2, Fp); if (!interior) TX = t; }
+  const int ncu = device_cus();
+  g_fused_ncu = held;
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  out[0] = TX; out[1] = schedule == 3 ? HO_TY : (FUSED_TX * FUSED_TY) / TX;
+  out[13] = ncu;
+  if (interior) {
+    out[2] = F.ntx; out[3] = F.nty; out[4] = F.sx;
+    out[5] = F.lz; out[6] = F.nchunks; out[7] = (F.pb - F.pa) - (F.nchunks - 1) * F.cstride;
+    out[8] = F.cstride; out[9] = F.total;
+    out[10] = (F.total + ncu - 1) / ncu;
+    out[11] = F.per_xcd; out[12] = F.per_xcd * 8;
+  } else { out[2] = Fp.ntx; out[3] = Fp.nty; out[4] = Fp.sx; }
+  if (!G.zwrap) { out[14] = Fp.lz; out[15] = one_pair_launch ? Fp.cstride : 0; }
+  return 0;
+}
+
 }  // extern "C"
 
 #include "bflbm_fieldsel.h"

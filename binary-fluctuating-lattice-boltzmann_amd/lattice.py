@@ -1416,6 +1416,23 @@ def fused_plan_query(n, replicas=1, noise=False, compute_units=0):
     return dict(zip(PLAN_FIELDS, list(out)))
 
 
+SWEEP_PLAN_FIELDS = ("tile_x", "tile_y", "ntx", "nty", "sx", "planes_per_chunk", "chunks", "last_chunk_planes", "chunk_stride",
+                     "workgroups", "rounds", "per_xcd", "grid", "compute_units", "pair_planes", "pair_stride")
+
+
+def sweep_plan_query(n, schedule="handover", noise=False, slab_planes=0, compute_units=0):
+    """The launch plans of the plane-marching sweeps of one step of a lone context (bflbm_sweep_plan_query; no device
+    needed): schedule "fused" or "handover"; slab_planes=0 the whole periodic lattice n, otherwise the interior sweep of a
+    ring's slab of that many planes and its boundary-pair launch.  compute_units as in fused_plan_query.
+    -> dict of SWEEP_PLAN_FIELDS."""
+    n = (n, n, n) if np.isscalar(n) else tuple(n)
+    n3 = (ctypes.c_int * 3)(*[int(v) for v in n])
+    out = (ctypes.c_int * 16)()
+    check(_lib.load().bflbm_sweep_plan_query(n3, int(SCHEDULES.get(schedule, schedule)), int(bool(noise)), int(slab_planes),
+                                             int(compute_units), out))
+    return dict(zip(SWEEP_PLAN_FIELDS, list(out)))
+
+
 def rng_site_normals(seed, site, noise_index):
     """Host evaluation of the project's Gaussian stream: the 33 normals of one site and noise index."""
     out = (ctypes.c_double * 36)()

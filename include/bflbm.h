@@ -284,6 +284,25 @@ int bflbm_batch_sync(bflbm_batch* b);
  * Fails on a null pointer, a size < 1 or too large for a context, nreplicas outside 1..65535, compute_units < 0. */
 int bflbm_fused_plan_query(const int n[3], int nreplicas, int noise, int compute_units, int out[16]);
 
+/* The launch plans of the plane-marching sweeps of ONE step of a lone context: schedule 1 (fused, pulled ring; tiles as in
+ * bflbm_fused_plan_query, noise != 0 selects the noise tile) or 3 (hand-over, 64 x 4 tiles; noise does not change its plan).
+ * slab_planes == 0: the whole periodic lattice n[3], one sweep.  slab_planes > 0: a slab of that many planes of a ring
+ * (nranks > 1): the interior sweep over its planes minus the two boundary pairs, and the boundary-pair launch of
+ * bflbm_step_boundary.  Worked out by the planner the launches call; host arithmetic only, compute_units as in
+ * bflbm_fused_plan_query.  out[0..15]:
+ *    0 tile width, 1 tile height;
+ *    2 tiles in x, 3 tiles in y, 4 strip width in tiles of the column order;
+ *   the interior sweep (all zero for a slab of 4 planes, which has none):
+ *    5 planes per chunk, 6 chunks, 7 planes in the last chunk, 8 planes between the starts of consecutive chunks;
+ *    9 workgroups, 10 rounds = ceil(workgroups / compute units);
+ *   11 length of one XCD's part of the work list, 12 grid size launched (8 x that; the excess workgroups leave at once);
+ *   13 the compute units used;
+ *   the boundary pairs of a slab (zero for slab_planes == 0): 14 planes of each of its two chunks, 15 planes between their
+ *   starts in the one launch that takes both (0: a slab of 4 planes, two launches of one chunk).
+ * Fails on a null pointer, a schedule other than 1 or 3, a size < 1 or too large for a context, slab_planes outside
+ * {0, 4..nz-4}, compute_units < 0, and for schedule 3 on a lattice the hand-over kernel does not take. */
+int bflbm_sweep_plan_query(const int n[3], int schedule, int noise, int slab_planes, int compute_units, int out[16]);
+
 /* ---- Ensemble traces: droplet moments of every replica recorded on the device, read once at the end (the notebooks
  * observe their ensembles every step: nine 32^3 droplets in Surface_Tension.ipynb, a 64^3 droplet's centre of mass 3201
  * times in Droplet_Fluctuation.ipynb, whose estimator where(rho > 0.06, rho, 0) is threshold = 0.06).

@@ -14,7 +14,7 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 BATCH_SYMBOLS = ["bflbm_batch_create", "bflbm_batch_destroy", "bflbm_batch_size", "bflbm_batch_replica",
                  "bflbm_batch_set_schedule", "bflbm_batch_resolved_schedule", "bflbm_batch_step", "bflbm_batch_sync",
-                 "bflbm_fused_plan_query"]
+                 "bflbm_fused_plan_query", "bflbm_sweep_plan_query"]
 
 
 def test_batch_symbols_exported_and_declared(pkg):

@@ -16,6 +16,10 @@ which the trajectory carries forward with its own conditioning.  What is asserte
       thousands of lattice units at near-vacuum sites, the oracle's OWN one-ulp response 1e-9 in the densities and 5e-3 cs in
       the velocities within 100 steps -- stays within 10 x that response (`test_handover_through_spinodal_demixing`).
 `test_named_stress_cases` keeps the four diverging runs of round 2's stress.log.
+Launch plans: every lone shape of this file marches chunks of 4 to 6 planes in one round (250 x 250 x 8 one chunk of 8,
+512 x 512 x 16 one of 16 in 4 rounds; tests/test_sweep_plans.py pins that through the library's planner).  The plans of
+large lattices -- one long chunk, several rounds, cut chunks, long slab interiors -- are pinned against the oracle in
+tests/test_gpu_sweep_plans.py.
 BFLBM_STRICT_COLLECT=<file> appends one JSON line per case and checkpoint (tests/golden/make_strict_exceptions.py turns
 the file into the committed list).
 """
