@@ -1781,6 +1781,7 @@ int bflbm_sweep_plan_query(const int n[3], int schedule, int noise, int slab_pla
 }  // extern "C"
 
 #include "bflbm_fieldsel.h"
+#include "bflbm_spectra.h"
 #include "bflbm_sf.h"
 #include "bflbm_sf_ring.h"
 #include "bflbm_droplet.h"

@@ -1,6 +1,6 @@
 // bflbm_fieldsel.h -- the one field-selection layer of the recorders that read observed fields: field statistics
-// (bflbm_fstat.h), profile, radial and mode traces (bflbm_profile.h, bflbm_radial.h, bflbm_modes.h), spectrum traces
-// (bflbm_spectrum.h, bflbm_spectrum_ring.h) and the ensemble structure factors (bflbm_batch_sf.h).  A kind chooses
+// (bflbm_fstat.h), profile, radial and mode traces (bflbm_profile.h, bflbm_radial.h, bflbm_modes.h) and, through the
+// transform layer (bflbm_spectra.h), the structure factors and the spectrum traces.  A kind chooses
 // variables of one source (hydrovs, hydrovsbar or the noise moments) and, some kinds, pairs of them.  Here is what the
 // kinds share around their kernels: the refusals of those arguments, the selection that tells the observation what to
 // write and the kernels where to read it, the observation itself, the choice of a kernel's NV instantiation and the

@@ -5,18 +5,16 @@
 // observable of a coarsening mixture is S(k, t) per shell and its first moment, which until now was a field download
 // and a numpy fftn per sample.
 // A sample is, on the owner's stream and without a host synchronisation,
-//   the accumulators' observation   batch_observe_launch into the trace's [B][nsel][n] / observe_launch into the scratch buffer,
-//   hipFFT D2Z                      one plan_many of B x nsel transforms / one plan3d execution per distinct variable,
+//   the dense transform of bflbm_spectra.h   the spectra hat[B][nspec][nk],
 //   k_spectrum_bin                  stage 1: per chunk of the sorted list, pair and replica the weighted sum of
 //                                   Re(a^ conj(b^)) / N, threads striding the chunk in index order, the tree of block_sum,
 //   k_spectrum_finish               stage 2: per bin, pair and replica the chunk sums in chunk order, into the slot.
 // The list holds the half-spectrum indices sorted by (bin, index), 4 B each; a chunk never crosses a bin, so a record
 // depends on the spectra and the chunk table alone.  No atomics, no LDS beyond the tree, no scratch.
-// A ring of z-slabs takes its samples by a slab FFT with one sorted list per slab (spectrum_tables::build_slab here, the
-// rest in bflbm_spectrum_ring.h); the handle, the per-handle calls and the two binning kernels are the ones below.
-// The lifecycle and the sample store are those of bflbm_recorder.h, the selection that of bflbm_fieldsel.h.  Included by
-// bflbm.hip after bflbm_batch_sf.h (needs bflbm_ctx, bflbm_batch, block_sum, FftApi, SfPairs, sf_pairs, FieldSelection,
-// field_select_pairs, fields_observe).
+// A ring of z-slabs takes its samples by the slab transform with one sorted list per slab (spectrum_tables::build_slab
+// here, the rest in bflbm_spectrum_ring.h); the handle, the per-handle calls and the two binning kernels are the ones below.
+// The lifecycle and the sample store are those of bflbm_recorder.h, selection and transforms those of bflbm_spectra.h.
+// Included by bflbm.hip after bflbm_spectra.h (needs bflbm_ctx, bflbm_batch, block_sum).
 #ifndef BFLBM_SPECTRUM_H_
 #define BFLBM_SPECTRUM_H_
 
@@ -145,57 +143,36 @@ inline void build(int nx, int ny, int nz, int kind, int zero_avg, uint64_t L, in
 
 #ifndef BFLBM_SPECTRUM_TABLES_ONLY
 
-// a ring's trace (bflbm_spectrum_ring.h): what slab d holds on its own device.  Slab d owns the rows ky in [ky0, ky1).
-struct SpectrumSrc { const double2* h2; int z0, nzl; };   // a source slab of the transpose, as k_spectrum_collect reads it
-struct SpectrumSlab {
-  int device = 0, ky0 = 0, ky1 = 0;
-  long long nk = 0, nchunks = 0;    // nz nky nxc; chunks of the slab's own sorted list
-  hipfftHandle plan2d = nullptr, plan1d = nullptr;
-  double2* h2 = nullptr;            // [var][nzl][ny][nxc]: the 2-D transforms of the own planes; the other slabs read it
-  double2* zb = nullptr;            // [var][nz][nky][nxc]: the own rows of every plane, transformed along z in place
-  uint32_t* d_list = nullptr;       // the slab's tables (spectrum_tables::build_slab)
+// the tables of one sorted list on a device, and the chunk sums of a ring's slab
+struct SpectrumTables {
+  int device = 0;
+  long long nchunks = 0;
+  uint32_t* d_list = nullptr;       // the sorted half-spectrum indices
   spectrum_tables::Chunk* d_chunks = nullptr;
-  int* d_bin_first = nullptr;
-  double* partial = nullptr;        // [pair][chunk]; the bin sums [pair][bin] are the slab's block of the handle's gather
-  SpectrumSrc* d_src = nullptr;     // [nslabs], in slab order
-  bool reachable = false;           // every source is on this device or peer-mapped: k_spectrum_collect may read it in place
-  hipEvent_t planes = nullptr;      // h2 is complete (recorded on the slab's stream) ...
-  hipEvent_t collected = nullptr;   // ... and this slab has taken its rows of every other slab's h2
+  int* d_bin_first = nullptr;       // [nbins + 1]
+  double* partial = nullptr;        // a ring's slab: [pair][chunk]; the bin sums [pair][bin] are its block of the gather
 };
 
 struct bflbm_spectrum : bflbm_sample_store {  // d_rec [capacity][nrep][npairs][nbins], d_stage [nrep][npairs][nchunks]
   int nx = 0, ny = 0, nz = 0;
-  long long nsites = 0, nk = 0;     // sites, half-spectrum size
+  long long nsites = 0;
   int kind = 0, zero_avg = 0;
-  SfPairs pairs;                    // a, b: where the pair's spectra lie in `hat` of one replica
-  FieldSelection fs;                // the distinct variables of the pairs; source 0 hydrovs, 1 hydrovsbar
-  std::vector<int> vars;            // a lone context: the distinct variables, in the order of their spectra
-  int nspec = 0;                    // spectra per replica: fs.sel.nsel of a batch, vars.size() of a lone context
+  SpectraSelection sel;             // source 0 hydrovs, 1 hydrovsbar
   int nbins = 0, max_chunks_per_bin = 0;
   long long nchunks = 0;
   std::vector<long long> count;     // [nbins]
   std::vector<double> q;            // [nbins]
-  double* fields = nullptr;         // a batch: [nrep][nsel][nsites]
-  double2* hat = nullptr;           // [nrep][nspec][nk]
-  uint32_t* d_list = nullptr;       // the sorted half-spectrum indices
-  spectrum_tables::Chunk* d_chunks = nullptr;
-  int* d_bin_first = nullptr;       // [nbins + 1]
-  hipfftHandle plan = nullptr;
-  // a ring: d_stage is [nslabs][npairs][nbins] on slab 0's device, nchunks the slabs' total, max_chunks_per_bin the most
-  // of any (slab, bin); the members from `fields` to `plan` stay empty
-  std::vector<SpectrumSlab> slab;
+  DenseSpectra T;                   // a lone context or a batch
+  // a ring: one table per slab (slab d owns the rows of slabs.slab[d]), d_stage is [nslabs][npairs][nbins] on slab 0's
+  // device, nchunks the slabs' total, max_chunks_per_bin the most of any (slab, bin); T stays empty
+  std::vector<SpectrumTables> tab;  // [1] of a lone context or a batch
+  SlabSpectra slabs;
   RingGather gather;                // slab d's bin sums [npairs][nbins] into block d of d_stage (slab 0 writes block 0 itself)
   bflbm_spectrum() : bflbm_sample_store("spectrum trace", "bflbm_spectrum") {}
   ~bflbm_spectrum() override {
-    if (plan) g_fft.destroy(plan);
-    for (void* p : {(void*)fields, (void*)hat, (void*)d_list, (void*)d_chunks, (void*)d_bin_first}) if (p) hipFree(p);
-    for (SpectrumSlab& q : slab) {
-      hipSetDevice(q.device);
-      if (q.plan2d) g_fft.destroy(q.plan2d);
-      if (q.plan1d) g_fft.destroy(q.plan1d);
-      for (void* p : {(void*)q.h2, (void*)q.zb, (void*)q.d_list, (void*)q.d_chunks, (void*)q.d_bin_first, (void*)q.partial, (void*)q.d_src})
-        if (p) hipFree(p);
-      for (hipEvent_t e : {q.planes, q.collected}) if (e) hipEventDestroy(e);
+    for (SpectrumTables& t : tab) {
+      hipSetDevice(t.device);
+      for (void* p : {(void*)t.d_list, (void*)t.d_chunks, (void*)t.d_bin_first, (void*)t.partial}) if (p) hipFree(p);
     }
   }
   int record() override;
@@ -203,6 +180,29 @@ struct bflbm_spectrum : bflbm_sample_store {  // d_rec [capacity][nrep][npairs][
 };
 
 namespace {
+
+// the tables T on `device`, with npairs rows of chunk sums where a slab keeps its own (partial_pairs > 0)
+int spectrum_tables_upload(SpectrumTables& t, const char* call, int device, const spectrum_tables::Tables& T, int partial_pairs) {
+  t.device = device;
+  t.nchunks = (long long)T.chunks.size();
+  HIP_TRY(hipSetDevice(device));
+  const size_t lb_ = std::max<size_t>(T.list.size(), 1) * sizeof(uint32_t);
+  const size_t cb = std::max<size_t>(T.chunks.size(), 1) * sizeof(spectrum_tables::Chunk), bb = T.bin_first.size() * sizeof(int);
+  const size_t pb = (size_t)partial_pairs * std::max<size_t>(T.chunks.size(), 1) * sizeof(double);
+  hipError_t e = hipMalloc((void**)&t.d_list, lb_);
+  if (e == hipSuccess) e = hipMalloc((void**)&t.d_chunks, cb);
+  if (e == hipSuccess) e = hipMalloc((void**)&t.d_bin_first, bb);
+  if (e == hipSuccess && pb) e = hipMalloc((void**)&t.partial, pb);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail("%s: out of device memory on device %d (index list %zu + chunk table %zu + bin table %zu + chunk sums %zu bytes): %s",
+                call, device, lb_, cb, bb, pb, hipGetErrorString(e));
+  }
+  if (!T.list.empty()) HIP_TRY(hipMemcpy(t.d_list, T.list.data(), T.list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (!T.chunks.empty()) HIP_TRY(hipMemcpy(t.d_chunks, T.chunks.data(), T.chunks.size() * sizeof(spectrum_tables::Chunk), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(t.d_bin_first, T.bin_first.data(), bb, hipMemcpyHostToDevice));
+  return 0;
+}
 
 // Stage 1, grid (chunks, pairs, B): the thread adds weight * (scale a^) . b^ / N of the chunk's entries tid, tid + 256, ...
 // in that order (the product as k_sf_accumulate writes it; the weight, 1 or 2, is exact), the workgroup adds the 256
@@ -260,16 +260,13 @@ int spectrum_refuse_box(const char* call, int kind, const Geo& G, uint64_t* L) {
   return 0;
 }
 
-// the box, the kind and where a pair's spectra lie
+// the box, the kind, where a pair's spectra lie and the bins of the whole box
 void spectrum_select(bflbm_spectrum* t, const Geo& G, int npairs, const int* var_a, const int* var_b, const double* scale,
-                     int lb_hydrovars, int kind, int zero_avg) {
-  t->nx = G.nx; t->ny = G.ny; t->nz = G.nz; t->nk = (long long)(G.nx / 2 + 1) * G.ny * G.nz; t->nsites = (long long)G.nx * G.ny * G.nz;
+                     int lb_hydrovars, int kind, int zero_avg, const spectrum_tables::Tables& T) {
+  t->nx = G.nx; t->ny = G.ny; t->nz = G.nz; t->nsites = (long long)G.nx * G.ny * G.nz;
   t->kind = kind; t->zero_avg = zero_avg ? 1 : 0;
-  // the slots of the batch observation, or the rank among the distinct variables: the same order, the variables ascending
-  t->fs = field_select_pairs(lb_hydrovars ? 1 : 0, npairs, var_a, var_b);
-  for (int v = 0; v < BFLBM_NHYDRO_; ++v) if (t->fs.sel.mask & (1u << v)) t->vars.push_back(v);
-  t->nspec = t->fs.sel.nsel;
-  t->pairs = sf_pairs(t->fs.sel, npairs, var_a, var_b, scale);
+  t->sel = spectra_select(lb_hydrovars ? 1 : 0, npairs, var_a, var_b, scale);
+  t->nbins = T.nbins; t->count = T.count; t->q = T.q;
 }
 
 int spectrum_create(bflbm_ctx* c, bflbm_batch* b, int npairs, const int* var_a, const int* var_b, const double* scale,
@@ -281,49 +278,19 @@ int spectrum_create(bflbm_ctx* c, bflbm_batch* b, int npairs, const int* var_a, 
   if (store_refuse_owner(c, call, "bflbm_batch_spectrum_create", "spectrum trace")) return 1;
   if (recorder_refuse_open(c, b, nullptr, call)) return 1;
   if (spectrum_refuse_box(call, kind, G, &L)) return 1;
-  const int nx = G.nx, ny = G.ny, nz = G.nz;
-  const long long nk = (long long)(nx / 2 + 1) * ny * nz;
   if (load_fft()) return 1;
-  HIP_TRY(hipSetDevice(c ? c->dom.device : b->device));
 
   std::unique_ptr<bflbm_spectrum> t(new bflbm_spectrum());
   const int nrep = c ? 1 : (int)b->ctx.size();
-  spectrum_select(t.get(), G, npairs, var_a, var_b, scale, lb_hydrovars, kind, zero_avg);
   spectrum_tables::Tables T;
-  spectrum_tables::build(nx, ny, nz, kind, t->zero_avg, L, spectrum_tables::kChunkLen, T);
-  t->nbins = T.nbins; t->nchunks = (long long)T.chunks.size(); t->max_chunks_per_bin = T.max_chunks_per_bin;
-  t->count = T.count; t->q = T.q;
-
-  const size_t fb = b ? (size_t)nrep * t->nspec * t->nsites * sizeof(double) : 0;
-  const size_t hb = (size_t)nrep * t->nspec * nk * sizeof(double2);
-  const size_t lb_ = std::max<size_t>(T.list.size(), 1) * sizeof(uint32_t);
-  const size_t cb = std::max<size_t>(T.chunks.size(), 1) * sizeof(spectrum_tables::Chunk), bb = T.bin_first.size() * sizeof(int);
+  spectrum_tables::build(G.nx, G.ny, G.nz, kind, zero_avg, L, spectrum_tables::kChunkLen, T);
+  spectrum_select(t.get(), G, npairs, var_a, var_b, scale, lb_hydrovars, kind, zero_avg, T);
+  t->nchunks = (long long)T.chunks.size(); t->max_chunks_per_bin = T.max_chunks_per_bin;
+  if (dense_create(t->T, call, c, b, t->sel.nspec)) return 1;
+  t->tab.resize(1);
+  if (spectrum_tables_upload(t->tab[0], call, t->T.device, T, 0)) return 1;
   const size_t per = (size_t)nrep * npairs * (size_t)T.nbins;
   const size_t stage = (size_t)nrep * npairs * std::max<size_t>(T.chunks.size(), 1);
-  hipError_t e = fb ? hipMalloc((void**)&t->fields, fb) : hipSuccess;
-  if (e == hipSuccess) e = hipMalloc((void**)&t->hat, hb);
-  if (e == hipSuccess) e = hipMalloc((void**)&t->d_list, lb_);
-  if (e == hipSuccess) e = hipMalloc((void**)&t->d_chunks, cb);
-  if (e == hipSuccess) e = hipMalloc((void**)&t->d_bin_first, bb);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return fail("%s: out of device memory (fields %zu + spectra %zu + index list %zu + chunk table %zu + bin table %zu bytes; then records %zu x %lld + chunk sums %zu): %s",
-                call, fb, hb, lb_, cb, bb, per * sizeof(double), capacity, stage * sizeof(double), hipGetErrorString(e));
-  }
-  if (!T.list.empty()) HIP_TRY(hipMemcpy(t->d_list, T.list.data(), T.list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if (!T.chunks.empty()) HIP_TRY(hipMemcpy(t->d_chunks, T.chunks.data(), T.chunks.size() * sizeof(spectrum_tables::Chunk), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(t->d_bin_first, T.bin_first.data(), bb, hipMemcpyHostToDevice));
-  hipfftResult fr;
-  if (b) {
-    int dims[3] = {nz, ny, nx};
-    fr = g_fft.plan_many(&t->plan, 3, dims, nullptr, 1, (int)t->nsites, nullptr, 1, (int)nk, HIPFFT_D2Z, nrep * t->nspec);
-  } else {
-    fr = g_fft.plan3d(&t->plan, nz, ny, nx, HIPFFT_D2Z);
-  }
-  if (fr != HIPFFT_SUCCESS) {
-    t->plan = nullptr;
-    return fail("%s: the hipFFT plan failed for %d transform(s) of %d x %d x %d", call, b ? nrep * t->nspec : 1, nx, ny, nz);
-  }
   const std::string shape = " x " + std::to_string(npairs) + " pairs x " + std::to_string(T.nbins) + " bins";
   if (store_attach(t.get(), c, b, call, every, capacity, per, stage, shape.c_str())) return 1;
   *out = t.release();
@@ -337,24 +304,15 @@ int bflbm_spectrum::record() {
   if (ring) return record_ring();
   if (store_begin(this)) return 1;
   const hipStream_t stream = recorder_stream(this);
-  g_fft.set_stream(plan, stream);                      // the owner's stream may have been replaced since the last sample
-  const double* dense;
-  long long rep_stride;
-  if (fields_observe(this, fs, fields, "spectrum trace sample", &dense, &rep_stride)) return 1;
-  if (batch) {
-    if (g_fft.exec_d2z(plan, fields, (hipfftDoubleComplex*)hat) != HIPFFT_SUCCESS) return fail("spectrum trace: hipfftExecD2Z failed");
-  } else {
-    for (size_t v = 0; v < vars.size(); ++v)
-      if (g_fft.exec_d2z(plan, const_cast<double*>(dense) + (long long)vars[v] * nsites, (hipfftDoubleComplex*)(hat + (long long)v * nk)) != HIPFFT_SUCCESS)
-        return fail("spectrum trace: hipfftExecD2Z failed");
-  }
+  if (dense_run(T, this, sel.fs, sel.vars, "spectrum trace sample")) return 1;
+  const SfPairs& pairs = sel.pairs;
   if (nchunks > 0) {
     hipLaunchKernelGGL(k_spectrum_bin, dim3((unsigned)nchunks, (unsigned)pairs.n, (unsigned)nrep), dim3(256), 0, stream,
-                       hat, d_list, d_chunks, d_stage, nk, nspec, nx, pairs, 1.0 / (double)nsites);
+                       T.hat, tab[0].d_list, tab[0].d_chunks, d_stage, T.nk, sel.nspec, nx, pairs, 1.0 / (double)nsites);
     HIP_TRY(hipGetLastError());
   }
   hipLaunchKernelGGL(k_spectrum_finish, dim3((unsigned)((nbins + 255) / 256), (unsigned)pairs.n, (unsigned)nrep), dim3(256), 0, stream,
-                     d_stage, d_bin_first, store_slot(this), nbins, std::max(nchunks, 1LL));
+                     d_stage, tab[0].d_bin_first, store_slot(this), nbins, std::max(nchunks, 1LL));
   HIP_TRY(hipGetLastError());
   store_recorded(this);
   return 0;
@@ -384,7 +342,7 @@ int bflbm_spectrum_read(bflbm_spectrum* t, long long first, long long count, dou
 int bflbm_spectrum_geometry(const bflbm_spectrum* t, int* nbins, int* npairs, long long* nchunks, int* max_chunks_per_bin) {
   if (!t) return fail("bflbm_spectrum_geometry: null argument");
   if (nbins) *nbins = t->nbins;
-  if (npairs) *npairs = t->pairs.n;
+  if (npairs) *npairs = t->sel.pairs.n;
   if (nchunks) *nchunks = t->nchunks;
   if (max_chunks_per_bin) *max_chunks_per_bin = t->max_chunks_per_bin;
   return 0;

@@ -1043,7 +1043,10 @@ int bflbm_sync(bflbm_ctx* c);
  * hydrovsbar (the shipped STRUCT_LB_HYDROVARS build, main_run_job.cpp:19, :344); scale may be NULL (1).
  * bflbm_sf_get returns the full fft-shifted spectrum (k = 0 at cell n/2) [npairs][nz][ny][nx]:
  * what 0 magnitude, 1 real, 2 imaginary part; zero_avg != 0 removes k = 0.  Needs the whole lattice in
- * one context (nranks == 1).  hipFFT is loaded at first use; without it these calls fail, nothing else. */
+ * one context (nranks == 1).  hipFFT is loaded at first use; without it these calls fail, nothing else.
+ * The accumulator is a recorder that stepping never serves (every = 0): bflbm_destroy of its context detaches it.
+ * Detached, bflbm_sf_nsamples, _reset and _destroy work, bflbm_sf_accumulate fails, and so does bflbm_sf_get, whose
+ * expansion is written into the context's scratch buffer.  Creation and a frame inside an open step are refused. */
 typedef struct bflbm_sf bflbm_sf;
 int bflbm_sf_create(bflbm_ctx* c, int npairs, const int* var_a, const int* var_b, const double* scale, bflbm_sf** out);
 int bflbm_sf_destroy(bflbm_sf* s);
@@ -1053,9 +1056,16 @@ int bflbm_sf_nsamples(const bflbm_sf* s, long long* n);
 int bflbm_sf_get(bflbm_sf* s, int what, int zero_avg, double* dst);
 
 /* The same accumulator for a lattice decomposed into the z-slabs of a bflbm_ring (any number of slabs, on one or
- * several GPUs): 2-D transforms of every slab's own planes, a transpose over the slabs (strided peer copies), z
- * transforms of row blocks, pair products per slab; bflbm_ring_sf_get assembles and expands the mean on the host.
- * Same arguments, normalisation and output layout as bflbm_sf_*; a ring of one slab delegates to it. */
+ * several GPUs): 2-D transforms of every slab's own planes, a transpose over the slabs, z transforms of row blocks,
+ * pair products per slab; bflbm_ring_sf_get assembles and expands the mean on the host.  A frame is stream-ordered like
+ * a sample of the ring's spectrum trace: events between the slabs' streams and no host synchronisation (hydrovs under
+ * a reference state excepted: the global centre of mass is summed on the host first).  The transpose reads its sources
+ * in place where every slab is on one device or peer-mapped and neither bflbm_ring_set_transport(1) nor
+ * BFLBM_RING_COPY_FALLBACK=1 asks for copies, by strided (peer) copies otherwise; both move the same doubles.
+ * bflbm_ring_sf_get, _reset and _destroy order themselves after the frames enqueued.
+ * Same arguments, normalisation and output layout as bflbm_sf_*; a ring of one slab delegates to it.  bflbm_ring_destroy
+ * detaches the accumulator as bflbm_destroy does a lone one; detached, bflbm_ring_sf_get still works: it reads only the
+ * accumulators the handle owns. */
 typedef struct bflbm_ring_sf bflbm_ring_sf;
 int bflbm_ring_sf_create(bflbm_ring* r, int npairs, const int* var_a, const int* var_b, const double* scale, bflbm_ring_sf** out);
 int bflbm_ring_sf_destroy(bflbm_ring_sf* s);

@@ -106,7 +106,7 @@ def _scratch_size(asm, kernel, template_arg=None):
     return int(m.group(1))
 
 
-@pytest.mark.parametrize("kernel,arg", [("k_sf_accumulate_batch", None), ("k_sf_expand_batch", None), ("k_observe_batch", 0)])
+@pytest.mark.parametrize("kernel,arg", [("k_sf_accumulate", None), ("k_sf_expand", None), ("k_observe_batch", 0)])
 def test_batch_sf_kernel_compiled_without_scratch(device_asm, kernel, arg):
     assert _scratch_size(device_asm, kernel, arg) == 0, f"{kernel} spills to scratch"
 

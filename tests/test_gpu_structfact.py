@@ -2,7 +2,10 @@
 twin (structfact.py, numpy FFT of downloaded frames).  FHDeX's StructFact is un-vendored: both follow the
 reference's call sites (main_run_job.cpp:301-310, :342-349, :50-54) -- parity unpinned beyond that.
 Two FFT libraries agree to rounding: tolerance 1e-11 of the largest |S| of each pair."""
+import ctypes
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -118,3 +121,138 @@ def test_structure_factor_on_a_slab_decomposed_lattice(pkg, nslabs, n):
     one.LBM_timestep(1); ring.LBM_timestep(1)
     assert np.array_equal(one.populations()[0], ring.populations()[0])
     dr.close(); d1.close(); one.close(); ring.close()
+
+
+# ---- the transform layer (csrc/bflbm_spectra.h) under the lone and the ring accumulator ---------------------------------------
+# Shapes whose ky rows and z planes both split unevenly over 3 slabs: (12, 10, 14) rows 3 / 3 / 4, planes 4 / 5 / 5;
+# (9, 7, 12) rows 2 / 2 / 3, planes 4 / 4 / 4, odd nx (nxc = 5).
+SHAPES = [(12, 10, 14), (9, 7, 12)]
+MIXTURE = dict(kBT=1e-5, alpha0=1.0, tau_f=1.0, tau_g=1.0)
+
+
+def _frames(pkg, lbm, names=22, lb=False, between=None):
+    """Three frames four steps apart after 12 steps, as [mean(0), mean(1), magnitude(1)]; closes everything."""
+    lbm.LBM_init_mixture()
+    dev = pkg.structfact.DeviceStructFact(lbm, pkg.plotfile.variable_names(names), lb_hydrovars=lb)
+    lbm.LBM_timestep(12)
+    for _ in range(3):
+        lbm.LBM_timestep(4)
+        dev.fort_structure()
+        if between:
+            between()
+    out = [dev.mean(0), dev.mean(1), dev.magnitude(1)]
+    assert dev.nsamples == 3 and all(np.isfinite(a).all() for a in out) and np.abs(out[0]).max() > 0
+    dev.close(); lbm.close()
+    return out
+
+
+def _ring_means(pkg, transport=None):
+    out = {}
+    for n in SHAPES:
+        ring = pkg.RingLBM(*n, nslabs=3, params=pkg.default_params(**MIXTURE))
+        if transport:
+            ring.set_transport(transport)
+        m0, m1, _ = _frames(pkg, ring)
+        out["m0_%d_%d_%d" % n] = m0
+        out["m1_%d_%d_%d" % n] = m1
+    return out
+
+
+def test_ring_accumulator_does_not_depend_on_the_transport(pkg, tmp_path):
+    """The 22 hydrovs pairs on both shapes: the means with the sources read in place (fresh process, nothing set), with
+    BFLBM_RING_COPY_FALLBACK=1 (fresh process: the switch is read once) and after set_transport("copy") are the same doubles."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys, numpy as np; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "import __graft_entry__ as ge, test_gpu_structfact as t\n"
+            "got = t._ring_means(ge.load_package())\n"
+            "np.savez(sys.argv[1], **got)\n"
+            "print('SAVED', len(got))\n") % (root, os.path.join(root, "tests"))
+    recs = [_ring_means(pkg, "copy")]
+    for tag, env in (("kernel", {}), ("copies", {"BFLBM_RING_COPY_FALLBACK": "1"})):
+        path = str(tmp_path / (tag + ".npz"))
+        out = subprocess.run([sys.executable, "-c", code, path], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0 and "SAVED 4" in out.stdout, (env, out.stdout[-500:], out.stderr[-1500:])
+        recs.append(dict(np.load(path)))
+    assert len(recs[0]) == 4
+    for key, ref in recs[0].items():
+        assert ref.shape[0] == 22
+        assert np.array_equal(ref, recs[1][key]) and np.array_equal(ref, recs[2][key]), key
+
+
+@pytest.mark.parametrize("names,lb", [(22, False), (9, True)])
+def test_ring_of_one_slab_is_the_lone_accumulator(pkg, names, lb):
+    n = SHAPES[1]
+    par = pkg.default_params(**MIXTURE)
+    ring = _frames(pkg, pkg.RingLBM(*n, nslabs=1, params=par), names, lb)
+    lone = _frames(pkg, pkg.BinaryLBM(*n, params=par), names, lb)
+    for a, b in zip(ring, lone):
+        assert np.array_equal(a, b)
+
+
+def test_ring_frames_are_stream_ordered_and_change_nothing(pkg):
+    n = SHAPES[0]
+    par = pkg.default_params(**MIXTURE)
+    names = pkg.plotfile.variable_names(22)
+    rings = [pkg.RingLBM(*n, nslabs=3, params=par) for _ in range(3)]
+    for r in rings:
+        r.LBM_init_mixture()
+    back_to_back, synced, none = rings
+    devs = [pkg.structfact.DeviceStructFact(r, names) for r in (back_to_back, synced)]
+    for r in rings:
+        r.LBM_timestep(12)
+    devs[0].fort_structure(); devs[0].fort_structure()       # no call between the frames
+    devs[1].fort_structure(); synced.sync(); devs[1].fort_structure()
+    for r in rings:
+        r.LBM_timestep(1)
+    f, g = back_to_back.populations()
+    f0, g0 = none.populations()
+    assert np.array_equal(f, f0) and np.array_equal(g, g0)
+    for z in (0, 1):
+        assert np.array_equal(devs[0].mean(z), devs[1].mean(z))
+    for o in devs + rings:
+        o.close()
+
+
+@pytest.mark.parametrize("nslabs,n", [(0, SHAPES[1]), (3, SHAPES[0])])
+def test_accumulator_outlives_its_owner(pkg, nslabs, n):
+    """The owner is destroyed first (nslabs 0: a lone context).  The detached accumulator counts, resets and is destroyed;
+    it takes no frame; a ring's still reads what it owns, a lone one says why it cannot."""
+    lib = pkg._lib.load()
+    par = pkg.default_params(**MIXTURE)
+    lbm = pkg.RingLBM(*n, nslabs=nslabs, params=par) if nslabs else pkg.BinaryLBM(*n, params=par)
+    lbm.LBM_init_mixture(); lbm.LBM_timestep(3)
+    dev = pkg.structfact.DeviceStructFact(lbm, pkg.plotfile.variable_names(22))
+    dev.fort_structure()
+    before = dev._get(1, 1)
+    pre, h = dev._pre, dev._h
+    call = lambda name, *a: getattr(lib, pre + name)(h, *a)
+    lbm._dependents.remove(dev)                               # Python would close the accumulator first
+    lbm.close()
+    count = ctypes.c_longlong(-1)
+    assert call("nsamples", ctypes.byref(count)) == 0 and count.value == 1
+    assert call("accumulate", 0, 0) != 0
+    msg = lib.bflbm_last_error().decode()
+    assert pre + "accumulate" in msg and "destroyed" in msg, msg
+    after = np.full_like(before, np.nan)
+    rc = call("get", 1, 1, after.ctypes.data_as(ctypes.c_void_p))
+    if nslabs:
+        assert rc == 0 and np.array_equal(after, before)
+    else:
+        msg = lib.bflbm_last_error().decode()
+        assert rc != 0 and "bflbm_sf_get" in msg and "destroyed" in msg and "scratch buffer" in msg, msg
+    assert call("reset") == 0
+    assert call("nsamples", ctypes.byref(count)) == 0 and count.value == 0
+    assert call("destroy") == 0
+    dev._h = None
+
+
+@pytest.mark.parametrize("nslabs,n", [(0, SHAPES[1]), (3, SHAPES[0])])
+def test_accumulator_destroyed_before_its_owner(pkg, nslabs, n):
+    par = pkg.default_params(**MIXTURE)
+    lbm = pkg.RingLBM(*n, nslabs=nslabs, params=par) if nslabs else pkg.BinaryLBM(*n, params=par)
+    lbm.LBM_init_mixture()
+    dev = pkg.structfact.DeviceStructFact(lbm, pkg.plotfile.variable_names(22))
+    dev.fort_structure()
+    dev.close()
+    lbm.LBM_timestep(1)                                       # the owner no longer knows the accumulator
+    lbm.close()

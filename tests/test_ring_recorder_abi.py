@@ -54,6 +54,35 @@ def test_ring_recorder_null_pointers_are_refused(pkg):
             assert not h.value
 
 
+def test_structure_factor_null_pointers_are_refused(pkg):
+    """The twelve bflbm_sf_* / bflbm_ring_sf_* calls: every null-argument refusal names its call and comes before any
+    device is touched; the two _destroy calls take a null handle like free() and return 0."""
+    lib = pkg._lib.load()
+    h, n = ctypes.c_void_p(), ctypes.c_longlong()
+    owner = ctypes.c_void_p(8)                               # never dereferenced: the other null argument is refused first
+    va, vb = (ctypes.c_int * 1)(0), (ctypes.c_int * 1)(1)
+    buf = (ctypes.c_double * 1)()
+    for pre in ("bflbm_sf_", "bflbm_ring_sf_"):
+        f = lambda name: getattr(lib, pre + name)
+        calls = {
+            "create": [lambda: f("create")(None, 1, va, vb, None, ctypes.byref(h)),
+                       lambda: f("create")(owner, 1, None, vb, None, ctypes.byref(h)),
+                       lambda: f("create")(owner, 1, va, None, None, ctypes.byref(h)),
+                       lambda: f("create")(owner, 1, va, vb, None, None)],
+            "reset": [lambda: f("reset")(None)],
+            "accumulate": [lambda: f("accumulate")(None, 0, 0)],
+            "nsamples": [lambda: f("nsamples")(None, ctypes.byref(n)), lambda: f("nsamples")(owner, None)],
+            "get": [lambda: f("get")(None, 0, 1, buf), lambda: f("get")(owner, 0, 1, None)],
+        }
+        for name, variants in calls.items():
+            for call in variants:
+                assert call() != 0, pre + name
+                msg = lib.bflbm_last_error().decode()
+                assert "null argument" in msg and pre + name in msg, (pre + name, msg)
+                assert not h.value
+        assert f("destroy")(None) == 0
+
+
 # ---- the slab tables -------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def tables_program(tmp_path_factory):
