@@ -486,6 +486,8 @@ double* halo_buffer(bflbm_ctx* c, int kind) {
 
 }  // namespace
 
+#include "bflbm_reduce.h"
+
 extern "C" {
 
 void bflbm_default_params(bflbm_params* p) {
@@ -860,20 +862,11 @@ int bflbm_commit_upload(bflbm_ctx* c, int reset) {
   // (handover_contract_params).  The own planes' densities need no halo (the upload buffer holds the streamed populations
   // of every own site), so the slab reduces its own maximum; a ring combines the slabs' (bflbm_ring_commit_upload).
   // A NaN in the upload, or a failed reduction: never schedule 3.
-  double m = std::numeric_limits<double>::infinity();
-  const int rc = [&]() -> int {
-    const int lo = own_lo(c);
-    hipLaunchKernelGGL(k_density_streamed, plane_grid(c, c->nzl), dim3(256), 0, c->stream, c->S[1 - c->cur], c->rho, c->phi, c->G, lo);
-    hipLaunchKernelGGL(k_total_absmax, plane_grid(c, c->nzl), dim3(256), 0, c->stream, c->rho, c->phi, c->partial, c->G, lo);
-    HIP_TRY(hipGetLastError());
-    std::vector<double> h(c->partial_n);
-    HIP_TRY(hipMemcpyAsync(h.data(), c->partial, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    double v_max = 0.;
-    for (double v : h) v_max = (v != v || v_max != v_max) ? (v_max + v) : std::max(v_max, v);
-    if (v_max == v_max) m = v_max;
-    return 0;
-  }();
+  double m = std::numeric_limits<double>::infinity(), v[1] = {0.};
+  hipLaunchKernelGGL(k_density_streamed, plane_grid(c, c->nzl), dim3(256), 0, c->stream, c->S[1 - c->cur], c->rho, c->phi, c->G, own_lo(c));
+  const int rc = slab_reduce<1, AbsMaxRule>(c, Fold::HostBlocks, false, v, [&](dim3 g, double* partial) {
+    hipLaunchKernelGGL(k_total_absmax, g, dim3(256), 0, c->stream, c->rho, c->phi, partial, c->G, own_lo(c)); });
+  if (!rc && v[0] == v[0]) m = v[0];
   state_replaced(c, reset ? 0 : c->steps, 0, m);   // LBM_init: COM relative to com_ref (:651-654)
   return rc;
 }
@@ -1078,18 +1071,10 @@ int bflbm_inject_noise(bflbm_ctx* c, const double* fn, const double* gn, const b
   return 0;
 }
 
-static int reduce5(bflbm_ctx* c, double out[5]) {
-  if (c->step_open()) return fail("reduction requested inside an open step");
-  HIP_TRY(hipSetDevice(c->dom.device));
-  if (ensure_density(c)) return 1;
-  hipLaunchKernelGGL(k_reduce, plane_grid(c, c->nzl), dim3(256), 0, c->stream, c->rho, c->phi, c->partial, c->G, own_lo(c));
-  HIP_TRY(hipGetLastError());
-  std::vector<double> h(c->partial_n * 5);
-  HIP_TRY(hipMemcpyAsync(h.data(), c->partial, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+static int reduce5(bflbm_ctx* c, double (&out)[5]) {
   for (int k = 0; k < 5; ++k) out[k] = 0.;
-  for (size_t b = 0; b < c->partial_n; ++b) for (int k = 0; k < 5; ++k) out[k] += h[b * 5 + k];
-  return 0;
+  return slab_reduce<5, SumRule>(c, Fold::HostBlocks, true, out, [&](dim3 g, double* partial) {
+    hipLaunchKernelGGL(k_reduce, g, dim3(256), 0, c->stream, c->rho, c->phi, partial, c->G, own_lo(c)); });
 }
 
 int bflbm_com_sums(bflbm_ctx* c, double sums[4]) {

@@ -3,7 +3,7 @@
 // of Droplet_Fluctuation.ipynb / Surface_Tension.ipynb cell 3.  The reference's C++ twins are
 // getCenterOfMass / fittingDropletCovariance / fittingDropletParams (LBM_hydrovs.H:62-335, off by default,
 // main_run_job.cpp:111); the host-side numpy restatement these are tested against is analysis.py.
-// Included by bflbm.hip (needs bflbm_ctx).
+// Included by bflbm.hip (needs bflbm_ctx and bflbm_reduce.h: the tree, stage 2 and the host side of every reduction here).
 #ifndef BFLBM_DROPLET_H_
 #define BFLBM_DROPLET_H_
 
@@ -12,33 +12,15 @@ namespace {
 constexpr int kNMom = 20;    // {1, x, y, z, xx, xy, xz, yy, yz, zz} x {plain, trapezoid-weighted}
 constexpr int kNFit = 15;    // J^T J (10), J^T e (4), e^2
 
-template <int NV>
-__device__ __forceinline__ void block_sum(double (&v)[NV], double* __restrict__ partial) {
-  __shared__ double sh[NV][256];
-  for (int k = 0; k < NV; ++k) sh[k][threadIdx.x] = v[k];
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) for (int k = 0; k < NV; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const long long b = (long long)blockIdx.y * gridDim.x + blockIdx.x;
-    for (int k = 0; k < NV; ++k) partial[b * NV + k] = sh[k][0];
-  }
-}
-
 // raw moments of rho in GLOBAL cell indices; the weighted set counts the end planes of the lattice half in
 // every direction (Integration::trapezoid3DWeightTensor in the reference, the notebook's `wt`)
 __global__ void __launch_bounds__(256) k_moments(const double* __restrict__ rho, double* __restrict__ partial, Geo G, int p0) {
-  const long long s_ = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int p = p0 + (int)blockIdx.y;
+  const PlaneSite st = plane_site(G, p0);
+  const int x = st.x, y = st.y, z = st.z;
   double v[kNMom];
   for (int k = 0; k < kNMom; ++k) v[k] = 0.;
-  const int y = (int)(s_ / G.pitch);
-  const int x = (int)(s_ - (long long)y * G.pitch);
-  if (s_ < G.plane && x < G.nx) {
-    const int z = G.z0 + (p - G.H);
-    const double r = rho[(long long)p * G.plane + s_];
+  if (st.in) {
+    const double r = rho[(long long)st.p * G.plane + st.s];
     double w = r;
     if (x == 0 || x == G.nx - 1) w *= 0.5;
     if (y == 0 || y == G.ny - 1) w *= 0.5;
@@ -47,27 +29,23 @@ __global__ void __launch_bounds__(256) k_moments(const double* __restrict__ rho,
                            (double)y * y, (double)y * z, (double)z * z };
     for (int k = 0; k < 10; ++k) { v[k] = r * m[k]; v[10 + k] = w * m[k]; }
   }
-  block_sum<kNMom>(v, partial);
+  block_reduce<kNMom>(v, partial);
 }
 
 // normal equations of rho(r) = hi - (hi - lo)/2 (1 + tanh((r - R)/W)), r = |cell centre - r0| in the unit box
 struct FitParams { double hi, lo, R, W, r0[3], inv_n[3]; };
 __global__ void __launch_bounds__(256) k_tanhfit(const double* __restrict__ rho, double* __restrict__ partial, Geo G, int p0, FitParams F) {
-  const long long s_ = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int p = p0 + (int)blockIdx.y;
+  const PlaneSite st = plane_site(G, p0);
   double v[kNFit];
   for (int k = 0; k < kNFit; ++k) v[k] = 0.;
-  const int y = (int)(s_ / G.pitch);
-  const int x = (int)(s_ - (long long)y * G.pitch);
-  if (s_ < G.plane && x < G.nx) {
-    const int z = G.z0 + (p - G.H);
-    const double dx = (x + 0.5) * F.inv_n[0] - F.r0[0], dy = (y + 0.5) * F.inv_n[1] - F.r0[1], dz = (z + 0.5) * F.inv_n[2] - F.r0[2];
+  if (st.in) {
+    const double dx = (st.x + 0.5) * F.inv_n[0] - F.r0[0], dy = (st.y + 0.5) * F.inv_n[1] - F.r0[1], dz = (st.z + 0.5) * F.inv_n[2] - F.r0[2];
     const double r = sqrt(dx * dx + dy * dy + dz * dz);
     const double u = (r - F.R) / F.W;
     const double t = tanh(u);
     const double half = 0.5 * (1. + t);
     const double model = F.hi - (F.hi - F.lo) * half;
-    const double e = rho[(long long)p * G.plane + s_] - model;
+    const double e = rho[(long long)st.p * G.plane + st.s] - model;
     const double sech2 = 1. - t * t;
     const double amp = 0.5 * (F.hi - F.lo) * sech2 / F.W;
     const double J[4] = { 1. - half, half, amp, amp * u };          // d model / d (hi, lo, R, W)
@@ -76,57 +54,14 @@ __global__ void __launch_bounds__(256) k_tanhfit(const double* __restrict__ rho,
     for (int a = 0; a < 4; ++a) v[10 + a] = J[a] * e;
     v[14] = e * e;
   }
-  block_sum<kNFit>(v, partial);
-}
-
-// second stage on the device: one workgroup per plane adds that plane's block partials (fixed order: every thread a strided
-// subsequence, then the tree of block_sum), so that a reduction hands O(nz) doubles to the host instead of one per block --
-// the gradient-flow fit runs ~400 such reductions per fit, at 512^3 that was 8 MB per reduction
-template <int NV>
-__global__ void __launch_bounds__(256) k_sum_partials(const double* __restrict__ partial, double* __restrict__ out, int nbx) {
-  __shared__ double sh[NV][256];
-  double v[NV];
-  for (int k = 0; k < NV; ++k) v[k] = 0.;
-  const long long base = (long long)blockIdx.x * nbx;
-  for (int b = threadIdx.x; b < nbx; b += 256) for (int k = 0; k < NV; ++k) v[k] += partial[(base + b) * NV + k];
-  for (int k = 0; k < NV; ++k) sh[k][threadIdx.x] = v[k];
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) for (int k = 0; k < NV; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) for (int k = 0; k < NV; ++k) out[(long long)blockIdx.x * NV + k] = sh[k][0];
-}
-
-// block partials of one launch -> per-plane sums on the device -> ADDED to `out` plane by plane on the host.  The caller zeroes
-// `out` once and passes the slabs in order, so the sum runs over the planes of the whole lattice in one fixed sequence whatever
-// the decomposition: a ring gives the same doubles as the single context.
-template <int NV, class Launch>
-int reduce_blocks(bflbm_ctx* c, double (&out)[NV], Launch launch) {
-  if (c->step_open()) return fail("reduction requested inside an open step");
-  HIP_TRY(hipSetDevice(c->dom.device));
-  if (ensure_density(c)) return 1;
-  const dim3 g = plane_grid(c, c->nzl);
-  const size_t nblocks = (size_t)g.x * g.y;
-  static_assert(NV <= 20, "scratch sizing");
-  double* scratch = c->S[1 - c->cur];               // far larger than (nblocks + planes)*NV
-  double* planes = scratch + nblocks * NV;
-  launch(g, scratch);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL((k_sum_partials<NV>), dim3(g.y), dim3(256), 0, c->stream, scratch, planes, (int)g.x);
-  HIP_TRY(hipGetLastError());
-  std::vector<double> h((size_t)g.y * NV);
-  HIP_TRY(hipMemcpyAsync(h.data(), planes, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (size_t b = 0; b < (size_t)g.y; ++b) for (int k = 0; k < NV; ++k) out[k] += h[b * NV + k];
-  return 0;
+  block_reduce<kNFit>(v, partial);
 }
 
 int moments_of(const std::vector<bflbm_ctx*>& ctx, double out[kNMom]) {
   double m[kNMom];
   for (int k = 0; k < kNMom; ++k) m[k] = 0.;
   for (bflbm_ctx* c : ctx)
-    if (reduce_blocks<kNMom>(c, m, [&](dim3 g, double* scratch) {
+    if (slab_reduce<kNMom, SumRule>(c, Fold::Planes, true, m, [&](dim3 g, double* scratch) {
           hipLaunchKernelGGL(k_moments, g, dim3(256), 0, c->stream, c->rho, scratch, c->G, own_lo(c)); })) return 1;
   for (int k = 0; k < kNMom; ++k) out[k] = m[k];
   return 0;
@@ -136,7 +71,7 @@ int normal_equations(const std::vector<bflbm_ctx*>& ctx, const FitParams& F, dou
   double m[kNFit];
   for (int k = 0; k < kNFit; ++k) m[k] = 0.;
   for (bflbm_ctx* c : ctx)
-    if (reduce_blocks<kNFit>(c, m, [&](dim3 g, double* scratch) {
+    if (slab_reduce<kNFit, SumRule>(c, Fold::Planes, true, m, [&](dim3 g, double* scratch) {
           hipLaunchKernelGGL(k_tanhfit, g, dim3(256), 0, c->stream, c->rho, scratch, c->G, own_lo(c), F); })) return 1;
   for (int k = 0; k < kNFit; ++k) out[k] = m[k];
   return 0;
@@ -309,73 +244,32 @@ inline FlowCoef flow_coefficients(double W, double R, double eta_W, double eta_R
 // Mf_W, Mf_R (MfWn, MfRn, externlib.H:255-342): sum over cell centres of rho dist sech^2(dist / sqrt(2W)) and rho sech^2(...)
 struct FlowParams { double R, inv_s2w, r0[3], inv_n[3]; };
 __global__ void __launch_bounds__(256) k_flowfit(const double* __restrict__ rho, double* __restrict__ partial, Geo G, int p0, FlowParams F) {
-  const long long s_ = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int p = p0 + (int)blockIdx.y;
+  const PlaneSite st = plane_site(G, p0);
   double v[2] = {0., 0.};
-  const int y = (int)(s_ / G.pitch);
-  const int x = (int)(s_ - (long long)y * G.pitch);
-  if (s_ < G.plane && x < G.nx) {
-    const int z = G.z0 + (p - G.H);
-    const double dx = (x + 0.5) * F.inv_n[0] - F.r0[0], dy = (y + 0.5) * F.inv_n[1] - F.r0[1], dz = (z + 0.5) * F.inv_n[2] - F.r0[2];
+  if (st.in) {
+    const double dx = (st.x + 0.5) * F.inv_n[0] - F.r0[0], dy = (st.y + 0.5) * F.inv_n[1] - F.r0[1], dz = (st.z + 0.5) * F.inv_n[2] - F.r0[2];
     const double dist = F.R - sqrt(dx * dx + dy * dy + dz * dz);
     const double u = dist * F.inv_s2w;
     const double sech = fabs(u) < 710.4 ? 1. / cosh(u) : 0.;       // inv_acosh, externlib.H:25-32
-    const double r = rho[(long long)p * G.plane + s_];
+    const double r = rho[(long long)st.p * G.plane + st.s];
     v[0] = r * (dist * sech * sech);
     v[1] = r * (sech * sech);
   }
-  block_sum<2>(v, partial);
+  block_reduce<2>(v, partial);
 }
 // per-block minimum and maximum of rho (C0 = max - min, LBM_hydrovs.H:128-129)
 __global__ void __launch_bounds__(256) k_minmax(const double* __restrict__ rho, double* __restrict__ partial, Geo G, int p0) {
-  __shared__ double lo[256], hi[256];
-  const long long s_ = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int p = p0 + (int)blockIdx.y;
-  const int y = (int)(s_ / G.pitch);
-  const int x = (int)(s_ - (long long)y * G.pitch);
-  const bool in = s_ < G.plane && x < G.nx;
-  const double r = in ? rho[(long long)p * G.plane + s_] : 0.;
-  lo[threadIdx.x] = in ? r : 1e300; hi[threadIdx.x] = in ? r : -1e300;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) { lo[threadIdx.x] = fmin(lo[threadIdx.x], lo[threadIdx.x + w]); hi[threadIdx.x] = fmax(hi[threadIdx.x], hi[threadIdx.x + w]); }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { const long long b = (long long)blockIdx.y * gridDim.x + blockIdx.x; partial[2 * b] = lo[0]; partial[2 * b + 1] = hi[0]; }
-}
-// second stage of k_minmax: one workgroup per plane
-__global__ void __launch_bounds__(256) k_minmax_partials(const double* __restrict__ partial, double* __restrict__ out, int nbx) {
-  __shared__ double lo[256], hi[256];
-  double l = 1e300, h = -1e300;
-  const long long base = (long long)blockIdx.x * nbx;
-  for (int b = threadIdx.x; b < nbx; b += 256) { l = fmin(l, partial[2 * (base + b)]); h = fmax(h, partial[2 * (base + b) + 1]); }
-  lo[threadIdx.x] = l; hi[threadIdx.x] = h;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) { lo[threadIdx.x] = fmin(lo[threadIdx.x], lo[threadIdx.x + w]); hi[threadIdx.x] = fmax(hi[threadIdx.x], hi[threadIdx.x + w]); }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { out[2 * blockIdx.x] = lo[0]; out[2 * blockIdx.x + 1] = hi[0]; }
+  const PlaneSite st = plane_site(G, p0);
+  const double r = st.in ? rho[(long long)st.p * G.plane + st.s] : 0.;
+  const double v[2] = { st.in ? r : 1e300, st.in ? r : -1e300 };
+  block_reduce<2, MinMaxRule>(v, partial);
 }
 int rho_range(const std::vector<bflbm_ctx*>& ctx, double& lo, double& hi) {
-  lo = 1e300; hi = -1e300;
-  for (bflbm_ctx* c : ctx) {
-    if (c->step_open()) return fail("reduction requested inside an open step");
-    HIP_TRY(hipSetDevice(c->dom.device));
-    if (ensure_density(c)) return 1;
-    const dim3 g = plane_grid(c, c->nzl);
-    const size_t nb = (size_t)g.x * g.y;
-    double* scratch = c->S[1 - c->cur];
-    hipLaunchKernelGGL(k_minmax, g, dim3(256), 0, c->stream, c->rho, scratch, c->G, own_lo(c));
-    HIP_TRY(hipGetLastError());
-    double* planes = scratch + 2 * nb;
-    hipLaunchKernelGGL(k_minmax_partials, dim3(g.y), dim3(256), 0, c->stream, scratch, planes, (int)g.x);
-    HIP_TRY(hipGetLastError());
-    std::vector<double> h(2 * (size_t)g.y);
-    HIP_TRY(hipMemcpyAsync(h.data(), planes, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (size_t b = 0; b < (size_t)g.y; ++b) { lo = std::min(lo, h[2 * b]); hi = std::max(hi, h[2 * b + 1]); }
-  }
+  double m[2] = { 1e300, -1e300 };
+  for (bflbm_ctx* c : ctx)
+    if (slab_reduce<2, MinMaxRule>(c, Fold::Planes, true, m, [&](dim3 g, double* scratch) {
+          hipLaunchKernelGGL(k_minmax, g, dim3(256), 0, c->stream, c->rho, scratch, c->G, own_lo(c)); })) return 1;
+  lo = m[0]; hi = m[1];
   return 0;
 }
 
@@ -395,7 +289,7 @@ int flow_run(const std::vector<bflbm_ctx*>& ctx, const FlowSeries& S, const doub
     P.inv_n[0] = 1. / G.nx; P.inv_n[1] = 1. / G.ny; P.inv_n[2] = 1. / G.nz;
     double m[2] = {0., 0.};
     for (bflbm_ctx* c : ctx)
-      if (reduce_blocks<2>(c, m, [&](dim3 g, double* scratch) {
+      if (slab_reduce<2, SumRule>(c, Fold::Planes, true, m, [&](dim3 g, double* scratch) {
             hipLaunchKernelGGL(k_flowfit, g, dim3(256), 0, c->stream, c->rho, scratch, c->G, own_lo(c), P); })) return 1;
     const double s2w = sqrt(2. * W);
     const double MfW = m[0] * cell / (s2w * s2w * s2w), MfR = m[1] * cell / s2w;

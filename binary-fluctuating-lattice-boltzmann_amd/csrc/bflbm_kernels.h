@@ -378,55 +378,4 @@ __global__ void __launch_bounds__(256) k_halo_pull(double* __restrict__ D, const
   *reinterpret_cast<double2*>(D + (long long)Td.comp[e]*dvol + (long long)Td.plane[e]*plane + s) = v;
 }
 
-// ---- slab reductions (deterministic: per-block partials, summed on the host in block order)
-// out[b][0..5] = sum rho, sum phi, sum rho*i, sum rho*j, sum rho*k (global k), 0
-__global__ void __launch_bounds__(256) k_reduce(const double* __restrict__ rho, const double* __restrict__ phi,
-                                                double* __restrict__ partial, Geo G, int p0) {
-  __shared__ double sh[5][256];
-  const long long s_ = (long long)blockIdx.x*blockDim.x + threadIdx.x;
-  const int p = p0 + (int)blockIdx.y;
-  double v[5] = {0., 0., 0., 0., 0.};
-  const int y = (int)(s_ / G.pitch);
-  const int x = (int)(s_ - (long long)y*G.pitch);
-  if (s_ < G.plane && x < G.nx) {
-    const long long o = (long long)p*G.plane + s_;
-    const double r = rho[o];
-    int gz = G.z0 + (p - G.H);
-    v[0] = r; v[1] = phi[o]; v[2] = r*x; v[3] = r*y; v[4] = r*gz;
-  }
-  for (int k = 0; k < 5; ++k) sh[k][threadIdx.x] = v[k];
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) for (int k = 0; k < 5; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const long long b = (long long)blockIdx.y*gridDim.x + blockIdx.x;
-    for (int k = 0; k < 5; ++k) partial[b*5 + k] = sh[k][0];
-  }
-}
-
-// largest |rho + phi| per block over the slab's own planes (what `auto` keys its stability bound on after an upload,
-// bflbm_commit_upload); NaN propagates to the result so that a broken upload is not mistaken for a small one
-__global__ void __launch_bounds__(256) k_total_absmax(const double* __restrict__ rho, const double* __restrict__ phi,
-                                                      double* __restrict__ partial, Geo G, int p0) {
-  __shared__ double sh[256];
-  const long long s_ = (long long)blockIdx.x*blockDim.x + threadIdx.x;
-  const int p = p0 + (int)blockIdx.y;
-  double v = 0.;
-  const int y = (int)(s_ / G.pitch);
-  const int x = (int)(s_ - (long long)y*G.pitch);
-  if (s_ < G.plane && x < G.nx) {
-    const long long o = (long long)p*G.plane + s_;
-    v = fabs(rho[o] + phi[o]);
-  }
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) { const double a = sh[threadIdx.x], b = sh[threadIdx.x + w]; sh[threadIdx.x] = (a != a || b != b) ? (a + b) : (a > b ? a : b); }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[(long long)blockIdx.y*gridDim.x + blockIdx.x] = sh[0];
-}
-
 #endif  // BFLBM_KERNELS_H_

@@ -7,7 +7,7 @@
 //   the accumulators' observation   batch_observe_launch into the trace's [B][nsel][n] / observe_launch into the scratch buffer,
 //   k_modes_project                 stage 1: per tile of 2048 consecutive sites of a dense plane and replica, for every
 //                                   (variable, wavevector) the sum of a(x, y) T_nx[jx] T_ny[jy], threads striding the
-//                                   tile, the tree of block_sum, into [replica][z][tile][var][mode][2],
+//                                   tile, the tree of block_reduce, into [replica][z][tile][var][mode][2],
 //   k_modes_finish                  stage 2: per (variable, wavevector, replica) the tiles of a plane in tile order,
 //                                   times T_nz[jz], the planes in the sequence z = 0 .. nz-1, into the slot.
 // The planes are the last sum, so that a ring of z-slabs can follow the way bflbm_ring_trace_create did.  No atomics,
@@ -93,7 +93,7 @@ __device__ __forceinline__ double2 modes_phase(const double2* t, int j, int n) {
 // loaded once and kept for every wavevector.  Per wavevector the phase indices jx = (mx x) mod nx and jy = (my y) mod ny
 // are formed once for the thread's first site and advance by additions and a conditional subtraction; the xy phase of a
 // (site, wavevector) is formed once and applied to all variables.  The 256 partial sums of a wavevector are added in the
-// order of block_sum's tree, all variables at once.  NV, the number of variables, is a template parameter: the accumulators
+// order of block_reduce's tree, all variables at once.  NV, the number of variables, is a template parameter: the accumulators
 // and the site values are register arrays, and a run-time count costs a select per (site, variable, wavevector).
 template <int NV>
 __global__ void __launch_bounds__(256) k_modes_project(const double* __restrict__ fields, long long rep_stride, long long nsites,
@@ -144,7 +144,7 @@ __global__ void __launch_bounds__(256) k_modes_project(const double* __restrict_
       jy += M.dy; if (jy >= ny) jy -= ny;
       if (carry & (1u << i)) { jy += M.my; if (jy >= ny) jy -= ny; }
     }
-    // the tree of block_sum, v[t] += v[t + w] for w = 128, 64, ..., 1, with the same operands in the same order: the upper
+    // the tree of block_reduce, v[t] += v[t + w] for w = 128, 64, ..., 1, with the same operands in the same order: the upper
     // two waves hand their sums to the lower two through LDS, wave 1 hands its to wave 0, and wave 0 finishes by lane
     // shifts (lane t adds lane t + w; the lanes t >= w hold values no later level reads).  Two barriers per wavevector;
     // xa of the next wavevector is written after the second barrier of this one, xb after its first, so nothing is

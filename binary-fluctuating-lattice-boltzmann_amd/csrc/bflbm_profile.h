@@ -95,7 +95,7 @@ __device__ __forceinline__ void profile_two_turns(const double* __restrict__ p, 
   else { first = s < limit ? p[s] : 0.; second = s + stride < limit ? p[s + stride] : 0.; }
 }
 
-// axis z, grid.x = tiles: thread t adds the sites t, t + 256, ... of its tile, the tree of block_sum over the 256 sums
+// axis z, grid.x = tiles: thread t adds the sites t, t + 256, ... of its tile, the tree of block_reduce over the 256 sums
 // (levels 128 and 64 through LDS, the rest by lane shifts in wave 0).  vol[v]: variable v on this plane; out: [nq][tiles].
 template <int NV>
 __device__ __forceinline__ void profile_plane_z(const double* (&vol)[NV], int plane, const FstatPairs& P, int nq,

@@ -7,14 +7,14 @@
 // A sample is, on the owner's stream and without a host synchronisation,
 //   the dense transform of bflbm_spectra.h   the spectra hat[B][nspec][nk],
 //   k_spectrum_bin                  stage 1: per chunk of the sorted list, pair and replica the weighted sum of
-//                                   Re(a^ conj(b^)) / N, threads striding the chunk in index order, the tree of block_sum,
+//                                   Re(a^ conj(b^)) / N, threads striding the chunk in index order, the tree of block_reduce,
 //   k_spectrum_finish               stage 2: per bin, pair and replica the chunk sums in chunk order, into the slot.
 // The list holds the half-spectrum indices sorted by (bin, index), 4 B each; a chunk never crosses a bin, so a record
 // depends on the spectra and the chunk table alone.  No atomics, no LDS beyond the tree, no scratch.
 // A ring of z-slabs takes its samples by the slab transform with one sorted list per slab (spectrum_tables::build_slab
 // here, the rest in bflbm_spectrum_ring.h); the handle, the per-handle calls and the two binning kernels are the ones below.
 // The lifecycle and the sample store are those of bflbm_recorder.h, selection and transforms those of bflbm_spectra.h.
-// Included by bflbm.hip after bflbm_spectra.h (needs bflbm_ctx, bflbm_batch, block_sum).
+// Included by bflbm.hip after bflbm_spectra.h (needs bflbm_ctx, bflbm_batch, block_reduce).
 #ifndef BFLBM_SPECTRUM_H_
 #define BFLBM_SPECTRUM_H_
 
@@ -206,7 +206,7 @@ int spectrum_tables_upload(SpectrumTables& t, const char* call, int device, cons
 
 // Stage 1, grid (chunks, pairs, B): the thread adds weight * (scale a^) . b^ / N of the chunk's entries tid, tid + 256, ...
 // in that order (the product as k_sf_accumulate writes it; the weight, 1 or 2, is exact), the workgroup adds the 256
-// partial sums by the tree of block_sum into partial[replica][pair][chunk].
+// partial sums by the tree of block_reduce into partial[replica][pair][chunk].
 __global__ void __launch_bounds__(256) k_spectrum_bin(const double2* __restrict__ hat, const uint32_t* __restrict__ list,
                                                       const spectrum_tables::Chunk* __restrict__ chunks, double* __restrict__ partial,
                                                       long long nk, int nspec, int nx, SfPairs P, double inv_n) {
@@ -226,7 +226,7 @@ __global__ void __launch_bounds__(256) k_spectrum_bin(const double2* __restrict_
     const uint32_t mx = k % nxc;
     v[0] += (mx == 0 || 2 * (int)mx == nx) ? t : 2. * t;      // -k lies in the same bin and adds the same real part
   }
-  block_sum<1>(v, partial + (long long)blockIdx.z * gridDim.y * gridDim.x);
+  block_reduce<1>(v, partial + (long long)blockIdx.z * gridDim.y * gridDim.x);
 }
 
 // Stage 2, grid (ceil(nbins / 256), pairs, B): one thread per (bin, pair, replica) adds the bin's chunk sums in chunk

@@ -2,8 +2,8 @@
 // reduced into a device buffer every k steps on the owner's stream, read by the host once (include/bflbm.h, "Ensemble
 // traces").  The per-lattice observables (bflbm_droplet_moments, bflbm_com_sums) cost a density pass, a reduction, a copy
 // and a stream synchronisation per lattice and call; an ensemble sampled every step paid that B times per step.
-// The sums are added in the order of bflbm_droplet.h (block_sum over 256 consecutive sites of the padded plane, the
-// strided sum and tree of k_sum_partials per plane, the planes in sequence), so a record equals bflbm_droplet_moments
+// The sums are added in the order of bflbm_reduce.h (block_reduce over 256 consecutive sites of the padded plane, the
+// strided sum and tree of plane_reduce per plane, the planes in sequence), so a record equals bflbm_droplet_moments
 // of the same state bit for bit and does not depend on how the lattice is run.
 // The lifecycle and the sample store are those of bflbm_recorder.h; here are the kernels, their launch and the checks of
 // the kind's own arguments.
@@ -12,7 +12,7 @@
 // slab 0 writes its planes straight into the stage buffer [nz][plane blocks][kNTrace] and takes every other slab's block
 // to its planes' place there by the ring gather of bflbm_recorder.h; the same k_trace_finish then runs on slab 0.  The
 // summation order is a lone context's, so with the bit-exact schedules the record equals the lone trace's bit for bit.
-// Included by bflbm.hip after bflbm_droplet.h (needs bflbm_ctx, bflbm_batch, bflbm_ring, block_sum,
+// Included by bflbm.hip after bflbm_droplet.h (needs bflbm_ctx, bflbm_batch, bflbm_ring, bflbm_reduce.h,
 // batch_sync_table).  trace_moments_launch also serves the centre of mass of bflbm_shape.h and bflbm_radial.h.
 #ifndef BFLBM_TRACE_H_
 #define BFLBM_TRACE_H_
@@ -34,25 +34,22 @@ constexpr int kNTrace = BFLBM_TRACE_NREC;
 // order), its 12 terms, the workgroup's tree.  152 B read per site, nothing written per site; rho / phi of the owner are
 // not touched.  `partial` is the lattice's own [nz][plane blocks][kNTrace].
 __device__ __forceinline__ void trace_moments_body(const double* __restrict__ S, double* __restrict__ partial, const Geo& G, double threshold) {
-  const long long s_ = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int p = G.H + (int)blockIdx.y;                 // the own planes; a single slab: storage plane == global z (H = 0, z0 = 0)
+  const PlaneSite st = plane_site(G, G.H);              // the own planes; a single slab: storage plane == global z (H = 0, z0 = 0)
+  const int x = st.x, y = st.y, z = st.z;
   double v[kNTrace];
   for (int k = 0; k < kNTrace; ++k) v[k] = 0.;
-  const int y = (int)(s_ / G.pitch);
-  const int x = (int)(s_ - (long long)y * G.pitch);
-  if (s_ < G.plane && x < G.nx) {
-    SiteOff I; site_offsets(G, x, y, p, I);
+  if (st.in) {
+    SiteOff I; site_offsets(G, x, y, st.p, I);
     const double r = pull_density(S, G, I);
     v[10] = r;
     if (threshold == -INFINITY || r > threshold) {     // -inf: every cell, whatever its density is
-      const int z = G.z0 + (int)blockIdx.y;
       const double m[10] = { 1., (double)x, (double)y, (double)z, (double)x * x, (double)x * y, (double)x * z,
                              (double)y * y, (double)y * z, (double)z * z };
       for (int k = 0; k < 10; ++k) v[k] = r * m[k];
       v[11] = 1.;
     }
   }
-  block_sum<kNTrace>(v, partial);
+  block_reduce<kNTrace>(v, partial);
 }
 
 // grid (plane blocks, own planes, 1): a lone context, or a slab of a ring, hands over its resident buffer
@@ -67,26 +64,15 @@ __global__ void __launch_bounds__(256) k_trace_moments_batch(const BatchRec* __r
   trace_moments_body(R->S[cur], partial + (long long)blockIdx.z * per_replica, G, threshold);
 }
 
-// Stages 2 and 3, one workgroup per replica: per plane the sum of k_sum_partials (every thread a 256-strided subsequence
-// of the plane's block sums, then the tree), the planes added in sequence as reduce_blocks does on the host; the result
+// Stages 2 and 3, one workgroup per replica: per plane the sum of plane_reduce (every thread a 256-strided subsequence
+// of the plane's block sums, then the tree), the planes added in sequence as slab_reduce does on the host; the result
 // goes straight into the sample's slot.  out = the slot of replica 0.
 __global__ void __launch_bounds__(256) k_trace_finish(const double* __restrict__ partial, double* __restrict__ out, int nbx, int nplanes) {
-  __shared__ double sh[kNTrace][256];
   const double* __restrict__ mine = partial + (long long)blockIdx.x * nplanes * nbx * kNTrace;
   double acc[kNTrace];
   for (int k = 0; k < kNTrace; ++k) acc[k] = 0.;
   for (int p = 0; p < nplanes; ++p) {
-    double v[kNTrace];
-    for (int k = 0; k < kNTrace; ++k) v[k] = 0.;
-    const long long base = (long long)p * nbx;
-    for (int b = threadIdx.x; b < nbx; b += 256) for (int k = 0; k < kNTrace; ++k) v[k] += mine[(base + b) * kNTrace + k];
-    for (int k = 0; k < kNTrace; ++k) sh[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      if ((int)threadIdx.x < w) for (int k = 0; k < kNTrace; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + w];
-      __syncthreads();
-    }
-    // thread 0 reads only its own column here, and nobody reads a column again before the next plane's barrier
+    const Column* sh = plane_reduce<kNTrace, SumRule>(mine + (long long)p * nbx * kNTrace, nbx);
     if (threadIdx.x == 0) for (int k = 0; k < kNTrace; ++k) acc[k] += sh[k][0];
   }
   if (threadIdx.x == 0) for (int k = 0; k < kNTrace; ++k) out[(long long)blockIdx.x * kNTrace + k] = acc[k];

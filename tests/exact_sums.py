@@ -30,7 +30,7 @@ def depth_bound(kind, nx, ny, nz, nslabs=1):
     """d u / (1 - d u): the relative error, against sum |term|, of a sum whose every term passes through at most d
     roundings (Higham, Accuracy and Stability of Numerical Algorithms, section 4.2, for any fixed order).
     "two_stage" (droplet moments, traces; the same for a ring, whose planes are added in the lone order):
-        d = 1 (the product rho * monomial) + 8 (tree of block_sum) + ceil(nbx / 256) (the strided pass of stage 2)
+        d = 1 (the product rho * monomial) + 8 (tree of block_reduce) + ceil(nbx / 256) (the strided pass of stage 2)
             + 8 (its tree) + nz (the planes in sequence)
     "host_blocks" (mass, com_sums: reduce5 adds the nbx * nz block sums of a slab in sequence on the host; a ring adds
     its slabs' sums after that):
@@ -133,7 +133,7 @@ def ratio_to_bound(got, exact, abs_sum, bound):
 
 
 def _tree(a):
-    """The shared-memory tree of block_sum over the last axis (256 wide): a[t] += a[t + w], w = 128 .. 1."""
+    """The shared-memory tree of block_reduce over the last axis (256 wide): a[t] += a[t + w], w = 128 .. 1."""
     a = a.copy()
     w = BLOCK // 2
     while w > 0:
@@ -160,7 +160,7 @@ def device_terms(rho_zyx, weighted=False, threshold=None):
 
 
 def emulate_two_stage(terms_zyx, first_pass_only=False):
-    """The sum of terms[nz, ny, nx] in the order of k_moments / trace_moments_body + k_sum_partials / k_trace_finish + the
+    """The sum of terms[nz, ny, nx] in the order of k_moments / trace_moments_body + k_plane_partials / k_trace_finish + the
     plane loop: rows at the padded pitch, blocks of 256 consecutive sites of the padded plane, the tree; every thread of
     stage 2 a 256-strided subsequence of the plane's block sums, the tree; the planes in sequence.
     first_pass_only: stage 2 cut to b < min(nbx, 256), the fault the wide-plane tests exist to catch."""

@@ -49,7 +49,7 @@ def _indices(m, n):
 
 
 def _tree(v):
-    """The tree of block_sum over the last axis (256 wide): v[t] += v[t + w], w = 128 .. 1."""
+    """The tree of block_reduce over the last axis (256 wide): v[t] += v[t + w], w = 128 .. 1."""
     v = v.copy()
     w = BLOCK // 2
     while w:

@@ -3,14 +3,12 @@ device is touched) and the compiled batch kernels (hipcc cross-compiles gfx950, 
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
+from device_listing import device_asm, kernel_of   # noqa: F401  (device_asm: the listing fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "binary-fluctuating-lattice-boltzmann_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 BATCH_SYMBOLS = ["bflbm_batch_create", "bflbm_batch_destroy", "bflbm_batch_size", "bflbm_batch_replica",
                  "bflbm_batch_set_schedule", "bflbm_batch_resolved_schedule", "bflbm_batch_step", "bflbm_batch_sync",
@@ -58,16 +56,6 @@ def test_batch_python_arguments(pkg):
         pkg.BatchLBM(8, params=[{}, {}], replicas=3)
 
 
-@pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("asm") / "bflbm.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-w",
-                    "--cuda-device-only", "-S", "-o", str(out), "bflbm.hip"], cwd=CSRC, check=True, timeout=600)
-    return out.read_text().split("\n")
-
-
 BATCH_KERNELS = [
     r"_Z15k_density_batchPK8BatchRec",
     r"_Z15k_collide_batchILb0EE",
@@ -82,10 +70,7 @@ BATCH_KERNELS = [
 
 @pytest.mark.parametrize("symbol", BATCH_KERNELS)
 def test_batch_kernel_compiled_without_scratch(device_asm, symbol):
-    starts = [i for i, l in enumerate(device_asm) if re.match(r"^%s\w*:" % symbol, l)]
-    assert len(starts) == 1, f"batch kernel {symbol} not in the gfx950 assembly"
-    end = [i for i in range(starts[0], len(device_asm)) if device_asm[i].startswith(".Lfunc_end")][0]
-    meta = "\n".join(device_asm[end:end + 120])
+    body, meta = kernel_of(device_asm, r"^%s\w*:" % symbol, "batch kernel")
     assert re.search(r"; ScratchSize: 0\b", meta), f"{symbol} spills to scratch"
-    body = "\n".join(device_asm[starts[0]:end])
+    body = "\n".join(body)
     assert "s_load_dword" in body                                        # the per-replica record: scalar loads

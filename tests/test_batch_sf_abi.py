@@ -3,14 +3,14 @@ any device is touched, and the compiled kernels (hipcc cross-compiles gfx950, no
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+from device_listing import device_asm, kernel_of, mangled, scratch_size   # noqa: F401  (device_asm: the listing fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "binary-fluctuating-lattice-boltzmann_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 SYMBOLS = ["bflbm_batch_sf_create", "bflbm_batch_sf_destroy", "bflbm_batch_sf_reset", "bflbm_batch_sf_accumulate",
            "bflbm_batch_sf_nsamples", "bflbm_batch_sf_get", "bflbm_batch_get_hydrovs", "bflbm_batch_get_hydrovsbar"]
@@ -84,26 +84,10 @@ def test_batch_sf_refusals_touch_no_device(pkg):
     assert lib.bflbm_batch_sf_destroy(None) == 0         # like every destroy of the ABI: nothing to do
 
 
-@pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("asm") / "bflbm.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-w",
-                    "--cuda-device-only", "-S", "-o", str(out), "bflbm.hip"], cwd=CSRC, check=True, timeout=600)
-    return out.read_text().split("\n")
-
-
 def _scratch_size(asm, kernel, template_arg=None):
     """ScratchSize of the one definition of `kernel` (Itanium mangling: <length><name>, then ILi<N>E for <N>)."""
     tail = r"ILi%dEE" % template_arg if template_arg is not None else r"E?"
-    label = re.compile(r"^_Z\w*?%d%s%s\w*:" % (len(kernel), kernel, tail))
-    starts = [i for i, l in enumerate(asm) if label.match(l)]
-    assert len(starts) == 1, f"{kernel}: {len(starts)} definitions in the gfx950 assembly"
-    end = [i for i in range(starts[0], len(asm)) if asm[i].startswith(".Lfunc_end")][0]
-    m = re.search(r"; ScratchSize: (\d+)\b", "\n".join(asm[end:end + 120]))
-    assert m, f"{kernel}: no ScratchSize line"
-    return int(m.group(1))
+    return scratch_size(kernel_of(asm, mangled(kernel, tail))[1])
 
 
 @pytest.mark.parametrize("kernel,arg", [("k_sf_accumulate", None), ("k_sf_expand", None), ("k_observe_batch", 0)])

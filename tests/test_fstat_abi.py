@@ -4,15 +4,13 @@ any device is touched) and the compiled kernels' metadata (hipcc cross-compiles 
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from device_listing import device_asm, kernels   # noqa: F401  (device_asm: the listing fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "binary-fluctuating-lattice-boltzmann_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 FSTAT_SYMBOLS = ["bflbm_fstat_create", "bflbm_batch_fstat_create", "bflbm_ring_fstat_create", "bflbm_fstat_destroy",
                  "bflbm_fstat_sample", "bflbm_fstat_reset", "bflbm_fstat_count", "bflbm_fstat_get"]
@@ -136,31 +134,11 @@ def test_variable_names_of_the_sources(pkg):
 
 
 # ---- the compiled kernels ----------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("asm") / "bflbm.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-w",
-                    "--cuda-device-only", "-S", "-o", str(out), "bflbm.hip"], cwd=CSRC, check=True, timeout=600)
-    return out.read_text().split("\n")
-
-
-def _kernel_metadata(device_asm, label):
-    """The lines the compiler prints after each kernel whose label matches; never the kernel's instructions."""
-    starts = [i for i, l in enumerate(device_asm) if label.match(l)]
-    out = []
-    for s in starts:
-        end = [i for i in range(s, len(device_asm)) if device_asm[i].startswith(".Lfunc_end")][0]
-        out.append((label.match(device_asm[s]), "\n".join(device_asm[end:end + 120])))
-    return out
-
-
 def test_fstat_kernel_metadata(device_asm):
     """k_fstat_accumulate<NV>, NV = 1 .. 8, and k_fstat_derive: no scratch and no LDS, as include/bflbm.h states."""
-    found = _kernel_metadata(device_asm, re.compile(r"^_Z\w*?18k_fstat_accumulateILi(\d)EE\w*:"))    # Itanium mangling: <length><name>
+    found = kernels(device_asm, r"^_Z\w*?18k_fstat_accumulateILi(\d)EE\w*:")    # Itanium mangling: <length><name>
     assert sorted(int(m.group(1)) for m, _ in found) == list(range(1, 9))
-    found += _kernel_metadata(device_asm, re.compile(r"^_Z\w*?14k_fstat_derive(E)\w*:"))
+    found += kernels(device_asm, r"^_Z\w*?14k_fstat_derive(E)\w*:")
     assert len(found) == 9
     for m, meta in found:
         assert re.search(r"; ScratchSize: 0\b", meta), f"{m.group(0)} spills to scratch"

@@ -6,7 +6,7 @@ with numpy sums of the downloaded density under the a-priori bound of a re-order
 owner computes.  The shapes are the smallest at which the kernels take another path: a plane smaller than one block, a
 padded pitch with several blocks per plane, unequal extents with a ragged last block, nx no multiple of the padding, and
 a lattice the hand-over schedule takes.  One path these shapes do not reach: with more than 256 blocks per plane
-(pitch * ny > 65536) the strided loop of k_trace_finish and k_sum_partials runs a second time.  Those widths (256, 257,
+(pitch * ny > 65536) the strided loop of k_trace_finish and k_plane_partials runs a second time.  Those widths (256, 257,
 270 and 556 blocks per plane; lone, batch and ring traces) are in tests/test_gpu_wide_planes.py, against exact sums of a
 field in which every block carries weight."""
 import ctypes

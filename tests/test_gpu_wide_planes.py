@@ -1,7 +1,7 @@
 """GPU: the device-side observables on planes of more than 256 blocks, against exact sums.
 
-Every reduction of an observable has two stages: one partial per 256-site block of the padded plane (block_sum, k_reduce),
-then k_sum_partials / k_minmax_partials / k_trace_finish, whose 256 threads each walk a 256-strided subsequence of a
+Every reduction of an observable has two stages: one partial per 256-site block of the padded plane (block_reduce, k_reduce),
+then k_plane_partials / k_trace_finish, whose 256 threads each walk a 256-strided subsequence of a
 plane's partials (for mass / com_sums the host adds the partials in sequence).  That strided loop runs a second time only
 where pitch * ny > 65536; the shapes here are the smallest on either side of it (exact_sums.WIDE_SHAPES):
 
@@ -191,7 +191,7 @@ def test_a_ring_needs_four_planes_per_slab(pkg):
 def test_ring_observables_equal_the_lone_lattice(pkg, ob, shape, nslabs, schedule):
     """The ring's stage buffer takes slab k's blocks at plane z0 of the slab (peer copies of nzl * nbx * 12 doubles); with
     the exact schedules its trace equals the lone trace bit for bit, and so do its droplet moments, whose planes
-    reduce_blocks adds in the lone order whatever the decomposition."""
+    slab_reduce adds in the lone order whatever the decomposition."""
     f0, g0 = _populations(ob, *_fields(shape))
     ring = pkg.RingLBM(*shape, nslabs=nslabs, devices=(0,), schedule=schedule)
     assert [s.nzl for s in ring.slabs] == {2: [4, 4], 3: [4, 4, 5]}[nslabs]
@@ -280,3 +280,56 @@ def test_fits_on_a_wide_plane(pkg, ob):
     print(f"{BLOB} fit_droplet_flow: (W, R) = {(W, R)!r} against the twin {(Wt, Rt)!r}")
     assert retries == 0 and np.all(undt <= 1.0) and und <= 1.0
     np.testing.assert_allclose([W, R], [Wt, Rt], rtol=1e-9)
+
+
+# ---- 8. the total-density bound of `auto`: the NaN-propagating maximum, the host over all blocks ----------------------------
+ABSMAX_SHAPES = [(4112, 16, 3), (1000, 141, 2)]     # 257 blocks per plane; 556 blocks, the last one ragged at 48 sites
+
+
+def _peaked(ob, shape, nan=False):
+    """The module's uniform upload with rho of the last site (nx-1, ny-1, nz-1) scaled by 5, so that rho + phi >= 3 there
+    and < 3 everywhere else: the maximum lives in the last block of the last plane.  nan: that site's f0[0] is NaN."""
+    rho, phi = _fields(shape)
+    rho = rho.copy()
+    rho[-1, -1, -1] *= 5.0
+    f0, g0 = _populations(ob, rho, phi)
+    if nan:
+        f0[0, -1, -1, -1] = np.nan
+    return f0, g0
+
+
+def _assert_peak(total_max, rho, phi):
+    total = np.abs(rho + phi)
+    peak = np.unravel_index(np.argmax(total), total.shape)
+    print(f"{rho.shape[::-1]} state_total_max {total_max!r} against the downloaded densities {total.max()!r} at (z, y, x) = {peak}")
+    assert peak == tuple(n - 1 for n in total.shape) and total.max() >= 3.0 > np.partition(total.ravel(), -2)[-2]
+    assert total_max == total.max(), (total_max, total.max())           # bit for bit: a maximum rounds nothing
+
+
+@pytest.mark.parametrize("shape", ABSMAX_SHAPES)
+def test_state_total_max_on_a_wide_plane(pkg, ob, shape):
+    assert xs.blocks_per_plane(*shape[:2]) > 256
+    with pkg.BinaryLBM(*shape) as lbm:
+        lbm.LBM_init(*_peaked(ob, shape))
+        m = lbm.state_total_max
+        rho, phi = lbm.LBM_hydrovars(ncomp=2)
+    _assert_peak(m, rho, phi)
+
+
+def test_state_total_max_of_a_ring_is_the_global_one(pkg, ob):
+    """The large site lies in slab 1; every slab resolves `auto` on the whole lattice's maximum."""
+    ring = pkg.RingLBM(*RING8, nslabs=2, devices=(0,))
+    ring.LBM_init(*_peaked(ob, RING8))
+    ms = [s.state_total_max for s in ring.slabs]
+    rho, phi = ring.LBM_hydrovars(ncomp=2)
+    ring.close()
+    assert ms[0] == ms[1]
+    _assert_peak(ms[0], rho, phi)
+
+
+@pytest.mark.parametrize("shape", ABSMAX_SHAPES)
+def test_a_nan_in_the_last_block_keeps_auto_on_an_exact_schedule(pkg, ob, shape):
+    with pkg.BinaryLBM(*shape) as lbm:
+        lbm.LBM_init(*_peaked(ob, shape, nan=True))
+        assert lbm.state_total_max == np.inf
+        assert lbm.resolved_schedule() in ("two_pass", "fused")

@@ -12,13 +12,14 @@ import subprocess
 import numpy as np
 import pytest
 
+from device_listing import device_asm, kernels   # noqa: F401  (device_asm: the listing fixture)
+
 import hist_counts as hc
 import profile_sums as ps
-from test_profile_abi import _declared_arguments, _kernel_metadata
+from test_profile_abi import _declared_arguments
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "binary-fluctuating-lattice-boltzmann_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 HIST_SYMBOLS = ["bflbm_hist_create", "bflbm_batch_hist_create", "bflbm_ring_hist_create", "bflbm_hist_destroy", "bflbm_hist_sample",
                 "bflbm_hist_reset", "bflbm_hist_count", "bflbm_hist_geometry", "bflbm_hist_read"]
@@ -181,25 +182,15 @@ CHECKS = 46  # the checks hist_main.cpp makes: a check that silently stops runni
 
 
 # ---- the compiled kernels ----------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("asm") / "bflbm.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-w",
-                    "--cuda-device-only", "-S", "-o", str(out), "bflbm.hip"], cwd=CSRC, check=True, timeout=600)
-    return out.read_text().split("\n")
-
-
 def test_hist_kernel_metadata(device_asm):
     """k_hist_count<NV, CCAP>, NV = 1 .. 8, CCAP = 4096 and 16384, and k_hist_finish: no scratch; the counting kernel's LDS
     is the 4 CCAP bytes include/bflbm.h states (16384 bytes for C <= 4096, else 65536), the finishing kernel uses none."""
-    found = _kernel_metadata(device_asm, re.compile(r"^_Z\w*?12k_hist_countILi(\d)ELi(\d+)EE\w*:"))      # Itanium mangling: <length><name>
+    found = kernels(device_asm, r"^_Z\w*?12k_hist_countILi(\d)ELi(\d+)EE\w*:")      # Itanium mangling: <length><name>
     assert sorted((int(m.group(1)), int(m.group(2))) for m, _ in found) == [(nv, c) for nv in range(1, 9) for c in (4096, 16384)]
     for m, meta in found:
         assert int(m.group(2)) == hc.lds_counters(int(m.group(2)))
         assert re.search(r"; LDSByteSize: %d\b" % (4 * int(m.group(2))), meta), f"{m.group(0)}: LDS"
-    finish = _kernel_metadata(device_asm, re.compile(r"^_Z\w*?13k_hist_finish(E)\w*:"))
+    finish = kernels(device_asm, r"^_Z\w*?13k_hist_finish(E)\w*:")
     assert len(finish) == 1 and re.search(r"; LDSByteSize: 0\b", finish[0][1])
     for m, meta in found + finish:
         assert re.search(r"; ScratchSize: 0\b", meta), f"{m.group(0)} spills to scratch"

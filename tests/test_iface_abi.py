@@ -5,15 +5,13 @@ import ctypes
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from device_listing import device_asm, kernel_of, mangled   # noqa: F401  (device_asm: the listing fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "binary-fluctuating-lattice-boltzmann_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 IFACE_SYMBOLS = ["bflbm_iface_create", "bflbm_batch_iface_create", "bflbm_iface_destroy", "bflbm_iface_sample",
                  "bflbm_iface_reset", "bflbm_iface_count", "bflbm_iface_geometry", "bflbm_iface_read"]
@@ -174,21 +172,7 @@ def test_capillary_spectrum_against_a_direct_sum(pkg):
 
 
 # ---- the compiled kernels ----------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("asm") / "bflbm.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-w",
-                    "--cuda-device-only", "-S", "-o", str(out), "bflbm.hip"], cwd=CSRC, check=True, timeout=600)
-    return out.read_text().split("\n")
-
-
 @pytest.mark.parametrize("kernel", ["k_iface_scan", "k_iface_scan_batch", "k_iface_finish"])
 def test_iface_kernel_compiled_without_scratch(device_asm, kernel):
-    label = re.compile(r"^_Z\w*?%d%sE\w*:" % (len(kernel), kernel))           # Itanium mangling: <length><name>
-    starts = [i for i, l in enumerate(device_asm) if label.match(l)]
-    assert len(starts) == 1, f"interface kernel {kernel}: {len(starts)} definitions in the gfx950 assembly"
-    end = [i for i in range(starts[0], len(device_asm)) if device_asm[i].startswith(".Lfunc_end")][0]
-    meta = "\n".join(device_asm[end:end + 120])
+    _, meta = kernel_of(device_asm, mangled(kernel), "interface kernel")
     assert re.search(r"; ScratchSize: 0\b", meta), f"{kernel} spills to scratch"

@@ -5,17 +5,15 @@ reference inside its bound, and the compiled kernels' metadata (hipcc cross-comp
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from device_listing import device_asm, kernels   # noqa: F401  (device_asm: the listing fixture)
+
 import mode_sums as ms
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "binary-fluctuating-lattice-boltzmann_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 MODES_SYMBOLS = ["bflbm_modes_create", "bflbm_batch_modes_create", "bflbm_modes_destroy", "bflbm_modes_sample",
                  "bflbm_modes_reset", "bflbm_modes_count", "bflbm_modes_geometry", "bflbm_modes_phases", "bflbm_modes_read"]
@@ -155,36 +153,16 @@ def test_emulation_follows_the_tiles(pkg):
 
 
 # ---- the compiled kernels ----------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("asm") / "bflbm.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-w",
-                    "--cuda-device-only", "-S", "-o", str(out), "bflbm.hip"], cwd=CSRC, check=True, timeout=600)
-    return out.read_text().split("\n")
-
-
-def _kernel_metadata(device_asm, label):
-    """The lines the compiler prints after each kernel whose label matches; never the kernel's instructions."""
-    starts = [i for i, l in enumerate(device_asm) if label.match(l)]
-    out = []
-    for s in starts:
-        end = [i for i in range(s, len(device_asm)) if device_asm[i].startswith(".Lfunc_end")][0]
-        out.append((label.match(device_asm[s]), "\n".join(device_asm[end:end + 120])))
-    return out
-
-
 def test_modes_kernel_metadata(device_asm):
     """k_modes_project<NV>, NV = 1 .. 8, and k_modes_finish: no scratch, and the LDS size include/bflbm.h states."""
     header = open(os.path.join(ROOT, "include", "bflbm.h")).read()
     assert "36864 + 3072 nvars" in header and "61440" in header and "4096" in header
-    found = _kernel_metadata(device_asm, re.compile(r"^_Z\w*?15k_modes_projectILi(\d)EE\w*:"))     # Itanium mangling: <length><name>
+    found = kernels(device_asm, r"^_Z\w*?15k_modes_projectILi(\d)EE\w*:")     # Itanium mangling: <length><name>
     assert sorted(int(m.group(1)) for m, _ in found) == list(range(1, 9))
     for m, meta in found:
         nv = int(m.group(1))
         assert re.search(r"; ScratchSize: 0\b", meta), f"k_modes_project<{nv}> spills to scratch"
         assert re.search(r"; LDSByteSize: %d\b" % (36864 + 3072 * nv), meta), f"k_modes_project<{nv}>: not the LDS size include/bflbm.h states"
-    finish = _kernel_metadata(device_asm, re.compile(r"^_Z\w*?14k_modes_finishE\w*:"))
+    finish = kernels(device_asm, r"^_Z\w*?14k_modes_finishE\w*:")
     assert len(finish) == 1
     assert re.search(r"; ScratchSize: 0\b", finish[0][1]) and re.search(r"; LDSByteSize: 4096\b", finish[0][1])

@@ -7,17 +7,15 @@ import ctypes
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from device_listing import device_asm, kernels   # noqa: F401  (device_asm: the listing fixture)
+
 import profile_sums as ps
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "binary-fluctuating-lattice-boltzmann_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 PROFILE_SYMBOLS = ["bflbm_profile_create", "bflbm_batch_profile_create", "bflbm_ring_profile_create", "bflbm_profile_destroy",
                    "bflbm_profile_sample", "bflbm_profile_reset", "bflbm_profile_count", "bflbm_profile_geometry",
@@ -205,34 +203,14 @@ def test_profile_null_pointers_are_refused(pkg):
 
 
 # ---- the compiled kernels ----------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("asm") / "bflbm.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-w",
-                    "--cuda-device-only", "-S", "-o", str(out), "bflbm.hip"], cwd=CSRC, check=True, timeout=600)
-    return out.read_text().split("\n")
-
-
-def _kernel_metadata(device_asm, label):
-    """The lines the compiler prints after each kernel whose label matches; never the kernel's instructions."""
-    starts = [i for i, l in enumerate(device_asm) if label.match(l)]
-    out = []
-    for s in starts:
-        end = [i for i in range(s, len(device_asm)) if device_asm[i].startswith(".Lfunc_end")][0]
-        out.append((label.match(device_asm[s]), "\n".join(device_asm[end:end + 120])))
-    return out
-
-
 def test_profile_kernel_metadata(device_asm):
     """k_profile_planes<NV>, NV = 1 .. 8, and k_profile_finish: no scratch; the plane kernel's LDS is the 1536 (NV + 16)
     bytes include/bflbm.h states, the finishing kernel uses none."""
-    found = _kernel_metadata(device_asm, re.compile(r"^_Z\w*?16k_profile_planesILi(\d)EE\w*:"))      # Itanium mangling: <length><name>
+    found = kernels(device_asm, r"^_Z\w*?16k_profile_planesILi(\d)EE\w*:")      # Itanium mangling: <length><name>
     assert sorted(int(m.group(1)) for m, _ in found) == list(range(1, 9))
     for m, meta in found:
         assert re.search(r"; LDSByteSize: %d\b" % (1536 * (int(m.group(1)) + 16)), meta), f"{m.group(0)}: LDS"
-    finish = _kernel_metadata(device_asm, re.compile(r"^_Z\w*?16k_profile_finish(E)\w*:"))
+    finish = kernels(device_asm, r"^_Z\w*?16k_profile_finish(E)\w*:")
     assert len(finish) == 1 and re.search(r"; LDSByteSize: 0\b", finish[0][1])
     for m, meta in found + finish:
         assert re.search(r"; ScratchSize: 0\b", meta), f"{m.group(0)} spills to scratch"

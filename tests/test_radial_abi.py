@@ -7,18 +7,16 @@ import ctypes
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
+
+from device_listing import device_asm, kernels   # noqa: F401  (device_asm: the listing fixture)
 
 import radial_sums as rs
 from test_gpu_notebook_surface_tension import CELL13, CELL18, GAMMA_15, GAMMA_17, R_15, R_17
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "binary-fluctuating-lattice-boltzmann_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 GOLDEN = os.path.join(ROOT, "tests", "golden", "radial_droplets.npz")
 
 RADIAL_SYMBOLS = ["bflbm_radial_create", "bflbm_batch_radial_create", "bflbm_radial_destroy", "bflbm_radial_sample",
@@ -324,37 +322,17 @@ def test_radial_null_pointers_are_refused(pkg):
 
 
 # ---- the compiled kernels ----------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("asm") / "bflbm.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-w",
-                    "--cuda-device-only", "-S", "-o", str(out), "bflbm.hip"], cwd=CSRC, check=True, timeout=600)
-    return out.read_text().split("\n")
-
-
-def _kernel_metadata(device_asm, label):
-    """The lines the compiler prints after each kernel whose label matches; never the kernel's instructions."""
-    starts = [i for i, l in enumerate(device_asm) if label.match(l)]
-    out = []
-    for s in starts:
-        end = [i for i in range(s, len(device_asm)) if device_asm[i].startswith(".Lfunc_end")][0]
-        out.append((label.match(device_asm[s]), "\n".join(device_asm[end:end + 120])))
-    return out
-
-
 def test_radial_kernel_metadata(device_asm):
     """k_radial_shells<NV>, NV = 1 .. 8, and k_radial_finish: no scratch; the shell kernel's LDS is the 2048 (NV + 4) + 1312
     bytes include/bflbm.h states (six workgroups of the largest fit the 160 KiB of a compute unit), the finishing kernel
     uses none."""
-    found = _kernel_metadata(device_asm, re.compile(r"^_Z\w*?15k_radial_shellsILi(\d)EE\w*:"))        # Itanium mangling: <length><name>
+    found = kernels(device_asm, r"^_Z\w*?15k_radial_shellsILi(\d)EE\w*:")        # Itanium mangling: <length><name>
     assert sorted(int(m.group(1)) for m, _ in found) == list(range(1, 9))
     for m, meta in found:
         lds = 2048 * (int(m.group(1)) + 4) + 1312
         assert re.search(r"; LDSByteSize: %d\b" % lds, meta), f"{m.group(0)}: LDS"
         assert 6 * lds <= 160 * 1024
-    finish = _kernel_metadata(device_asm, re.compile(r"^_Z\w*?15k_radial_finish(E)\w*:"))
+    finish = kernels(device_asm, r"^_Z\w*?15k_radial_finish(E)\w*:")
     assert len(finish) == 1 and re.search(r"; LDSByteSize: 0\b", finish[0][1])
     for m, meta in found + finish:
         assert re.search(r"; ScratchSize: 0\b", meta), f"{m.group(0)} spills to scratch"

@@ -10,9 +10,10 @@ import subprocess
 
 import pytest
 
+from device_listing import device_asm, kernel_of, mangled   # noqa: F401  (device_asm: the listing fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "binary-fluctuating-lattice-boltzmann_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 RING_SYMBOLS = ["bflbm_ring_trace_create", "bflbm_ring_spectrum_create"]
 
@@ -103,25 +104,10 @@ def test_slab_tables_partition_the_half_spectrum(tables_program, n, nslabs):
 
 
 # ---- the compiled kernels ----------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("asm") / "bflbm.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-w",
-                    "--cuda-device-only", "-S", "-o", str(out), "bflbm.hip"], cwd=CSRC, check=True, timeout=600)
-    return out.read_text().split("\n")
-
-
 @pytest.mark.parametrize("kernel", ["k_spectrum_collect", "k_spectrum_combine"])
 def test_ring_spectrum_kernel_compiled_once_without_scratch(device_asm, kernel):
-    label = re.compile(r"^_Z\w*?%d%sE\w*:" % (len(kernel), kernel))           # Itanium mangling: <length><name>
-    starts = [i for i, l in enumerate(device_asm) if label.match(l)]
-    assert len(starts) == 1, f"{kernel}: {len(starts)} definitions in the gfx950 assembly"
-    end = [i for i in range(starts[0], len(device_asm)) if device_asm[i].startswith(".Lfunc_end")][0]
-    body = device_asm[starts[0]:end]
+    body, meta = kernel_of(device_asm, mangled(kernel))
     assert not [l for l in body if "atomic" in l], f"{kernel} uses atomics"
-    meta = "\n".join(device_asm[end:end + 120])
     assert re.search(r"; ScratchSize: 0\b", meta), f"{kernel} spills to scratch"
     assert re.search(r"; LDSByteSize: 0\b", meta), f"{kernel} uses LDS"
     if kernel == "k_spectrum_collect":                       # 16 bytes per element, both ways

@@ -6,15 +6,13 @@ import ctypes
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from device_listing import device_asm, kernel_of, mangled   # noqa: F401  (device_asm: the listing fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "binary-fluctuating-lattice-boltzmann_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 SHAPE_SYMBOLS = ["bflbm_shape_create", "bflbm_batch_shape_create", "bflbm_shape_destroy", "bflbm_shape_sample",
                  "bflbm_shape_reset", "bflbm_shape_count", "bflbm_shape_geometry", "bflbm_shape_read"]
@@ -259,21 +257,7 @@ def test_planted_modes_are_recovered(pkg):
 
 
 # ---- the compiled kernels ----------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("asm") / "bflbm.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-w",
-                    "--cuda-device-only", "-S", "-o", str(out), "bflbm.hip"], cwd=CSRC, check=True, timeout=600)
-    return out.read_text().split("\n")
-
-
 @pytest.mark.parametrize("kernel", ["k_shape_density", "k_shape_density_batch", "k_shape_rays", "k_shape_finish"])
 def test_shape_kernel_compiled_without_scratch(device_asm, kernel):
-    label = re.compile(r"^_Z\w*?%d%sE\w*:" % (len(kernel), kernel))           # Itanium mangling: <length><name>
-    starts = [i for i, l in enumerate(device_asm) if label.match(l)]
-    assert len(starts) == 1, f"shape kernel {kernel}: {len(starts)} definitions in the gfx950 assembly"
-    end = [i for i in range(starts[0], len(device_asm)) if device_asm[i].startswith(".Lfunc_end")][0]
-    meta = "\n".join(device_asm[end:end + 120])
+    _, meta = kernel_of(device_asm, mangled(kernel), "shape kernel")
     assert re.search(r"; ScratchSize: 0\b", meta), f"{kernel} spills to scratch"

@@ -6,15 +6,13 @@ import ctypes
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from device_listing import device_asm, kernel_of, mangled   # noqa: F401  (device_asm: the listing fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "binary-fluctuating-lattice-boltzmann_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 SPECTRUM_SYMBOLS = ["bflbm_spectrum_create", "bflbm_batch_spectrum_create", "bflbm_spectrum_destroy", "bflbm_spectrum_sample",
                     "bflbm_spectrum_reset", "bflbm_spectrum_count", "bflbm_spectrum_geometry", "bflbm_spectrum_bins",
@@ -174,24 +172,9 @@ def test_domain_length_of_a_single_mode(pkg, n):
 
 
 # ---- the compiled kernels ----------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("asm") / "bflbm.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-w",
-                    "--cuda-device-only", "-S", "-o", str(out), "bflbm.hip"], cwd=CSRC, check=True, timeout=600)
-    return out.read_text().split("\n")
-
-
 @pytest.mark.parametrize("kernel,lds", [("k_spectrum_bin", 2048), ("k_spectrum_finish", 0)])
 def test_spectrum_kernel_compiled_without_scratch_or_atomics(device_asm, kernel, lds):
-    label = re.compile(r"^_Z\w*?%d%sE\w*:" % (len(kernel), kernel))           # Itanium mangling: <length><name>
-    starts = [i for i, l in enumerate(device_asm) if label.match(l)]
-    assert len(starts) == 1, f"spectrum kernel {kernel}: {len(starts)} definitions in the gfx950 assembly"
-    end = [i for i in range(starts[0], len(device_asm)) if device_asm[i].startswith(".Lfunc_end")][0]
-    body = device_asm[starts[0]:end]
+    body, meta = kernel_of(device_asm, mangled(kernel), "spectrum kernel")
     assert not [l for l in body if "atomic" in l], f"{kernel} uses atomics"
-    meta = "\n".join(device_asm[end:end + 120])
     assert re.search(r"; ScratchSize: 0\b", meta), f"{kernel} spills to scratch"
     assert re.search(r"; LDSByteSize: %d\b" % lds, meta), f"{kernel}: LDS beyond the tree of 256 doubles"

@@ -3,15 +3,13 @@ before any device is touched), analysis.msd, and the compiled trace kernels (hip
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from device_listing import device_asm, kernel_of, mangled   # noqa: F401  (device_asm: the listing fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "binary-fluctuating-lattice-boltzmann_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 TRACE_SYMBOLS = ["bflbm_trace_create", "bflbm_batch_trace_create", "bflbm_trace_destroy", "bflbm_trace_sample",
                  "bflbm_trace_reset", "bflbm_trace_count", "bflbm_trace_read"]
@@ -71,21 +69,7 @@ def test_msd_against_a_double_loop(pkg):
         pkg.analysis.msd(r, 40)
 
 
-@pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("asm") / "bflbm.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-w",
-                    "--cuda-device-only", "-S", "-o", str(out), "bflbm.hip"], cwd=CSRC, check=True, timeout=600)
-    return out.read_text().split("\n")
-
-
 @pytest.mark.parametrize("kernel", ["k_trace_moments", "k_trace_moments_batch", "k_trace_finish"])
 def test_trace_kernel_compiled_without_scratch(device_asm, kernel):
-    label = re.compile(r"^_Z\w*?%d%sE\w*:" % (len(kernel), kernel))           # Itanium mangling: <length><name>
-    starts = [i for i, l in enumerate(device_asm) if label.match(l)]
-    assert len(starts) == 1, f"trace kernel {kernel}: {len(starts)} definitions in the gfx950 assembly"
-    end = [i for i in range(starts[0], len(device_asm)) if device_asm[i].startswith(".Lfunc_end")][0]
-    meta = "\n".join(device_asm[end:end + 120])
+    _, meta = kernel_of(device_asm, mangled(kernel), "trace kernel")
     assert re.search(r"; ScratchSize: 0\b", meta), f"{kernel} spills to scratch"

@@ -6,7 +6,7 @@ import re
 
 import pytest
 
-from test_kernel_schedule import _steady_loop, device_asm   # noqa: F401  (the listing fixture)
+from device_listing import device_asm, kernel_of, spills, steady_loop   # noqa: F401  (device_asm: the listing fixture)
 
 # unit-rate kernel -> the generic kernel it stands in for
 UNIT_KERNELS = {
@@ -25,27 +25,14 @@ UNIT_KERNELS = {
 
 
 def _kernel(lines, symbol):
-    starts = [i for i, l in enumerate(lines) if re.match(r"^%s\w*:" % symbol, l)]
-    assert len(starts) == 1, f"{symbol} not in the gfx950 assembly"
-    end = [i for i in range(starts[0], len(lines)) if lines[i].startswith(".Lfunc_end")][0]
-    return lines[starts[0]:end], "\n".join(lines[end:end + 120])
-
-
-def _spills(lines, symbol):
-    """(sgpr_spill_count, vgpr_spill_count, private_segment_fixed_size) of a kernel from the code object metadata."""
-    at = [i for i, l in enumerate(lines) if re.match(r"\s+\.name:\s+%s\w*$" % symbol, l)]
-    assert len(at) == 1, symbol
-    lo = max(i for i in range(at[0]) if lines[i].startswith("  - .")) if any(lines[i].startswith("  - .") for i in range(at[0])) else 0
-    hi = min([i for i in range(at[0] + 1, len(lines)) if lines[i].startswith("  - .") or lines[i].startswith("amdhsa.")] + [len(lines)])
-    rec = "\n".join(lines[lo:hi])
-    return tuple(int(re.search(r"\.%s:\s+(\d+)" % k, rec).group(1)) for k in ("sgpr_spill_count", "vgpr_spill_count", "private_segment_fixed_size"))
+    return kernel_of(lines, r"^%s\w*:" % symbol)
 
 
 @pytest.mark.parametrize("symbol", list(UNIT_KERNELS))
 def test_unit_rate_kernel_compiled_without_scratch_or_more_spills(device_asm, symbol):
     _, meta = _kernel(device_asm, symbol)
     assert re.search(r"; ScratchSize: 0\b", meta), f"{symbol} spills to scratch"
-    unit, gen = _spills(device_asm, symbol), _spills(device_asm, UNIT_KERNELS[symbol])
+    unit, gen = spills(device_asm, symbol), spills(device_asm, UNIT_KERNELS[symbol])
     print(symbol, "sgpr spills, vgpr spills, scratch bytes:", unit, "generic:", gen)
     assert unit[2] == 0
     assert unit[0] <= gen[0] and unit[1] <= gen[1], (unit, gen)
@@ -59,7 +46,7 @@ def _valu(body, lo, hi):
 def test_handover_unit_kernel_lost_the_ghost_mode_arithmetic_and_kept_the_spread(device_asm, rag):
     gen, _ = _kernel(device_asm, r"_Z10k_fused_hoILi4ELi0ELb%dEE" % rag)
     unit, _ = _kernel(device_asm, r"_Z15k_fused_ho_unitILi4ELb%dEE" % rag)
-    (glo, ghi), (ulo, uhi) = _steady_loop(gen), _steady_loop(unit)
+    (glo, ghi), (ulo, uhi) = steady_loop(gen), steady_loop(unit)
     vg, vu = _valu(gen, glo, ghi), _valu(unit, ulo, uhi)
     print(f"rag={rag}: VALU instructions in the steady-state loop {vg} -> {vu}")
     # nine ghost rows of d_moments (about 8 additions each), their relaxation (3 each) and what d_population_terms does with

@@ -10,16 +10,15 @@ profiles/request_placement_ab.txt) and none of it shows in the source as such, s
 """
 import re
 
-from test_kernel_schedule import _steady_loop, device_asm   # noqa: F401  (the listing fixture)
-from test_unit_rate_listing import _kernel
+from device_listing import device_asm, kernel_of, steady_loop   # noqa: F401  (device_asm: the listing fixture)
 
 SYMBOL = r"_Z15k_fused_ho_unitILi4ELb0EE"
 DEFERRED, AT_ONCE = 15, 4
 
 
 def _loop(device_asm):
-    body, _ = _kernel(device_asm, SYMBOL)
-    lo, hi = _steady_loop(body)
+    body, _ = kernel_of(device_asm, r"^%s\w*:" % SYMBOL)
+    lo, hi = steady_loop(body)
     ops = []
     for l in body[lo:hi]:
         t = l.split()[0] if l.split() else ""
