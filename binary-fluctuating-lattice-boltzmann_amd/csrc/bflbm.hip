@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -94,6 +95,7 @@ struct bflbm_ctx {
   bflbm_domain dom;
   Geo G;
   int nzl = 0;
+  int ncu = 256;                 // compute units of dom.device: what the launch plans of this context are made for (bflbm_fused.h)
   double* S[2] = {nullptr, nullptr};
   int cur = 0;
   double* rho = nullptr;
@@ -247,7 +249,7 @@ int launch_handover(bflbm_ctx* c, int pa, int pb, int pair_len = 0) {
   const int kind = pair_len > 0 ? 1 : 0;
   HoSig sig;
   const hipError_t e = handover_launch(c->S[c->cur], c->S[1 - c->cur], c->frames[c->cur], c->frames[1 - c->cur], c->G, c->dp, pa, pb,
-                                       c->steps, c->fsig[c->cur][kind], sig, c->stream, pair_len, c->dp.noise_on ? 1 : 0);
+                                       c->steps, c->fsig[c->cur][kind], sig, c->ncu, c->stream, pair_len, c->dp.noise_on ? 1 : 0);
   c->fsig[1 - c->cur][kind] = (e == hipSuccess) ? sig : HoSig();     // frames are valid only where a launch wrote them
   return e != hipSuccess ? fail("hand-over launch failed: %s", hipGetErrorString(e)) : 0;
 }
@@ -255,7 +257,7 @@ int launch_handover(bflbm_ctx* c, int pa, int pb, int pair_len = 0) {
 int launch_fused(bflbm_ctx* c, int pa, int pb, int pair_len = 0) {
   if (pb <= pa) return 0;
   const hipError_t e = fused_launch(c->S[c->cur], c->S[1 - c->cur], c->injf, c->injg, c->G, c->dp, pa, pb,
-                                    (uint32_t)c->steps, c->inject ? 2 : (c->dp.noise_on ? 1 : 0), c->stream, pair_len);
+                                    (uint32_t)c->steps, c->inject ? 2 : (c->dp.noise_on ? 1 : 0), c->ncu, c->stream, pair_len);
   return e != hipSuccess ? fail("fused launch failed: %s", hipGetErrorString(e)) : 0;
 }
 
@@ -285,11 +287,10 @@ inline bool handover_contract_params(const bflbm_ctx* c) {
 // alternative is the two-pass schedule and the hand-over kernel wins on every ragged lattice measured (250^3 +25 %).
 inline bool handover_worthwhile(const bflbm_ctx* c, bool noisy) {
   constexpr int min_lz = 16;
-  const int lo = c->G.H, hi = c->G.H + c->nzl;
-  const int a = c->G.zwrap ? lo : lo + 2, b = c->G.zwrap ? hi : hi - 2;   // the interior sweep
-  if (b - a < min_lz) return false;
+  const StepRanges R = step_ranges(c->G, c->nzl);
+  if (R.b - R.a < min_lz) return false;
   FusedGrid F;
-  handover_plan(c->G, a, b, 0, F);
+  (void)launch_plan(3, c->G, R.a, R.b, 0, 0, c->ncu, F);
   if (F.lz < min_lz) return false;
   if (noisy) return true;
   const double lanes_busy = (double)c->G.nx / (64.0 * F.ntx);
@@ -301,12 +302,11 @@ inline bool handover_worthwhile(const bflbm_ctx* c, bool noisy) {
 // schedule faster (same doubles): 32^3 2440 against 1000 MLUPS, 48^3 5070 / 3350, the reference's 8 x 256 x 64 flat-interface
 // box 5910 / 3530; 64^3 (exactly 256 workgroups) and 96^3 are equal (tools/size_sweep.sh, NOTES.md section 3.1d).
 inline int exact_quiet_schedule(const bflbm_ctx* c) {
-  const int lo = c->G.H, hi = c->G.H + c->nzl;
-  const int a = c->G.zwrap ? lo : lo + 2, b = c->G.zwrap ? hi : hi - 2;   // the interior sweep
-  if (b - a < 2) return 0;                       // a slab of 4 or 5 planes is all boundary pairs
+  const StepRanges R = step_ranges(c->G, c->nzl);
+  if (R.b - R.a < 2) return 0;                   // a slab of 4 or 5 planes is all boundary pairs
   FusedGrid F;
-  (void)fused_plan(c->G, a, b, 0, 0, F);
-  return F.total < device_cus() ? 0 : 1;
+  (void)launch_plan(1, c->G, R.a, R.b, 0, 0, c->ncu, F);
+  return F.total < c->ncu ? 0 : 1;
 }
 
 // 0 two-pass, 1 fused (pulled ring), 3 hand-over.  The bit-exact choice is 1 at zero noise and 0 with noise.
@@ -387,18 +387,19 @@ void halos_written(bflbm_ctx* c) { c->density_valid = false; }
 // A boundary or interior sweep failed: the step closes with S[cur] intact (it may be retried); no frame of S[1-cur] is valid.
 int sweep_failed(bflbm_ctx* c) { c->step_sch = -1; for (auto& sg : c->fsig[1 - c->cur]) sg = HoSig(); return 1; }
 
-// One sweep of the resolved schedule sch (0 two-pass, 1 fused, 3 hand-over) over the storage planes [pa, pb).
-// pair_len > 0: only the boundary plane pairs [pa, pa+pair_len) and [pb-pair_len, pb) of a slab; the plane-marching
-// kernels take both in one launch where they are disjoint.
-int launch_sweep(bflbm_ctx* c, int sch, int pa, int pb, int pair_len = 0) {
-  if (sch == 0) {
-    if (ensure_density(c)) return 1;
-    if (pair_len == 0) return launch_collide(c, pa, pb);
-    return launch_collide(c, pa, pa + pair_len) || launch_collide(c, pb - pair_len, pb);
-  }
-  auto launch = [&](int a, int b) { return sch == 3 ? launch_handover(c, a, b, pair_len) : launch_fused(c, a, b, pair_len); };
-  if (pair_len == 0 || pb - pa > 2 * pair_len) return launch(pa, pb);
-  return launch(pa, pa + pair_len) || launch(pb - pair_len, pb);
+// One sweep of the resolved schedule sch (0 two-pass, 1 fused, 3 hand-over) over a part of step_ranges: the interior, or
+// (pairs) the two boundary plane pairs of a slab, which the plane-marching kernels take in one launch where they may.
+int launch_sweep(bflbm_ctx* c, int sch, bool pairs) {
+  const StepRanges R = step_ranges(c->G, c->nzl);
+  if (sch == 0 && ensure_density(c)) return 1;
+  auto launch = [&](int pa, int pb) {
+    if (sch == 0) return launch_collide(c, pa, pb);
+    const int pair_len = pairs ? R.pair_len : 0;
+    return sch == 3 ? launch_handover(c, pa, pb, pair_len) : launch_fused(c, pa, pb, pair_len);
+  };
+  if (!pairs) return launch(R.a, R.b);
+  if (sch != 0 && R.one_pair_launch) return launch(R.lo, R.hi);
+  return launch(R.lo, R.a) || launch(R.b, R.hi);
 }
 
 struct Overlap { int x0, x1, y0, y1, z0, z1; bool empty; };
@@ -532,6 +533,18 @@ static void domain_geo(const bflbm_domain* d, Geo& G) {
   G.vol = G.plane * G.nzs + pad;
 }
 
+// The domain of whoever owns the first `planes` planes of the lattice n, on device 0: all of it (nranks 1) or a slab of a ring of nranks
+static bflbm_domain periodic_domain(const int n[3], int planes, int nranks) {
+  bflbm_domain d;
+  for (int a = 0; a < 3; ++a) d.n[a] = n[a];
+  d.z0 = 0; d.z1 = planes; d.rank = 0; d.nranks = nranks; d.device = 0;
+  return d;
+}
+
+// What compute_units == 0 means to the plan queries (include/bflbm.h): the count of the device of the last context created,
+// 256 before.  Written by create_ctx and read by the two queries; no launch plan reads it (a context plans with its own ncu).
+static std::atomic<int> g_query_ncu{256};
+
 // ext: a replica of a batch (bflbm_batch_create): runs on the batch's stream ext and draws no placement
 static int create_ctx(const bflbm_params* p, const bflbm_domain* d, hipStream_t ext, bflbm_ctx** out) {
   if (!p || !d || !out) return fail("bflbm_create: null argument");
@@ -578,7 +591,7 @@ static int create_ctx(const bflbm_params* p, const bflbm_domain* d, hipStream_t 
   c->bytes = 2 * sbytes + 2 * fbytes + c->partial_n * 5 * sizeof(double);
   // halo planes must never hold NaN garbage that a reduction could touch
   hipMemsetAsync(c->S[0], 0, sbytes, c->stream);
-  { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, d->device) == hipSuccess && ncu > 0) g_fused_ncu = ncu; }
+  { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, d->device) == hipSuccess && ncu > 0) g_query_ncu = c->ncu = ncu; }
   hipMemsetAsync(c->S[1], 0, sbytes, c->stream);
   hipMemsetAsync(c->rho, 0, fbytes, c->stream);
   hipMemsetAsync(c->phi, 0, fbytes, c->stream);
@@ -909,7 +922,7 @@ int bflbm_step_boundary(bflbm_ctx* c) {
   if (sch < 0) return 1;
   c->step_sch = sch;                             // the step runs sch to its end: what could change it is refused until then
   if (c->G.zwrap) return 0;                      // single slab: everything is "interior"
-  return launch_sweep(c, sch, own_lo(c), own_hi(c), 2) ? sweep_failed(c) : 0;
+  return launch_sweep(c, sch, true) ? sweep_failed(c) : 0;
 }
 
 int bflbm_step_interior(bflbm_ctx* c) {
@@ -917,9 +930,7 @@ int bflbm_step_interior(bflbm_ctx* c) {
   BFLBM_REFUSE_VIEW(c, "bflbm_step_interior", "use bflbm_batch_step");
   if (!c->step_open()) return fail("bflbm_step_interior: call bflbm_step_boundary first");
   HIP_TRY(hipSetDevice(c->dom.device));
-  const int lo = own_lo(c), hi = own_hi(c);
-  const int a = c->G.zwrap ? lo : lo + 2, b = c->G.zwrap ? hi : hi - 2;
-  return launch_sweep(c, c->step_sch, a, b) ? sweep_failed(c) : 0;
+  return launch_sweep(c, c->step_sch, false) ? sweep_failed(c) : 0;
 }
 
 int bflbm_step_finish(bflbm_ctx* c) {
@@ -1513,6 +1524,7 @@ int bflbm_ring_sync(bflbm_ring* r) {
 namespace {
 
 void batch_obs_free(bflbm_batch* b);                 // the getters' dense buffer (bflbm_batch_sf.h)
+inline int batch_cus(const bflbm_batch* b) { return b->ctx[0]->ncu; }   // compute units: its replicas share one device
 
 // `auto` of a batch: the rule of exact_quiet_schedule over the whole batch -- the one-pass kernel once the fused
 // workgroups of all replicas fill the compute units, the two-pass schedule otherwise.  Unlike a lone lattice, a batch
@@ -1524,8 +1536,8 @@ int batch_resolved(const bflbm_batch* b) {
   bool noise = false;
   for (const bflbm_ctx* c : b->ctx) noise = noise || c->dp.noise_on;
   FusedGrid F;
-  (void)batch_fused_plan(b->G, (int)b->ctx.size(), noise ? 1 : 0, F);
-  return (long long)F.total * (long long)b->ctx.size() < device_cus() ? 0 : 1;
+  (void)batch_fused_plan(b->G, (int)b->ctx.size(), noise ? 1 : 0, batch_cus(b), F);
+  return (long long)F.total * (long long)b->ctx.size() < batch_cus(b) ? 0 : 1;
 }
 
 // Rewrite the device records when some replica's record is stale (a new view, new parameters, an init or upload,
@@ -1578,9 +1590,8 @@ int bflbm_batch_create(const bflbm_params* p, int nreplicas, const int n[3], int
   hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
   if (e != hipSuccess) { b->stream = nullptr; bflbm_batch_destroy(b); return fail("bflbm_batch_create: %s", hipGetErrorString(e)); }
   for (int r = 0; r < nreplicas; ++r) {
-    bflbm_domain d;
-    for (int a = 0; a < 3; ++a) d.n[a] = n[a];
-    d.z0 = 0; d.z1 = n[2]; d.rank = 0; d.nranks = 1; d.device = device;
+    bflbm_domain d = periodic_domain(n, n[2], 1);
+    d.device = device;
     bflbm_ctx* c = nullptr;
     if (create_ctx(&p[r], &d, b->stream, &c)) {
       const std::string msg = g_err;
@@ -1659,7 +1670,7 @@ int bflbm_batch_step(bflbm_batch* b, int nsteps) {
   for (const bflbm_ctx* c : b->ctx) unit = unit && unit_rates(c->dp);
   for (int s = 0; s < nsteps; ++s) {
     if (batch_sync_table(b)) return 1;
-    const hipError_t e = sch == 1 ? batch_fused_launch(b->d_rec, b->G, nrep, noise ? 1 : 0, unit, (int)b->k, b->stream)
+    const hipError_t e = sch == 1 ? batch_fused_launch(b->d_rec, b->G, nrep, noise ? 1 : 0, unit, (int)b->k, batch_cus(b), b->stream)
                                   : batch_two_pass_launch(b->d_rec, b->G, nrep, noise, unit, (int)b->k, b->stream);
     if (e != hipSuccess) return fail("bflbm_batch_step: launch failed: %s", hipGetErrorString(e));
     b->k += 1;
@@ -1677,7 +1688,7 @@ int bflbm_batch_sync(bflbm_batch* b) {
 }
 
 // The plan of the one-pass schedule for a periodic lattice n[3] (see include/bflbm.h).  Host arithmetic only: the planner
-// functions the launches call (fused_launch, batch_fused_launch), with compute_units > 0 in place of device_cus() for this call.
+// functions the launches call (fused_launch, batch_fused_launch), with compute_units > 0 in place of the held count.
 int bflbm_fused_plan_query(const int n[3], int nreplicas, int noise, int compute_units, int out[16]) {
   if (!n || !out) return fail("bflbm_fused_plan_query: null argument");
   if (nreplicas < 1 || nreplicas > 65535) return fail("bflbm_fused_plan_query: nreplicas must be in 1..65535 (got %d)", nreplicas);
@@ -1685,19 +1696,14 @@ int bflbm_fused_plan_query(const int n[3], int nreplicas, int noise, int compute
   if ((long long)(n[0] + 15) * n[1] * (long long)(n[2] + 4) >= (1LL << 31) || (long long)(n[0] + 15) * n[1] >= (1LL << 28))
     return fail("bflbm_fused_plan_query: %d x %d x %d is too large for 32-bit site offsets", n[0], n[1], n[2]);
   if (compute_units < 0) return fail("bflbm_fused_plan_query: compute_units < 0");
-  bflbm_domain d;
-  for (int a = 0; a < 3; ++a) d.n[a] = n[a];
-  d.z0 = 0; d.z1 = n[2]; d.rank = 0; d.nranks = 1; d.device = 0;
+  const bflbm_domain d = periodic_domain(n, n[2], 1);
   Geo G;
   domain_geo(&d, G);
   const int mode = noise ? 1 : 0;
-  const int held = g_fused_ncu;
-  if (compute_units > 0) g_fused_ncu = compute_units;
+  const int ncu = compute_units > 0 ? compute_units : g_query_ncu.load();
   FusedGrid F;
   const int threads = nreplicas == 1 ? FUSED_TX * FUSED_TY : batch_fused_threads(mode);
-  const int TX = nreplicas == 1 ? fused_plan(G, 0, G.nzs, mode, 0, F) : batch_fused_plan(G, nreplicas, mode, F);
-  const int ncu = device_cus();
-  g_fused_ncu = held;
+  const int TX = launch_plan(1, G, 0, G.nzs, 0, mode, ncu, F, nreplicas, threads);
   const long long all = (long long)nreplicas * F.total;
   const long long per_xcd = nreplicas == 1 ? F.per_xcd : (all + 7) / 8;   // the lists of fused_map and batch_map
   if (per_xcd * 8 > (long long)INT32_MAX) return fail("bflbm_fused_plan_query: the launch exceeds 2^31 workgroups");
@@ -1713,8 +1719,8 @@ int bflbm_fused_plan_query(const int n[3], int nreplicas, int noise, int compute
 }
 
 // The plans of the plane-marching sweeps of one step (see include/bflbm.h): the interior sweep of bflbm_step_interior and,
-// for a slab, the boundary-pair launch of bflbm_step_boundary, from handover_plan / fused_plan as launch_sweep reaches
-// them, with compute_units > 0 in place of device_cus() for this call.
+// for a slab, the boundary-pair launch of bflbm_step_boundary: launch_plan over the step_ranges launch_sweep walks, with
+// compute_units > 0 in place of the held count.
 int bflbm_sweep_plan_query(const int n[3], int schedule, int noise, int slab_planes, int compute_units, int out[16]) {
   if (!n || !out) return fail("bflbm_sweep_plan_query: null argument");
   if (schedule != 1 && schedule != 3) return fail("bflbm_sweep_plan_query: schedule must be 1 (fused) or 3 (hand-over) (got %d)", schedule);
@@ -1725,30 +1731,19 @@ int bflbm_sweep_plan_query(const int n[3], int schedule, int noise, int slab_pla
   if ((long long)(n[0] + 15) * n[1] * (long long)(nzl + 4) >= (1LL << 31) || (long long)(n[0] + 15) * n[1] >= (1LL << 28))
     return fail("bflbm_sweep_plan_query: %d x %d x %d is too large for 32-bit site offsets", n[0], n[1], nzl);
   if (compute_units < 0) return fail("bflbm_sweep_plan_query: compute_units < 0");
-  bflbm_domain d;
-  for (int a = 0; a < 3; ++a) d.n[a] = n[a];
-  d.z0 = 0; d.z1 = nzl; d.rank = 0; d.nranks = slab_planes ? 2 : 1; d.device = 0;
+  const bflbm_domain d = periodic_domain(n, nzl, slab_planes ? 2 : 1);
   Geo G;
   domain_geo(&d, G);
   if (schedule == 3 && !handover_ok(G))
     return fail("bflbm_sweep_plan_query: the hand-over kernel does not take a %d x %d lattice (a last tile column or row of one site, or less than one tile)", n[0], n[1]);
   const int mode = noise ? 1 : 0;
-  const int lo = G.H, hi = G.H + nzl;
-  const int a = G.zwrap ? lo : lo + 2, b = G.zwrap ? hi : hi - 2;        // the interior sweep (bflbm_step_interior)
-  const int held = g_fused_ncu;
-  if (compute_units > 0) g_fused_ncu = compute_units;
-  auto plan = [&](int pa, int pb, int pair_len, FusedGrid& F) {
-    if (schedule == 3) { handover_plan(G, pa, pb, pair_len, F); return 64; }
-    return fused_plan(G, pa, pb, mode, pair_len, F);
-  };
+  const int ncu = compute_units > 0 ? compute_units : g_query_ncu.load();
+  const StepRanges R = step_ranges(G, nzl);
+  const bool interior = R.b > R.a;                                       // a slab of 4 planes is all boundary pairs
   FusedGrid F, Fp;
-  int TX = 0;
-  const bool interior = b > a;                                           // a slab of 4 planes is all boundary pairs
-  if (interior) TX = plan(a, b, 0, F);
-  const bool one_pair_launch = hi - lo > 4;                              // launch_sweep: one launch where the pairs are disjoint
-  if (!G.zwrap) { const int t = one_pair_launch ? plan(lo, hi, 2, Fp) : plan(lo, lo + 2, 2, Fp); if (!interior) TX = t; }
-  const int ncu = device_cus();
-  g_fused_ncu = held;
+  int TX = 0;                                                            // the same tile for both sweeps
+  if (!G.zwrap) TX = launch_plan(schedule, G, R.lo, R.one_pair_launch ? R.hi : R.a, R.pair_len, mode, ncu, Fp);   // launch_sweep's first pair launch
+  if (interior) TX = launch_plan(schedule, G, R.a, R.b, 0, mode, ncu, F);
   for (int i = 0; i < 16; ++i) out[i] = 0;
   out[0] = TX; out[1] = schedule == 3 ? HO_TY : (FUSED_TX * FUSED_TY) / TX;
   out[13] = ncu;
@@ -1759,7 +1754,7 @@ int bflbm_sweep_plan_query(const int n[3], int schedule, int noise, int slab_pla
     out[10] = (F.total + ncu - 1) / ncu;
     out[11] = F.per_xcd; out[12] = F.per_xcd * 8;
   } else { out[2] = Fp.ntx; out[3] = Fp.nty; out[4] = Fp.sx; }
-  if (!G.zwrap) { out[14] = Fp.lz; out[15] = one_pair_launch ? Fp.cstride : 0; }
+  if (!G.zwrap) { out[14] = Fp.lz; out[15] = R.one_pair_launch ? Fp.cstride : 0; }
   return 0;
 }
 

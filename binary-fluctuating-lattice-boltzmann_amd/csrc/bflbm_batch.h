@@ -120,29 +120,23 @@ k_fused_batch_unit(const BatchRec* __restrict__ recs, Geo G, FusedGrid F, int nr
 
 // the batch's tile shape and chunking: the single-lattice plan with the workgroups of all replicas counted
 static inline int batch_fused_threads(int mode) { return mode == 1 ? 256 : FUSED_TX * FUSED_TY; }
-static inline int batch_fused_plan(const Geo& G, int nrep, int mode, FusedGrid& F) {
-  return fused_plan(G, 0, G.nzs, mode, 0, F, nrep, batch_fused_threads(mode));
+static inline int batch_fused_plan(const Geo& G, int nrep, int mode, int ncu, FusedGrid& F) {
+  return launch_plan(1, G, 0, G.nzs, 0, mode, ncu, F, nrep, batch_fused_threads(mode));
 }
 
 // unit: the caller found zero noise and unit_rates() in every replica
-static inline hipError_t batch_fused_launch(const BatchRec* recs, const Geo& G, int nrep, int mode, bool unit, int k, hipStream_t stream) {
+static inline hipError_t batch_fused_launch(const BatchRec* recs, const Geo& G, int nrep, int mode, bool unit, int k, int ncu, hipStream_t stream) {
   FusedGrid F;
-  const int TX = batch_fused_plan(G, nrep, mode, F);
+  const int TX = batch_fused_plan(G, nrep, mode, ncu, F);
   const long long per_xcd = ((long long)nrep * F.total + 7) / 8;
   if (per_xcd * 8 > (long long)INT32_MAX) return hipErrorInvalidConfiguration;
   dim3 grid((unsigned)(per_xcd * 8)), block(batch_fused_threads(mode));
-  constexpr int TX0 = FUSED_TX, TY0 = FUSED_TY;
-  if (mode == 1)      hipLaunchKernelGGL((k_fused_batch<32, 8, 1>), grid, block, 0, stream, recs, G, F, nrep, k);
-  else if (unit) {
-    if (TX == 32)      hipLaunchKernelGGL((k_fused_batch_unit<32, (TX0 * TY0) / 32>), grid, block, 0, stream, recs, G, F, nrep, k);
-    else if (TX == 16) hipLaunchKernelGGL((k_fused_batch_unit<16, (TX0 * TY0) / 16>), grid, block, 0, stream, recs, G, F, nrep, k);
-    else if (TX == 8)  hipLaunchKernelGGL((k_fused_batch_unit<8, (TX0 * TY0) / 8>), grid, block, 0, stream, recs, G, F, nrep, k);
-    else               hipLaunchKernelGGL((k_fused_batch_unit<TX0, TY0>), grid, block, 0, stream, recs, G, F, nrep, k);
-  }
-  else if (TX == 32)  hipLaunchKernelGGL((k_fused_batch<32, (TX0 * TY0) / 32, 0>), grid, block, 0, stream, recs, G, F, nrep, k);
-  else if (TX == 16)  hipLaunchKernelGGL((k_fused_batch<16, (TX0 * TY0) / 16, 0>), grid, block, 0, stream, recs, G, F, nrep, k);
-  else if (TX == 8)   hipLaunchKernelGGL((k_fused_batch<8, (TX0 * TY0) / 8, 0>), grid, block, 0, stream, recs, G, F, nrep, k);
-  else                hipLaunchKernelGGL((k_fused_batch<TX0, TY0, 0>), grid, block, 0, stream, recs, G, F, nrep, k);
+  if (mode == 1) hipLaunchKernelGGL((k_fused_batch<32, 8, 1>), grid, block, 0, stream, recs, G, F, nrep, k);
+  else fused_dispatch_tile(TX, [&](auto tx) {
+    constexpr int X = decltype(tx)::value, Y = (FUSED_TX * FUSED_TY) / X;
+    if (unit) hipLaunchKernelGGL((k_fused_batch_unit<X, Y>), grid, block, 0, stream, recs, G, F, nrep, k);
+    else      hipLaunchKernelGGL((k_fused_batch<X, Y, 0>), grid, block, 0, stream, recs, G, F, nrep, k);
+  });
   return hipGetLastError();
 }
 

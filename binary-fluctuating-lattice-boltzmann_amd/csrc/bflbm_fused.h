@@ -21,6 +21,7 @@
 #ifndef BFLBM_FUSED_H_
 #define BFLBM_FUSED_H_
 
+#include <type_traits>
 #include "bflbm_kernels.h"
 
 struct FusedGrid {
@@ -94,10 +95,21 @@ k_fused_unit(const double* __restrict__ S, double* __restrict__ D,
 #undef BFLBM_FUSED_MAP
 }
 
-constexpr int FUSED_TX = 64, FUSED_TY = 8;   // tile shape of the fused kernel (narrower lattices at zero noise: see fused_plan)
+constexpr int FUSED_TX = 64, FUSED_TY = 8;   // tile shape of the fused kernel (narrower lattices at zero noise: see launch_plan)
+constexpr int HO_TY = 4;                     // tile height of the hand-over kernel of bflbm_handover.h (tiles are 64 x HO_TY)
 
-static int g_fused_ncu = 0;     // compute units of the device (set at context creation)
-static inline int device_cus() { return g_fused_ncu > 0 ? g_fused_ncu : 256; }
+// ---- the launch-plan layer: host arithmetic, no ambient state.  ncu is the compute-unit count of the device of whoever
+// launches: a context's own (bflbm_ctx::ncu), a batch's replicas', or what a plan query was given.
+// The cut of one step over a context's own storage planes [lo, hi) = [H, H + nzl).  A periodic lattice is all interior
+// (pair_len 0).  A slab advances its two boundary pairs of pair_len = 2 planes, [lo, a) and [b, hi), first
+// (bflbm_step_boundary: its neighbours wait for them) and the interior [a, b) while they travel (bflbm_step_interior); a slab
+// of 4 planes has no interior (b <= a).  one_pair_launch: the pairs are disjoint and the plane-marching kernels take both in
+// ONE launch over [lo, hi).
+struct StepRanges { int lo, hi, pair_len, a, b; bool one_pair_launch; };
+static inline StepRanges step_ranges(const Geo& G, int nzl) {
+  const int lo = G.H, hi = G.H + nzl, pair_len = G.zwrap ? 0 : 2;
+  return {lo, hi, pair_len, lo + pair_len, hi - pair_len, pair_len > 0 && hi - lo > 2 * pair_len};
+}
 
 // Chunking of a launch of np planes over F.ncols tile columns (both plane-marching kernels); fills lz, nchunks, cstride,
 // total and per_xcd.  min_chunk: the shortest chunk the kernel takes.  nrep > 1: a replica batch launches nrep copies of
@@ -115,9 +127,8 @@ static inline int device_cus() { return g_fused_ncu > 0 ? g_fused_ncu : 256; }
 // (profiles/r04_chunk_scan.txt): a model fitted on the first box ((rounds + tail) x (planes + 4): 448^3 +5 % with 7
 // chunks, 512^3 +5 % with 4) changed nothing on the second (every lattice within the +-2 % process-to-process scatter,
 // 512x512x128 2 % SLOWER with its choice), so the rule stays.
-static inline void plan_chunks(FusedGrid& F, int np, bool zwrap, int min_chunk, int nrep, int pair_len) {
+static inline void plan_chunks(FusedGrid& F, int np, bool zwrap, int min_chunk, int nrep, int pair_len, int ncu) {
   constexpr int min_slab_rounds = 3;
-  const int ncu = device_cus();
   const int maxchunks = std::max(1, np / min_chunk);             // small lattices: short chunks buy parallelism
   long long best = -1;
   int nchunks = 1;
@@ -138,45 +149,49 @@ static inline void plan_chunks(FusedGrid& F, int np, bool zwrap, int min_chunk, 
   F.per_xcd = (F.total + 7) / 8;
 }
 
-// Tile shape, chunking and workgroup order of one launch of the fused kernel over the storage planes [pa, pb); returns the
-// tile width (the height is threads / width).  nrep, pair_len: see plan_chunks.
-// threads: workgroup size (tiles of at least 8 rows; the batch's noise kernel runs 256)
-static inline int fused_plan(const Geo& G, int pa, int pb, int mode, int pair_len, FusedGrid& F, int nrep = 1,
-                             int threads = FUSED_TX * FUSED_TY) {
-  // Tile shape: 64 x 8 sites; lattices narrower than 64 in x get the same 512 sites as 32 x 16, 16 x 32 or 8 x 64
-  // (zero noise only; e.g. the reference's 8 x 256 x 64 flat-interface box would use 8 of 64 lanes of a 64-wide tile)
-  const int TX = std::min((mode != 0 || G.nx > 32) ? FUSED_TX : (G.nx > 16 ? 32 : (G.nx > 8 ? 16 : 8)), threads / 8);
-  const int TY = threads / TX;
+// The plan of one launch of schedule sch (3: the hand-over kernel of bflbm_handover.h; otherwise the fused kernel) over the
+// storage planes [pa, pb): fills F with tiles, chunking and workgroup order and returns the tile width (the height is threads /
+// width).  The hand-over form returns 64 (tiles of 64 x HO_TY) and ignores mode and threads.  nrep, pair_len: see plan_chunks.
+// threads: workgroup size of the fused kernel (tiles of at least 8 rows; the batch's noise kernel runs 256)
+static inline int launch_plan(int sch, const Geo& G, int pa, int pb, int pair_len, int mode, int ncu, FusedGrid& F, int nrep = 1,
+                              int threads = FUSED_TX * FUSED_TY) {
+  const bool ho = sch == 3;
+  // Tile shape of the fused kernel: 64 x 8 sites; lattices narrower than 64 in x get the same 512 sites as 32 x 16, 16 x 32 or
+  // 8 x 64 (zero noise only; e.g. the reference's 8 x 256 x 64 flat-interface box would use 8 of 64 lanes of a 64-wide tile)
+  const int TX = ho ? 64 : std::min((mode != 0 || G.nx > 32) ? FUSED_TX : (G.nx > 16 ? 32 : (G.nx > 8 ? 16 : 8)), threads / 8);
+  const int TY = ho ? HO_TY : threads / TX;
   F.ntx = (G.nx + TX - 1) / TX;
   F.nty = (G.ny + TY - 1) / TY;
   F.ncols = F.ntx * F.nty;
   F.pa = pa; F.pb = pb;
-  plan_chunks(F, pb - pa, G.zwrap, 2, nrep, pair_len);
-  F.sx = std::min(F.ntx, 4);      // strips of 4 tiles: +2 % at 512^3 (ntx = 8), identical at 256^3
+  plan_chunks(F, pb - pa, G.zwrap, ho ? 4 : 2, nrep, pair_len, ncu);   // a hand-over chunk shorter than 4 planes has no complete frame
+  F.sx = ho ? F.ntx : std::min(F.ntx, 4);      // fused: strips of 4 tiles: +2 % at 512^3 (ntx = 8), identical at 256^3
   return TX;
+}
+
+// launch(std::integral_constant<int, TX>()) for the tile width TX of a zero-noise plan of the fused kernel, one of
+// 64, 32, 16, 8 (the height is FUSED_TX * FUSED_TY / TX): how a launch picks the kernel's tile instantiation
+template <class Launch> void fused_dispatch_tile(int TX, Launch&& launch) {
+  if (TX == 32)      launch(std::integral_constant<int, 32>());
+  else if (TX == 16) launch(std::integral_constant<int, 16>());
+  else if (TX == 8)  launch(std::integral_constant<int, 8>());
+  else               launch(std::integral_constant<int, FUSED_TX>());
 }
 
 // returns the launch's error code
 static inline hipError_t fused_launch(const double* S, double* D, const double* injf, const double* injg,
                                const Geo& G, const DevParams& P, int pa, int pb,
-                               uint32_t noise_index, int mode, hipStream_t stream, int pair_len = 0) {
+                               uint32_t noise_index, int mode, int ncu, hipStream_t stream, int pair_len = 0) {
   FusedGrid F;
-  const int TX = fused_plan(G, pa, pb, mode, pair_len, F);
-  const int TY = (FUSED_TX * FUSED_TY) / TX;
-  dim3 grid((unsigned)(F.per_xcd * 8)), block(TX * TY);
-  constexpr int TX0 = FUSED_TX, TY0 = FUSED_TY;
-  if (mode == 2)      hipLaunchKernelGGL((k_fused<TX0, TY0, 2>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
-  else if (mode == 1) hipLaunchKernelGGL((k_fused<TX0, TY0, 1>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
-  else if (unit_rates(P)) {
-    if (TX == 32)      hipLaunchKernelGGL((k_fused_unit<32, (TX0 * TY0) / 32>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
-    else if (TX == 16) hipLaunchKernelGGL((k_fused_unit<16, (TX0 * TY0) / 16>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
-    else if (TX == 8)  hipLaunchKernelGGL((k_fused_unit<8, (TX0 * TY0) / 8>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
-    else               hipLaunchKernelGGL((k_fused_unit<TX0, TY0>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
-  }
-  else if (TX == 32)  hipLaunchKernelGGL((k_fused<32, (TX0 * TY0) / 32, 0>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
-  else if (TX == 16)  hipLaunchKernelGGL((k_fused<16, (TX0 * TY0) / 16, 0>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
-  else if (TX == 8)   hipLaunchKernelGGL((k_fused<8, (TX0 * TY0) / 8, 0>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
-  else                hipLaunchKernelGGL((k_fused<TX0, TY0, 0>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
+  const int TX = launch_plan(1, G, pa, pb, pair_len, mode, ncu, F);
+  dim3 grid((unsigned)(F.per_xcd * 8)), block(FUSED_TX * FUSED_TY);
+  if (mode == 2)      hipLaunchKernelGGL((k_fused<FUSED_TX, FUSED_TY, 2>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
+  else if (mode == 1) hipLaunchKernelGGL((k_fused<FUSED_TX, FUSED_TY, 1>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
+  else fused_dispatch_tile(TX, [&](auto tx) {
+    constexpr int X = decltype(tx)::value, Y = (FUSED_TX * FUSED_TY) / X;
+    if (unit_rates(P)) hipLaunchKernelGGL((k_fused_unit<X, Y>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
+    else               hipLaunchKernelGGL((k_fused<X, Y, 0>), grid, block, 0, stream, S, D, injf, injg, G, P, F, noise_index);
+  });
   return hipGetLastError();
 }
 

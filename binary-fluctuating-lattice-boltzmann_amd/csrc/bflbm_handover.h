@@ -145,8 +145,6 @@ k_fused_ho_unit(const double* __restrict__ S, double* __restrict__ D, Geo G, Dev
 #include "bflbm_handover_body.inc"
 }
 
-constexpr int HO_TY = 4;   // tile height of the hand-over kernel (tiles are 64 x HO_TY)
-
 // lattices the hand-over kernel takes: at least one whole tile; a narrower last tile column / lower last tile row needs
 // two lanes / rows (a ring site owned by a tile ONE site wide or high also collects from the tile beyond it, which the
 // 3 x 3 lookup of the consumer does not reach, and its two edge roles must be different lanes / rows)
@@ -161,24 +159,14 @@ static inline size_t handover_frame_doubles(const Geo& G) {
 struct HoSig { int pa = -1, pb = -1, lz = -1, nchunks = -1, cstride = -1; long long step = -1;
   bool same_geometry(const HoSig& o) const { return pa == o.pa && pb == o.pb && lz == o.lz && nchunks == o.nchunks && cstride == o.cstride; } };
 
-// Tiles, chunking and workgroup order of one launch over the storage planes [pa, pb) (pair_len: see plan_chunks)
-static inline void handover_plan(const Geo& G, int pa, int pb, int pair_len, FusedGrid& F) {
-  constexpr int TX = 64, TY = HO_TY;
-  F.ntx = (G.nx + TX - 1) / TX; F.nty = (G.ny + TY - 1) / TY;
-  F.ncols = F.ntx * F.nty;
-  F.pa = pa; F.pb = pb;
-  plan_chunks(F, pb - pa, G.zwrap, 4, 1, pair_len);       // a chunk shorter than 4 planes has no complete frame
-  F.sx = F.ntx;
-}
-
 // fin/fout: frame buffers of the state read / written.  sig_in: what wrote fin (step == steps-1 required);
 // sig_out: the signature of this launch's plan, which describes fout once the launch has succeeded.  returns the
 // launch's error code
 static inline hipError_t handover_launch(const double* S, double* D, const double* fin, double* fout, const Geo& G, const DevParams& P,
-                                  int pa, int pb, long long steps, const HoSig& sig_in, HoSig& sig_out, hipStream_t stream, int pair_len = 0, int mode = 0) {
+                                  int pa, int pb, long long steps, const HoSig& sig_in, HoSig& sig_out, int ncu, hipStream_t stream, int pair_len = 0, int mode = 0) {
   constexpr int TX = 64, TY = HO_TY;
   FusedGrid F;
-  handover_plan(G, pa, pb, pair_len, F);
+  (void)launch_plan(3, G, pa, pb, pair_len, mode, ncu, F);
   HoSig sig;
   sig.pa = pa; sig.pb = pb; sig.lz = F.lz; sig.nchunks = F.nchunks; sig.cstride = F.cstride; sig.step = steps;
   HoGrid Hg;

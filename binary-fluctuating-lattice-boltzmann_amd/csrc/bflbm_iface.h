@@ -6,7 +6,7 @@
 // The shape is that of bflbm_trace.h: stage 1 reads the resident populations (152 B per site, nothing written per site),
 // stage 2 writes the sample's slot; rho / phi / density_valid of the owner are not touched.  No atomics, no LDS.
 // The lifecycle and the sample store are those of bflbm_recorder.h; here are the kernels, their launch, the segment rule and
-// the checks of the kind's own arguments.  Included by bflbm.hip after bflbm_trace.h (needs bflbm_ctx, bflbm_batch, device_cus).
+// the checks of the kind's own arguments.  Included by bflbm.hip after bflbm_trace.h (needs bflbm_ctx, bflbm_batch, batch_cus).
 #ifndef BFLBM_IFACE_H_
 #define BFLBM_IFACE_H_
 
@@ -87,9 +87,9 @@ __global__ void __launch_bounds__(256) k_iface_finish(const double* __restrict__
 // The segment count is the host's choice and changes no bit of a sample (a height depends only on its own pair, and
 // stage 2 keeps the segment order).  Rule: the fewest segments that give stage 1 at least two workgroups per compute
 // unit, each segment at least 4 pairs long, the last one ragged.  An unmeasured heuristic: nobody has timed other counts.
-void iface_segments(const Geo& G, int nrep, int npairs, int* nseg, int* seg_pairs) {
+void iface_segments(const Geo& G, int nrep, int npairs, int ncu, int* nseg, int* seg_pairs) {
   const long long wgs = (long long)((G.plane + 255) / 256) * nrep;     // workgroups of one segment
-  const long long want = (2LL * device_cus() + wgs - 1) / wgs;
+  const long long want = (2LL * ncu + wgs - 1) / wgs;
   const long long most = std::max(1, npairs / 4);
   const int n0 = (int)std::min(want, most);
   *seg_pairs = (npairs + n0 - 1) / n0;
@@ -107,7 +107,7 @@ int iface_create(bflbm_ctx* c, bflbm_batch* b, int field, double level, int z_lo
   const int nrep = c ? 1 : (int)b->ctx.size();
   std::unique_ptr<bflbm_iface> t(new bflbm_iface());
   t->G = G; t->field = field; t->level = level; t->z_lo = z_lo; t->z_hi = z_hi;
-  iface_segments(G, nrep, z_hi - z_lo - 1, &t->nseg, &t->seg_pairs);
+  iface_segments(G, nrep, z_hi - z_lo - 1, c ? c->ncu : batch_cus(b), &t->nseg, &t->seg_pairs);
   const std::string shape = " x 2 x " + std::to_string(G.ny) + " x " + std::to_string(G.nx) + " heights";
   if (store_attach(t.get(), c, b, call, every, capacity, (size_t)nrep * 2 * (size_t)G.ny * (size_t)G.nx,
                    (size_t)nrep * t->nseg * 2 * (size_t)G.plane, shape.c_str())) return 1;

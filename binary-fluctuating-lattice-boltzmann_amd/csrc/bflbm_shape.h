@@ -12,7 +12,7 @@
 //   3. k_shape_rays: one ray per lane, the pairs (k-1, k) split into segments, every work item writes its first candidate;
 //   4. k_shape_finish: per ray the first non-NaN candidate in segment order, and the centre, into the sample's slot.
 // The lifecycle and the sample store are those of bflbm_recorder.h.  Included by bflbm.hip after bflbm_iface.h (needs
-// bflbm_ctx, bflbm_batch, device_cus, trace_moments_launch).
+// bflbm_ctx, bflbm_batch, batch_cus, trace_moments_launch).
 #ifndef BFLBM_SHAPE_H_
 #define BFLBM_SHAPE_H_
 
@@ -166,9 +166,9 @@ __global__ void __launch_bounds__(256) k_shape_finish(const double* __restrict__
 // stage 4 keeps the segment order).  Rule: the fewest segments that give stage 3 at least one wave per SIMD (4 per
 // compute unit), each segment at least 4 pairs long, the last one ragged.  An unmeasured heuristic, like the one-wave
 // workgroups of stage 3: nobody has timed other counts or launch shapes.
-void shape_segments(int nrep, int ndir, int nsteps, int* nseg, int* seg_len) {
+void shape_segments(int nrep, int ndir, int nsteps, int ncu, int* nseg, int* seg_len) {
   const long long wgs = (long long)((ndir + kShapeLanes - 1) / kShapeLanes) * nrep;   // workgroups of one segment
-  const long long want = (4LL * device_cus() + wgs - 1) / wgs;
+  const long long want = (4LL * ncu + wgs - 1) / wgs;
   const long long most = std::max(1, nsteps / 4);
   const int n0 = (int)std::min(want, most);
   *seg_len = (nsteps + n0 - 1) / n0;
@@ -202,7 +202,7 @@ int shape_create(bflbm_ctx* c, bflbm_batch* b, int field, double level, int dire
   t->com = !centre;
   if (centre) std::copy(centre, centre + 3, t->centre);
   t->ndir = ndir; t->step = step; t->nsteps = nsteps;
-  shape_segments(nrep, ndir, nsteps, &t->nseg, &t->seg_len);
+  shape_segments(nrep, ndir, nsteps, c ? c->ncu : batch_cus(b), &t->nseg, &t->seg_len);
   const size_t nbx = (size_t)((G.plane + 255) / 256);
   const size_t stage = 3 * (size_t)ndir + (size_t)nrep * (t->density_doubles() + (size_t)t->nseg * ndir)
                      + (t->com ? (size_t)nrep * kNTrace * (1 + nbx * (size_t)G.nz) : 0);
