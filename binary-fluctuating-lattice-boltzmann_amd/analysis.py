@@ -565,6 +565,61 @@ def histogram_moments(counts, lo, hi):
     return mean, var
 
 
+# ---- morphology: the numpy restatement of the morphology trace (include/bflbm.h, "Morphology traces") ----
+MORPH_MAX_LEVELS = 8
+MORPH_SIDES = {"above": 0, "below": 1}
+
+
+def minkowski_counts(field_zyx, levels, side="above"):
+    """counts[nlevels, 4] int64 of include/bflbm.h, "Morphology traces", in numpy: N3, N2, N1, N0, the cubes, faces,
+    edges and vertices of the union of the closed voxels of the sites with field >= level (side "above" or 0) or
+    field < level (side "below" or 1) on the periodic box field_zyx[nz, ny, nx], for 1..8 finite levels.  A NaN occupies
+    nothing on either side."""
+    v = np.asarray(field_zyx, dtype=np.float64)
+    lv = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if v.ndim != 3 or v.size == 0:
+        raise ValueError(f"minkowski_counts: a field [nz, ny, nx], got shape {v.shape}")
+    if lv.ndim != 1 or not (1 <= len(lv) <= MORPH_MAX_LEVELS):
+        raise ValueError(f"minkowski_counts: 1..{MORPH_MAX_LEVELS} levels (got shape {lv.shape})")
+    if not np.isfinite(lv).all():
+        raise ValueError(f"minkowski_counts: the levels must be finite (got {lv.tolist()})")
+    if side not in MORPH_SIDES and side not in MORPH_SIDES.values():
+        raise ValueError(f"minkowski_counts: side {side!r}, expected 'above' (0) or 'below' (1)")
+    below = bool(MORPH_SIDES.get(side, side))
+    out = np.empty((len(lv), 4), dtype=np.int64)
+
+    def nxt(a, axis):                                      # the periodic successor along an axis: 0 z, 1 y, 2 x
+        return np.roll(a, -1, axis=axis)
+
+    for l, t in enumerate(lv):
+        with np.errstate(invalid="ignore"):
+            o = (v < t) if below else (v >= t)
+        ox, oy, oz = o | nxt(o, 2), o | nxt(o, 1), o | nxt(o, 0)
+        oyz, oxz, oxy = oy | nxt(oy, 0), ox | nxt(ox, 0), ox | nxt(ox, 1)
+        oxyz = oxy | nxt(oxy, 0)
+        out[l] = (o.sum(), ox.sum() + oy.sum() + oz.sum(), oyz.sum() + oxz.sum() + oxy.sum(), oxyz.sum())
+    return out
+
+
+def minkowski_functionals(counts):
+    """[..., 4] int64: V = N3, S = -6 N3 + 2 N2, 2B = 3 N3 - 2 N2 + N1, chi = -N3 + N2 - N1 + N0 of counts[..., 4]
+    (N3, N2, N1, N0): the volume in cells, the area in cell faces, twice the mean breadth in cell edges and the Euler
+    characteristic."""
+    c = np.asarray(counts)
+    if c.ndim < 1 or c.shape[-1] != 4 or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError(f"minkowski_functionals: integer counts [..., 4], got shape {c.shape} of {c.dtype}")
+    c = c.astype(np.int64)
+    n3, n2, n1, n0 = (c[..., k] for k in range(4))
+    return np.stack([n3, -6 * n3 + 2 * n2, 3 * n3 - 2 * n2 + n1, -n3 + n2 - n1 + n0], axis=-1)
+
+
+def morphology_length(counts, nsites):
+    """[...]: nsites / S of counts[..., 4], the real-space domain size L = V_box / S; NaN where S = 0."""
+    s = minkowski_functionals(counts)[..., 1].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(s != 0, float(nsites) / s, np.nan)
+
+
 PRESSURE_VARIABLES = ["rho", "phi", "afx", "afy", "afz", "agx", "agy", "agz"]
 PRESSURE_PAIRS = [("rho", "phi"), ("afx", "agx"), ("afy", "agy"), ("afz", "agz")]
 

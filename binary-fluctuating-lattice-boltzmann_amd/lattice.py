@@ -640,6 +640,62 @@ class HistogramTrace(_FieldRecorder):
             return h / (h.sum(axis=-1, keepdims=True) * width)
 
 
+MORPH_SIDES = {"above": 0, "below": 1}
+
+
+class MorphologyTrace(_FieldRecorder):
+    """The Minkowski functionals of the set {v >= level} (side "above") or {v < level} (side "below") of one hydrovs /
+    hydrovsbar variable at 1 to 8 levels, for every replica, recorded on the device as 64-bit integer counts of cubes,
+    faces, edges and vertices every `every` steps through the owner (a lone single-slab BinaryLBM or a BatchLBM; no
+    rings) and read once: include/bflbm.h, "Morphology traces"; analysis.minkowski_counts is the same rule in numpy.
+    Made by owner.morphology_trace(); an owner may carry several (rho and phi, or both sides).  Closing the owner
+    detaches the trace: it stays readable until its own close()."""
+    _abi, _label = "bflbm_morph", "morphology_trace"
+    _geometry_types = (ctypes.c_int,) * 5
+    _alias = FieldStats._alias
+
+    def __init__(self, owner, create, variable, levels, side, source, every, capacity):
+        if side not in MORPH_SIDES and side not in MORPH_SIDES.values():
+            raise ValueError(f"morphology_trace: side {side!r}, expected 'above' (0) or 'below' (1)")
+        if not isinstance(variable, (str, int, np.integer)):
+            raise ValueError(f"morphology_trace: one variable by name or component index, got {variable!r}")
+        self._select(source, variable)
+        self.side = int(MORPH_SIDES.get(side, side))
+        self.levels = np.atleast_1d(np.asarray(levels, dtype=np.float64)).copy()
+        if self.levels.ndim != 1:
+            raise ValueError(f"morphology_trace: levels is a number or a list of 1..8 numbers, got shape {self.levels.shape}")
+        lv = self.levels if len(self.levels) else np.zeros(1)
+        super().__init__(owner, create, self.source, self.variables[0], len(self.levels), _ptr(lv), self.side, int(every), int(capacity))
+        self.sites = owner.n[0] * owner.n[1] * owner.n[2]
+
+    names = property(_FieldRecorder._recorded_names, doc="The recorded variable by name, a list of one.")
+
+    def geometry(self):
+        """(levels, plane sites of a work item's tile, its planes Zc, work items per replica, workgroups of the counting
+        launch over all replicas): what the library built."""
+        return self._geometry()
+
+    def read(self, first=0, count=None):
+        """(steps[count, B] int64, counts[count, B, nlevels, 4] int64: N3, N2, N1, N0, the cubes, faces, edges and
+        vertices) of the samples first ... first + count - 1 (count None: all from `first`); synchronises the owner's
+        stream."""
+        first, count, b, steps = self._window(first, count)
+        counts = np.empty((max(count, 0), b, len(self.levels), 4), dtype=np.int64)
+        as_ll = ctypes.POINTER(ctypes.c_longlong)
+        check(self.lib.bflbm_morph_read(self._h, first, count, counts.ctypes.data_as(as_ll), steps.ctypes.data_as(as_ll)))
+        return steps, counts
+
+    def functionals(self, first=0, count=None):
+        """[count, B, nlevels, 4] int64: V, S, 2B, chi (analysis.minkowski_functionals of the counts)."""
+        from . import analysis
+        return analysis.minkowski_functionals(self.read(first, count)[1])
+
+    def length(self, first=0, count=None):
+        """[count, B, nlevels]: the real-space domain size nsites / S (analysis.morphology_length), NaN where S = 0."""
+        from . import analysis
+        return analysis.morphology_length(self.read(first, count)[1], self.sites)
+
+
 class RadialTrace(_FieldRecorder):
     """The sums of chosen hydrovs / hydrovsbar variables, of chosen products of them and of chosen projections onto the
     outward radial unit vector over the shells of width `delta` about a droplet's centre (a fixed one, or the centre of
@@ -957,6 +1013,13 @@ class BinaryLBM(_DropletMixin):
         device every `every` steps: ranges = {variable: (lo, hi, nbins)} of up to 8 variables of `source` ("hydrovs",
         "hydrovsbar" or "noise"), up to 4 pairs (a, b) of them by name or slot: HistogramTrace."""
         return HistogramTrace(self, "bflbm_hist_create", ranges, pairs, source, every, capacity)
+
+    def morphology_trace(self, variable, levels, side="above", source="hydrovs", every=1, capacity=64):
+        """Record, after every `every`-th step, the cubes, faces, edges and vertices of the set {variable >= level}
+        (side "above") or {variable < level} (side "below") at 1 to 8 levels, one variable of `source` ("hydrovs" or
+        "hydrovsbar") by name or component index: MorphologyTrace, whose functionals() are the volume, the interface
+        area, twice the mean breadth and the Euler characteristic."""
+        return MorphologyTrace(self, "bflbm_morph_create", variable, levels, side, source, every, capacity)
 
     def radial_trace(self, variables, pairs=(), radials=(), centre=None, threshold=None, delta=1.0, nbins=None, source="hydrovs",
                      every=1, capacity=64):
@@ -1367,6 +1430,12 @@ class BatchLBM:
         """Every replica's bin counts (BinaryLBM.histogram_trace) after every `every`-th batch step, with one counting
         launch over all replicas; the noise source is not available on a batch."""
         return HistogramTrace(self, "bflbm_batch_hist_create", ranges, pairs, source, every, capacity)
+
+    def morphology_trace(self, variable, levels, side="above", source="hydrovs", every=1, capacity=64):
+        """Every replica's cubes, faces, edges and vertices of a thresholded variable (BinaryLBM.morphology_trace) after
+        every `every`-th batch step, with one observation launch, one counting launch over all replicas and one finishing
+        launch per sample."""
+        return MorphologyTrace(self, "bflbm_batch_morph_create", variable, levels, side, source, every, capacity)
 
     def radial_trace(self, variables, pairs=(), radials=(), centre=None, threshold=None, delta=1.0, nbins=None, source="hydrovs",
                      every=1, capacity=64):

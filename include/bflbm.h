@@ -912,6 +912,84 @@ int bflbm_hist_read(bflbm_hist* t, long long first, long long count,
                     long long* counts /* [count][nreplicas][C] */,
                     long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
 
+/* ---- Morphology traces: the four Minkowski functionals (volume, interface area, mean breadth, Euler characteristic) of
+ * a thresholded field, recorded on the device as a time series of 64-bit integer counts and read once at the end.  Every
+ * other recorder records a sum, a spectrum, a height, a radius or a distribution; this one records the shape of the
+ * domains: the interface area S(t) of a coarsening mixture and with it the real-space domain size L = V_box / S, the Euler
+ * characteristic chi(t), strongly negative for a bicontinuous sponge and positive once it has broken into droplets, and
+ * the number of droplets, which for simply connected droplets is chi itself (has a satellite pinched off, per replica of
+ * a batch).  On a lattice these are sums of integer counts over 2 x 2 x 2 neighbourhoods (Michielsen and De Raedt's
+ * counting on the cubical complex).  A morphology trace is attached to one lone single-slab context or one replica batch.
+ *  - definition (stated here and nowhere else).  Inputs: a source (0: hydrovs, 22 components; 1: hydrovsbar, 9
+ *    components), one component index v of that source, nlevels in 1..8 finite levels t_l and a side.  Side 0 occupies
+ *    the site (x, y, z) at level l when v[z][y][x] >= t_l, side 1 when v[z][y][x] < t_l (IEEE double comparisons: a NaN
+ *    occupies nothing on either side, -0.0 equals +0.0).  Let o(x, y, z) in {0, 1} be the occupancy at one level and `+`
+ *    on a coordinate its periodic successor (n - 1 -> 0; an extent of 1 is its own successor).  Every site adds
+ *      N3 += o(x,y,z)
+ *      N2 += [o(x,y,z) | o(x+,y,z)] + [o(x,y,z) | o(x,y+,z)] + [o(x,y,z) | o(x,y,z+)]
+ *      N1 += [OR of o over the 2 x 2 block (y,y+) x (z,z+) at x] + [the same over (x,x+) x (z,z+) at y]
+ *            + [the same over (x,x+) x (y,y+) at z]               the edges along x, y and z
+ *      N0 += [OR of o over the 2 x 2 x 2 block (x,x+) x (y,y+) x (z,z+)]
+ *    These are the cubes, faces, edges and vertices of the union of the closed unit voxels of the occupied sites on the
+ *    3-torus, each element counted once; the rule holds for extents 1 and 2 as it stands.  Closed voxels: the set is
+ *    26-connected, its complement 6-connected.  From the counts
+ *      V = N3          S = -6 N3 + 2 N2          2B = 3 N3 - 2 N2 + N1          chi = -N3 + N2 - N1 + N0
+ *    (volume in cells, area in cell faces, twice the mean breadth in cell edges, the Euler characteristic).  An a x b x c
+ *    cuboid gives (abc, 2(ab + bc + ca), a + b + c, 1), the full box (nx ny nz, 0, 0, 0).
+ *    analysis.minkowski_counts restates the rule in numpy, analysis.minkowski_functionals the four lines above.
+ *  - sample: [replica][nlevels][4] 64-bit signed counts, N3, N2, N1, N0 per level in the order of the levels.  The sums
+ *    are of integers: a record does not depend on the number of replicas, `every`, the capacity, the schedule, what else
+ *    is attached, lone context versus replica, or the launch geometry.
+ *  - bflbm_morph_geometry reports nlevels, the plane sites of a work item's tile (1024), its planes Zc, the work items
+ *    per replica (tiles per plane x chunks of Zc planes) and the workgroups of the counting launch over all replicas
+ *    (one work item each: the launch does not stride).
+ *  - how a sample is taken, on the owner's stream and without a host synchronisation: the accumulators' observation of
+ *    the one variable, exactly as the histogram trace takes it; ONE counting launch, compiled once per number of levels
+ *    (the 4 nlevels counters of a wave live in scalar registers, which only static indices reach), grid (work items, 1,
+ *    replicas) of 256 threads: a work item is a tile of 1024 consecutive plane sites p = y nx + x times a chunk of Zc
+ *    planes; a thread marches four sites along z, per plane loads each site's value and those of its x+, y+ and x+y+
+ *    neighbours (cached re-loads; the wraps inside the row and inside the plane are offsets computed once), forms the
+ *    8-bit level mask of every value and the OR-masks of the (x,x+), (y,y+) and (x,x+,y,y+) neighbourhoods, keeps those
+ *    of the previous plane in one register, so that a cell between the planes z and z+ costs one new plane, and the last
+ *    chunk's z+ wraps to plane 0; per level and counter one population count of a wave ballot is added into a
+ *    wave-uniform 32-bit counter (integers only, no per-lane counters, no cross-lane reduction); after the march one LDS
+ *    add per wave and counter and one global 64-bit integer add per non-zero counter and workgroup into the replica's
+ *    totals.  A workgroup meets 1024 Zc <= 65536 cells and a cell adds at most 3 to a counter, so no 32-bit counter can
+ *    wrap.  Zc is the largest of 64, 32, 16, 8 that leaves 1024 work items over all replicas, else 8, and at most nz (an
+ *    untimed heuristic, like the tile).  Expected memory traffic: 8 (Zc + 1) / Zc bytes per site plus a tile's one-row
+ *    halo, 8 nx / 1024 bytes per site.  Then ONE finishing launch, the histogram trace's, writes the totals straight
+ *    into the slot [sample][replica][nlevels][4] and sets them back to zero.  No scratch, 128 bytes of static LDS.
+ *  - no ring: a cell crosses the slab boundary and needs the next slab's first observed plane, which no slab of a ring
+ *    holds.  There is no bflbm_ring_morph_create (the interface trace's exclusion).
+ *  - what is touched on the owner: what the histogram trace's observation touches.  Observing hydrovs rewrites rho / phi
+ *    by the density pass where they are stale; a context's scratch state buffer is overwritten.  The resident state, the
+ *    step counters and everything the owner computes are unchanged.
+ *  - sampling rule, capacity, step labels, order among the recorders of one owner: those of the other traces
+ *    ("morphology trace full").  An owner may carry any number of morphology traces: rho and phi, or both sides.
+ *  - refused at creation (non-zero return, a message naming the call, before any launch, nothing allocated, the owner's
+ *    recorder list untouched): null arguments (before any device is touched), nlevels outside 1..8, a non-finite level, a
+ *    side other than 0 or 1, a source outside 0..1, a component index outside its source, every < 1, capacity < 1, a
+ *    capacity beyond 1 TB of records, a plane of more than 2^30 sites, a replica view (use bflbm_batch_morph_create), a
+ *    context with nranks > 1, an open step, a failed allocation (the message gives the bytes of each buffer).  An open
+ *    step also refuses bflbm_morph_sample, _reset and _read.
+ *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_morph_read, _count,
+ *    _geometry and _destroy still work, bflbm_morph_sample fails.  bflbm_morph_destroy(NULL) returns 0.
+ *  - only bflbm_morph_read and bflbm_morph_destroy synchronise the owner's stream. */
+typedef struct bflbm_morph bflbm_morph;
+int bflbm_morph_create(bflbm_ctx* c, int source, int var, int nlevels, const double* levels /* [nlevels] */, int side,
+                       int every, long long capacity, bflbm_morph** out);
+int bflbm_batch_morph_create(bflbm_batch* b, int source, int var, int nlevels, const double* levels, int side,
+                             int every, long long capacity, bflbm_morph** out);
+int bflbm_morph_destroy(bflbm_morph* t);
+int bflbm_morph_sample(bflbm_morph* t);                    /* record the resident state now (e.g. frame 0) */
+int bflbm_morph_reset(bflbm_morph* t);                     /* forget the samples, restart the every-counter */
+int bflbm_morph_count(const bflbm_morph* t, long long* nsamples, int* nreplicas);
+int bflbm_morph_geometry(const bflbm_morph* t, int* nlevels, int* tile_sites, int* chunk_planes /* Zc */,
+                         int* items /* work items per replica */, int* groups /* workgroups over all replicas */);
+int bflbm_morph_read(bflbm_morph* t, long long first, long long count,
+                     long long* counts /* [count][nreplicas][nlevels][4] */,
+                     long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
+
 /* ---- Radial traces: the sums of chosen fields, of chosen products of them and of chosen projections onto the outward
  * radial unit vector, over the shells of width delta about a droplet's centre, recorded on the device as a time series
  * and read once at the end.  Surface_Tension.ipynb's droplet route needs, per droplet, the pressure inside and outside
