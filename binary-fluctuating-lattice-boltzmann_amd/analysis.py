@@ -620,6 +620,89 @@ def morphology_length(counts, nsites):
         return np.where(s != 0, float(nsites) / s, np.nan)
 
 
+# ---- clusters: the numpy restatement of the cluster trace (include/bflbm.h, "Cluster traces") ----
+CLUSTER_WORDS = 38
+CLUSTER_CONNECTIVITIES = (6, 26)
+
+
+def _cluster_occupancy(call, field_zyx, levels, side, connectivity):
+    v = np.asarray(field_zyx, dtype=np.float64)
+    lv = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if v.ndim != 3 or v.size == 0:
+        raise ValueError(f"{call}: a field [nz, ny, nx], got shape {v.shape}")
+    if v.size > 2 ** 31 - 1:
+        raise ValueError(f"{call}: {v.size} sites exceed 2^31 - 1 (labels are 32-bit)")
+    if lv.ndim != 1 or not (1 <= len(lv) <= MORPH_MAX_LEVELS):
+        raise ValueError(f"{call}: 1..{MORPH_MAX_LEVELS} levels (got shape {lv.shape})")
+    if not np.isfinite(lv).all():
+        raise ValueError(f"{call}: the levels must be finite (got {lv.tolist()})")
+    if side not in MORPH_SIDES and side not in MORPH_SIDES.values():
+        raise ValueError(f"{call}: side {side!r}, expected 'above' (0) or 'below' (1)")
+    if connectivity not in CLUSTER_CONNECTIVITIES:
+        raise ValueError(f"{call}: connectivity must be 6 or 26 (got {connectivity!r})")
+    below = bool(MORPH_SIDES.get(side, side))
+    with np.errstate(invalid="ignore"):
+        return [(v < t) if below else (v >= t) for t in lv]
+
+
+def _cluster_label_set(occ, connectivity):
+    """Canonical labels of a boolean set: every occupied site starts with its own index and takes the minimum over its
+    periodic neighbours until nothing changes; between the sweeps a site jumps to its label's label, which is a site of
+    its own component with a label no larger, so long chains close in a logarithmic number of sweeps."""
+    nz, ny, nx = occ.shape
+    none = np.int64(occ.size)
+    lab = np.where(occ, np.arange(occ.size, dtype=np.int64).reshape(occ.shape), none)
+    offsets = [(dz, dy, dx) for dz in (-1, 0, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1)
+               if (dz, dy, dx) != (0, 0, 0) and (connectivity == 26 or abs(dz) + abs(dy) + abs(dx) == 1)]
+    while True:
+        new = lab
+        for d in offsets:
+            new = np.minimum(new, np.roll(lab, d, axis=(0, 1, 2)))
+        new = np.where(occ, new, none)
+        flat = np.append(new.ravel(), none)                # the label of "none" is "none"
+        new = np.where(occ, flat[flat[new]], none)         # two jumps
+        if np.array_equal(new, lab):
+            break
+        lab = new
+    return np.where(occ, lab, -1).astype(np.int32)
+
+
+def cluster_labels(field_zyx, level, side="above", connectivity=26):
+    """labels[nz, ny, nx] int32 of include/bflbm.h, "Cluster traces", in numpy: the smallest linear index
+    p = (z ny + y) nx + x of the component of every site with field >= level (side "above" or 0) or field < level (side
+    "below" or 1) on the periodic box, -1 where the site is unoccupied; connectivity 6 (faces) or 26 (faces, edges and
+    corners).  A NaN occupies nothing on either side."""
+    lv = np.asarray(level, dtype=np.float64)
+    if lv.ndim != 0:
+        raise ValueError(f"cluster_labels: one level (got shape {lv.shape})")
+    return _cluster_label_set(_cluster_occupancy("cluster_labels", field_zyx, [float(lv)], side, connectivity)[0], connectivity)
+
+
+def cluster_sizes(labels):
+    """(roots, sizes): the canonical labels that occur in labels[...] (ascending) and how many sites carry each."""
+    lab = np.asarray(labels)
+    if not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"cluster_sizes: integer labels, got {lab.dtype}")
+    roots, sizes = np.unique(lab[lab >= 0], return_counts=True)
+    return roots.astype(np.int64), sizes.astype(np.int64)
+
+
+def cluster_record(field_zyx, levels, side="above", connectivity=26):
+    """record[nlevels, 38] int64 of include/bflbm.h, "Cluster traces", in numpy: ncomp, V, smax, the label of the
+    largest component (among equals the smallest; -1 if none), the sum of s^2, 0 (capped) and the 32 counts of the
+    components with 2^b <= s < 2^(b+1)."""
+    out = np.zeros((len(np.atleast_1d(levels)), CLUSTER_WORDS), dtype=np.int64)
+    for l, occ in enumerate(_cluster_occupancy("cluster_record", field_zyx, levels, side, connectivity)):
+        roots, sizes = cluster_sizes(_cluster_label_set(occ, connectivity))
+        out[l, 0], out[l, 1], out[l, 3] = len(roots), sizes.sum(), -1
+        if len(roots):
+            out[l, 2] = sizes.max()
+            out[l, 3] = roots[np.argmax(sizes)]            # the first of the largest: roots ascend
+            out[l, 4] = (sizes * sizes).sum()
+            out[l, 6:] = np.bincount(np.floor(np.log2(sizes)).astype(np.int64), minlength=32)
+    return out
+
+
 PRESSURE_VARIABLES = ["rho", "phi", "afx", "afy", "afz", "agx", "agy", "agz"]
 PRESSURE_PAIRS = [("rho", "phi"), ("afx", "agx"), ("afy", "agy"), ("afz", "agz")]
 

@@ -696,6 +696,84 @@ class MorphologyTrace(_FieldRecorder):
         return analysis.morphology_length(self.read(first, count)[1], self.sites)
 
 
+class ClusterTrace(_FieldRecorder):
+    """The connected components of the set {v >= level} (side "above") or {v < level} (side "below") of one hydrovs /
+    hydrovsbar variable at 1 to 8 levels under 6- or 26-connectivity on the periodic box, for every replica, labelled on
+    the device by a union-find and recorded as 38 64-bit integers per level every `every` steps through the owner (a lone
+    single-slab BinaryLBM or a BatchLBM; no rings) and read once: include/bflbm.h, "Cluster traces";
+    analysis.cluster_record and analysis.cluster_labels are the same rule in numpy.  Made by owner.cluster_trace(); an
+    owner may carry several.  Closing the owner detaches the trace: it stays readable until its own close()."""
+    _abi, _label = "bflbm_cluster", "cluster_trace"
+    _geometry_types = (ctypes.c_int,) * 7
+    _alias = FieldStats._alias
+
+    def __init__(self, owner, create, variable, levels, side, connectivity, source, every, capacity):
+        if side not in MORPH_SIDES and side not in MORPH_SIDES.values():
+            raise ValueError(f"cluster_trace: side {side!r}, expected 'above' (0) or 'below' (1)")
+        if connectivity not in (6, 26):
+            raise ValueError(f"cluster_trace: connectivity must be 6 or 26 (got {connectivity!r})")
+        if not isinstance(variable, (str, int, np.integer)):
+            raise ValueError(f"cluster_trace: one variable by name or component index, got {variable!r}")
+        self._select(source, variable)
+        self.side, self.connectivity = int(MORPH_SIDES.get(side, side)), int(connectivity)
+        self.levels = np.atleast_1d(np.asarray(levels, dtype=np.float64)).copy()
+        if self.levels.ndim != 1:
+            raise ValueError(f"cluster_trace: levels is a number or a list of 1..8 numbers, got shape {self.levels.shape}")
+        lv = self.levels if len(self.levels) else np.zeros(1)
+        super().__init__(owner, create, self.source, self.variables[0], len(self.levels), _ptr(lv), self.side, self.connectivity,
+                         int(every), int(capacity))
+        self.n = tuple(owner.n)
+
+    names = property(_FieldRecorder._recorded_names, doc="The recorded variable by name, a list of one.")
+
+    def geometry(self):
+        """(levels, connectivity, the brick's extents along x, y, z, bricks per replica, launches per level): what the
+        library built."""
+        return self._geometry()
+
+    def read(self, first=0, count=None):
+        """(steps[count, B] int64, record[count, B, nlevels, 38] int64: ncomp, V, smax, the largest component's label,
+        the sum of s^2, capped and the 32 bins of sizes in powers of two) of the samples first ... first + count - 1
+        (count None: all from `first`); synchronises the owner's stream.  Raises BflbmError where a device loop hit its
+        iteration cap (word 5 is not zero): such a record is not to be trusted."""
+        first, count, b, steps = self._window(first, count)
+        record = np.empty((max(count, 0), b, len(self.levels), 38), dtype=np.int64)
+        as_ll = ctypes.POINTER(ctypes.c_longlong)
+        check(self.lib.bflbm_cluster_read(self._h, first, count, record.ctypes.data_as(as_ll), steps.ctypes.data_as(as_ll)))
+        if record[..., 5].any():
+            raise _lib.BflbmError(f"cluster_trace: {int(record[..., 5].sum())} device loops hit their iteration cap")
+        return steps, record
+
+    def components(self, first=0, count=None):
+        """[count, B, nlevels] int64: the number of components."""
+        return self.read(first, count)[1][..., 0]
+
+    def largest(self, first=0, count=None):
+        """(smax[count, B, nlevels], label[count, B, nlevels]) int64: the size of the largest component and its label
+        (0 and -1 where there is none)."""
+        rec = self.read(first, count)[1]
+        return rec[..., 2], rec[..., 3]
+
+    def size_histogram(self, first=0, count=None):
+        """[count, B, nlevels, 32] int64: the components with 2^b <= s < 2^(b+1)."""
+        return self.read(first, count)[1][..., 6:]
+
+    def mean_sizes(self, first=0, count=None):
+        """(number average V / ncomp, weight average sum s^2 / V), each [count, B, nlevels]; NaN where there is no
+        component."""
+        rec = self.read(first, count)[1].astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (np.where(rec[..., 0] > 0, rec[..., 1] / rec[..., 0], np.nan), np.where(rec[..., 1] > 0, rec[..., 4] / rec[..., 1], np.nan))
+
+    def labels(self, level_index=0):
+        """[B, nz, ny, nx] int32: the canonical labels of the owner's resident state now at one level (the smallest linear
+        index of a site's component, -1 where unoccupied); records no sample; synchronises the owner's stream."""
+        b = self._count()[1]
+        out = np.empty((b, self.n[2], self.n[1], self.n[0]), dtype=np.int32)
+        check(self.lib.bflbm_cluster_labels(self._h, int(level_index), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return out
+
+
 class RadialTrace(_FieldRecorder):
     """The sums of chosen hydrovs / hydrovsbar variables, of chosen products of them and of chosen projections onto the
     outward radial unit vector over the shells of width `delta` about a droplet's centre (a fixed one, or the centre of
@@ -1020,6 +1098,13 @@ class BinaryLBM(_DropletMixin):
         "hydrovsbar") by name or component index: MorphologyTrace, whose functionals() are the volume, the interface
         area, twice the mean breadth and the Euler characteristic."""
         return MorphologyTrace(self, "bflbm_morph_create", variable, levels, side, source, every, capacity)
+
+    def cluster_trace(self, variable, levels, side="above", connectivity=26, source="hydrovs", every=1, capacity=64):
+        """Record, after every `every`-th step, the connected components of the set {variable >= level} (side "above") or
+        {variable < level} (side "below") at 1 to 8 levels under 6- or 26-connectivity, one variable of `source`
+        ("hydrovs" or "hydrovsbar") by name or component index: ClusterTrace, whose record holds the number of components,
+        the largest, the sum of the squared sizes and a histogram of the sizes, and whose labels() are the components."""
+        return ClusterTrace(self, "bflbm_cluster_create", variable, levels, side, connectivity, source, every, capacity)
 
     def radial_trace(self, variables, pairs=(), radials=(), centre=None, threshold=None, delta=1.0, nbins=None, source="hydrovs",
                      every=1, capacity=64):
@@ -1436,6 +1521,12 @@ class BatchLBM:
         every `every`-th batch step, with one observation launch, one counting launch over all replicas and one finishing
         launch per sample."""
         return MorphologyTrace(self, "bflbm_batch_morph_create", variable, levels, side, source, every, capacity)
+
+    def cluster_trace(self, variable, levels, side="above", connectivity=26, source="hydrovs", every=1, capacity=64):
+        """Every replica's connected components of a thresholded variable (BinaryLBM.cluster_trace) after every `every`-th
+        batch step, with one observation launch, four launches per level over all replicas and one finishing launch per
+        sample."""
+        return ClusterTrace(self, "bflbm_batch_cluster_create", variable, levels, side, connectivity, source, every, capacity)
 
     def radial_trace(self, variables, pairs=(), radials=(), centre=None, threshold=None, delta=1.0, nbins=None, source="hydrovs",
                      every=1, capacity=64):

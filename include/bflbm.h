@@ -990,6 +990,97 @@ int bflbm_morph_read(bflbm_morph* t, long long first, long long count,
                      long long* counts /* [count][nreplicas][nlevels][4] */,
                      long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
 
+/* ---- Cluster traces: the connected components of a thresholded field, labelled on the device by a union-find over the
+ * lattice and recorded as a time series of 64-bit integers, read once at the end.  The morphology trace answers "how many
+ * domains" only through chi, which is the count only while no domain has a tunnel or a cavity, and never gives a size.
+ * This one records the number of components, the size of the largest, the sum of the squared sizes and a histogram of the
+ * sizes in powers of two: the droplet-size distribution of an off-critical quench, the mass fraction of the largest domain
+ * (the order parameter of the bicontinuous-to-droplet transition), a satellite that has pinched off in one replica of a
+ * batch; bflbm_cluster_labels hands out which sites belong to which component.  A cluster trace is attached to one lone
+ * single-slab context or one replica batch.
+ *  - definition (stated here and nowhere else).  Inputs: a source (0: hydrovs, 22 components; 1: hydrovsbar, 9
+ *    components), one component index v of that source, nlevels in 1..8 finite levels t_l, a side with the morphology
+ *    trace's semantics (side 0 occupies the site (x, y, z) at level l when v[z][y][x] >= t_l, side 1 when v[z][y][x] < t_l;
+ *    IEEE double comparisons: a NaN occupies nothing on either side, -0.0 equals +0.0) and a connectivity, 6 (faces) or 26
+ *    (faces, edges and corners: the closed-voxel union of the morphology trace, so that for tunnel-free domains
+ *    ncomp == chi).  Links: two occupied sites are linked where one is the periodic neighbour of the other along one of
+ *    the 3 (connectivity 6) or 13 (connectivity 26) forward directions (dx, dy, dz) in {-1, 0, 1}^3 with (dz, dy, dx)
+ *    lexicographically positive, coordinates modulo the extents.  This holds on extents 1 and 2 as it stands: a site that
+ *    is its own neighbour, or whose + and - neighbours coincide, neither creates nor removes a component.  A component is a
+ *    class of the transitive closure of the links.  The canonical label of an occupied site is the smallest linear index
+ *    p = (z ny + y) nx + x of its component, the label of an unoccupied site -1.  Labels are 32-bit: nx ny nz > 2^31 - 1 is
+ *    refused.  analysis.cluster_labels and analysis.cluster_record restate the rule in numpy.
+ *  - sample: [replica][nlevels][W] 64-bit signed integers with W = 38, per level in the order of the levels:
+ *      word 0        ncomp, the number of components
+ *      word 1        V, the number of occupied sites (the morphology trace's N3)
+ *      word 2        smax, the size of the largest component (0 if none)
+ *      word 3        the label of the largest component; among equals the smallest label; -1 if none
+ *      word 4        the sum of s^2 over the components (it fits: sum s^2 <= V^2 <= 2^62)
+ *      word 5        capped: device loops that hit their iteration cap (below); 0 in every correct run
+ *      word 6 + b    b = 0..31: the components with 2^b <= s < 2^(b+1)
+ *    All are integers: a record does not depend on the number of replicas, `every`, the capacity, the schedule, what else
+ *    is attached, lone context versus replica, or the launch geometry.
+ *  - how a sample is taken, on the owner's stream and without a host synchronisation: the accumulators' observation of
+ *    the one variable, exactly as the morphology trace takes it; then per level, one after another through the same two
+ *    32-bit arrays parent and size [replica][nsites], 4 launches: k_cluster_local, one workgroup of 256 threads per brick of
+ *    32 x 4 x 4 sites (an untimed heuristic), unites in LDS the links inside the brick that do not wrap and writes every
+ *    site's brick-local root and every local root's size; k_cluster_merge unites in global memory every link that crosses
+ *    a brick face or wraps (those of a brick with itself included) in the lock-free form: find both roots, an atomic
+ *    minimum of the larger root's parent with the smaller, go on from the value returned if that root had meanwhile been
+ *    linked; k_cluster_resolve lets every brick-local root find its global root and add its size to it, so that the adds
+ *    per component are the bricks it touches, not its sites; k_cluster_stats sums words 0, 1, 4 and the bins over the global
+ *    roots per wave and workgroup (one 64-bit global add per non-zero counter and workgroup) and takes words 2 and 3 as one
+ *    packed 64-bit maximum, (size << 32) | (0xffffffff - label).  Then ONE finishing launch, k_cluster_finish, writes the
+ *    totals of all levels into the slot, unpacks the maximum and clears the totals.  The phases are separated by launches:
+ *    no grid barrier, no persistent kernel.  A root is always the smallest index of its tree (parent[p] <= p throughout).
+ *    Inside the merge and resolve launches the parents are read with relaxed agent-scope atomic loads and written with
+ *    agent-scope atomic minima only: parents only decrease, a stale parent is an older ancestor of the same tree, and
+ *    every link is decided by the value an atomic returns (csrc/bflbm_cluster.h argues it in full).
+ *  - termination: a find follows strictly falling indices and a union replaces the larger site of its pair by a smaller
+ *    one, so both end within nsites turns; both loops carry nsites as a hard cap as well, and a loop that reaches it adds
+ *    one to word 5 and leaves: a defect shows as capped != 0, never as a hang.  No scratch; static LDS 4096 bytes
+ *    (k_cluster_local) and 152 bytes (k_cluster_stats).
+ *  - memory per trace: parent and size, 8 bytes per site and replica; a batch also the dense field, 8 bytes per site and
+ *    replica, as the morphology trace.
+ *  - bflbm_cluster_geometry reports nlevels, the connectivity, the brick extents (32, 4, 4), the bricks per replica and
+ *    the launches per level (4).
+ *  - bflbm_cluster_labels labels the owner's resident state now, for the level level_index: the observation, the local and
+ *    merge launches and one flatten launch that reads the parents only and writes every site's root into the size array;
+ *    it synchronises and writes the canonical labels [replica][nz][ny][nx] as 32-bit integers.  It records no sample and
+ *    leaves the trace's totals and every-count untouched.  Refused: null arguments, a level index outside the levels, a
+ *    detached trace, an open step, a loop that hit its cap.
+ *  - out of scope: rings (a link crosses the slab boundary and needs the next slab's parents; there is
+ *    no bflbm_ring_cluster_create, the morphology trace's exclusion), spanning or wrapping detection of a component,
+ *    per-component sums of a second variable, component tracking between samples, 18-connectivity, a noise source.
+ *  - what is touched on the owner: what the morphology trace's observation touches.
+ *  - sampling rule, capacity, step labels, order among the recorders of one owner: those of the other traces
+ *    ("cluster trace full").  An owner may carry any number of cluster traces.
+ *  - refused at creation (non-zero return, a message naming the call, before any launch, nothing allocated, the owner's
+ *    recorder list untouched): null arguments (before any device is touched), then the morphology trace's refusals in its
+ *    order and wording (nlevels outside 1..8, a non-finite level, a side other than 0 or 1, a source outside 0..1, a
+ *    component index outside its source), "connectivity must be 6 or 26 (got %d)", every < 1, capacity < 1, a replica view
+ *    (use bflbm_batch_cluster_create), a context with nranks > 1, an open step, more than 2^31 - 1 sites, a capacity beyond
+ *    1 TB of records, a failed allocation (the message gives the bytes of each buffer).  An open step also refuses
+ *    bflbm_cluster_sample, _reset, _read and _labels.
+ *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_cluster_read, _count,
+ *    _geometry and _destroy still work, bflbm_cluster_sample and _labels fail.  bflbm_cluster_destroy(NULL) returns 0.
+ *  - only bflbm_cluster_read, bflbm_cluster_labels and bflbm_cluster_destroy synchronise the owner's stream. */
+typedef struct bflbm_cluster bflbm_cluster;
+int bflbm_cluster_create(bflbm_ctx* c, int source, int var, int nlevels, const double* levels /* [nlevels] */, int side,
+                         int connectivity, int every, long long capacity, bflbm_cluster** out);
+int bflbm_batch_cluster_create(bflbm_batch* b, int source, int var, int nlevels, const double* levels, int side,
+                               int connectivity, int every, long long capacity, bflbm_cluster** out);
+int bflbm_cluster_destroy(bflbm_cluster* t);
+int bflbm_cluster_sample(bflbm_cluster* t);                /* record the resident state now (e.g. frame 0) */
+int bflbm_cluster_reset(bflbm_cluster* t);                 /* forget the samples, restart the every-counter */
+int bflbm_cluster_count(const bflbm_cluster* t, long long* nsamples, int* nreplicas);
+int bflbm_cluster_geometry(const bflbm_cluster* t, int* nlevels, int* connectivity, int* brick_x, int* brick_y, int* brick_z,
+                           int* bricks /* per replica */, int* launches /* per level */);
+int bflbm_cluster_read(bflbm_cluster* t, long long first, long long count,
+                       long long* counts /* [count][nreplicas][nlevels][38] */,
+                       long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
+int bflbm_cluster_labels(bflbm_cluster* t, int level_index, int* labels /* [nreplicas][nz][ny][nx] */);
+
 /* ---- Radial traces: the sums of chosen fields, of chosen products of them and of chosen projections onto the outward
  * radial unit vector, over the shells of width delta about a droplet's centre, recorded on the device as a time series
  * and read once at the end.  Surface_Tension.ipynb's droplet route needs, per droplet, the pressure inside and outside
