@@ -206,6 +206,14 @@ SIGNATURES = {
     "bflbm_cluster_geometry": (ctypes.c_int, [_vp] + [_P(ctypes.c_int)] * 7),
     "bflbm_cluster_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _P(ctypes.c_longlong), _P(ctypes.c_longlong)]),
     "bflbm_cluster_labels": (ctypes.c_int, [_vp, ctypes.c_int, _P(ctypes.c_int)]),
+    "bflbm_component_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_batch_component_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_component_destroy": (ctypes.c_int, [_vp]),
+    "bflbm_component_sample": (ctypes.c_int, [_vp]),
+    "bflbm_component_reset": (ctypes.c_int, [_vp]),
+    "bflbm_component_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
+    "bflbm_component_geometry": (ctypes.c_int, [_vp, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_longlong)] + [_P(ctypes.c_int)] * 4),
+    "bflbm_component_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _P(ctypes.c_longlong), _P(ctypes.c_longlong)]),
     "bflbm_radial_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
     "bflbm_batch_radial_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
     "bflbm_radial_destroy": (ctypes.c_int, [_vp]),

@@ -703,6 +703,140 @@ def cluster_record(field_zyx, levels, side="above", connectivity=26):
     return out
 
 
+# ---- components: the numpy restatement of the component trace (include/bflbm.h, "Component traces") ----
+COMPONENT_HEADER = 6
+COMPONENT_ROW = 18
+COMPONENT_MAX_ROWS = 256
+
+
+def component_table(field_zyx, levels, side="above", connectivity=26, min_size=1, rows=COMPONENT_MAX_ROWS):
+    """(header[nlevels, 6], table[nlevels, rows, 18]) int64 of include/bflbm.h, "Component traces", in numpy.  Header:
+    ncomp, V, nqual, Vqual, nrows, 0 (capped).  Row j, the qualifying component (size >= min_size) with j qualifying
+    components of smaller label: label, size, origin (x, y, z), extent, sum d, sum d^2, sum dx dy, dx dz, dy dz, faces,
+    with d = (c - origin) mod n; unused rows have label -1 and zeros elsewhere."""
+    occs = _cluster_occupancy("component_table", field_zyx, levels, side, connectivity)
+    _component_refuse("component_table", min_size, rows)
+    parts = [component_table_from_labels(_cluster_label_set(occ, connectivity), min_size, rows) for occ in occs]
+    return np.stack([h for h, _ in parts]), np.stack([t for _, t in parts])
+
+
+def _component_refuse(call, min_size, rows):
+    if int(min_size) != min_size or min_size < 1:
+        raise ValueError(f"{call}: min_size must be an integer >= 1 (got {min_size!r})")
+    if int(rows) != rows or not (1 <= rows <= COMPONENT_MAX_ROWS):
+        raise ValueError(f"{call}: rows must be in 1..{COMPONENT_MAX_ROWS} (got {rows!r})")
+
+
+def component_table_from_labels(labels_zyx, min_size=1, rows=COMPONENT_MAX_ROWS):
+    """(header[6], table[rows, 18]) int64 of one level from canonical labels[nz, ny, nx] (cluster_labels, or one replica
+    of ClusterTrace.labels()): what component_table makes of every level."""
+    lab = np.asarray(labels_zyx)
+    if lab.ndim != 3 or lab.size == 0 or not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"component_table_from_labels: integer labels [nz, ny, nx], got shape {lab.shape} of {lab.dtype}")
+    _component_refuse("component_table_from_labels", min_size, rows)
+    min_size, rows = int(min_size), int(rows)
+    nz, ny, nx = lab.shape
+    n = (nx, ny, nz)
+    occ = lab >= 0
+    header = np.zeros(COMPONENT_HEADER, dtype=np.int64)
+    t = np.zeros((rows, COMPONENT_ROW), dtype=np.int64)
+    t[:, 0] = -1
+    roots, sizes = cluster_sizes(lab)
+    qual = sizes >= min_size
+    nrows = min(int(qual.sum()), rows)
+    header[:] = (len(roots), sizes.sum(), qual.sum(), sizes[qual].sum(), nrows, 0)
+    if nrows == 0:
+        return header, t
+    kept = roots[qual][:nrows]
+    t[:nrows, 0], t[:nrows, 1] = kept, sizes[qual][:nrows]
+    p = np.flatnonzero(occ.ravel())
+    slot = np.searchsorted(kept, lab.ravel()[p])
+    inside = (slot < nrows) & (kept[np.minimum(slot, nrows - 1)] == lab.ravel()[p])
+    p, slot = p[inside], slot[inside]
+    c = (p % nx, (p // nx) % ny, p // (nx * ny))           # x, y, z
+    bare = sum((~np.roll(occ, s, axis=a)).astype(np.int64) for a in range(3) for s in (1, -1))   # unoccupied periodic neighbours
+    d = []
+    for a in range(3):
+        present = np.zeros((nrows, n[a]), dtype=bool)
+        present[slot, c[a]] = True
+        starts = present & ~np.roll(present, 1, axis=1)    # the predecessor is unoccupied
+        origin = np.where(starts.any(axis=1), starts.argmax(axis=1), 0).astype(np.int64)
+        t[:nrows, 2 + a], t[:nrows, 5 + a] = origin, present.sum(axis=1)
+        d.append((c[a] - origin[slot]) % n[a])
+    sums = list(d) + [v * v for v in d] + [d[0] * d[1], d[0] * d[2], d[1] * d[2], bare.ravel()[p]]
+    for w, v in enumerate(sums):
+        np.add.at(t[:, 8 + w], slot, v)                    # integer adds: exact
+    return header, t
+
+
+def component_centroids(table, n):
+    """[..., 3]: the centroids (x, y, z) in cell indices of table[..., 18] on the box n = (nx, ny, nz),
+    (origin + sum d / size) mod n; NaN along a spanned axis (extent == n: no unwrapping exists) and in unused rows."""
+    t = np.asarray(table)
+    n = np.asarray(n, dtype=np.float64)
+    size = t[..., 1:2].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        c = np.mod(t[..., 2:5] + t[..., 8:11] / size, n)
+    return np.where((t[..., 0:1] >= 0) & (t[..., 5:8] < n), c, np.nan)
+
+
+def component_gyration(table):
+    """[..., 3, 3] float64: the central second-moment tensor sum d_a d_b / size - (sum d_a / size)(sum d_b / size) of
+    table[..., 18], axes x, y, z; NaN in unused rows.  Along a spanned axis it is taken about coordinate 0."""
+    t = np.asarray(table)
+    size = np.where(t[..., 0] >= 0, t[..., 1], 0).astype(np.float64)[..., None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        m1 = t[..., 8:11] / size
+        d2, cross = t[..., 11:14] / size, t[..., 14:17] / size
+    g = np.empty(t.shape[:-1] + (3, 3))
+    for a in range(3):
+        g[..., a, a] = d2[..., a]
+    for k, (a, b) in enumerate(((0, 1), (0, 2), (1, 2))):
+        g[..., a, b] = g[..., b, a] = cross[..., k]
+    return g - m1[..., :, None] * m1[..., None, :]
+
+
+def track_components(centroids, sizes, n, max_jump):
+    """Unwrapped trajectories [ntracks, T, 3] from the rows of consecutive samples: centroids[T, R, 3] (NaN: no
+    position) and sizes[T, R] (0: unused row) of one replica and level on the periodic box n = (nx, ny, nz).  A
+    component's label, and with it its row, changes whenever it drifts across the box origin, so rows are linked by
+    position: between consecutive samples the pairs (track, row) within max_jump of each other by the minimum image are
+    taken greedily by ascending distance, ties by the smaller track, then the smaller row.  A row left over starts a new
+    track, a track left over ends.  NaN before birth and after loss: ready for msd per track."""
+    c = np.asarray(centroids, dtype=np.float64)
+    s = np.asarray(sizes)
+    n = np.asarray(n, dtype=np.float64)
+    if c.ndim != 3 or c.shape[-1] != 3 or s.shape != c.shape[:2]:
+        raise ValueError(f"track_components: centroids[T, R, 3] and sizes[T, R], got {c.shape} and {s.shape}")
+    if not max_jump > 0:
+        raise ValueError(f"track_components: max_jump must be > 0 (got {max_jump!r})")
+    steps = c.shape[0]
+    tracks, live = [], {}                                  # live: track index -> (wrapped, unwrapped) position
+    for t in range(steps):
+        rows = [r for r in range(c.shape[1]) if s[t, r] > 0 and np.isfinite(c[t, r]).all()]
+        pairs = []
+        for k, (wrapped, _) in live.items():
+            for r in rows:
+                step = np.mod(c[t, r] - wrapped + 0.5 * n, n) - 0.5 * n
+                dist = float(np.sqrt((step * step).sum()))
+                if dist <= max_jump:
+                    pairs.append((dist, k, r, step))
+        taken, new_live = set(), {}
+        for dist, k, r, step in sorted(pairs, key=lambda q: q[:3]):
+            if k in new_live or r in taken:
+                continue
+            taken.add(r)
+            new_live[k] = (c[t, r], live[k][1] + step)
+        for r in rows:
+            if r not in taken:
+                tracks.append(np.full((steps, 3), np.nan))
+                new_live[len(tracks) - 1] = (c[t, r], c[t, r].copy())
+        live = new_live
+        for k, (_, unwrapped) in live.items():
+            tracks[k][t] = unwrapped
+    return np.array(tracks).reshape(len(tracks), steps, 3)
+
+
 PRESSURE_VARIABLES = ["rho", "phi", "afx", "afy", "afz", "agx", "agy", "agz"]
 PRESSURE_PAIRS = [("rho", "phi"), ("afx", "agx"), ("afy", "agy"), ("afz", "agz")]
 

@@ -46,8 +46,10 @@
 // Expected traffic per site and level, derived: local 8 (field) + 8 (parent, size) bytes; merge 4 plus the neighbours'
 // parents of the 45 % (26) or 40 % (6) of sites on a forward brick face, through the caches; resolve 4 (size) and the
 // chains of the roots only; stats 8: about 32 bytes against the 608 of a step.  The brick is an untimed heuristic.
-// Out of scope: rings (a link crosses the slab boundary: no bflbm_ring_cluster_create), spanning or wrapping detection,
-// per-component sums of a second variable, tracking between samples, 18-connectivity, a noise source.
+// Out of scope: rings (a link crosses the slab boundary: no bflbm_ring_cluster_create), per-component sums of a second
+// variable, wrapping (winding) detection, tracking between samples on the device, 18-connectivity, a noise source.  Per
+// component size, origin, extent (spanning), integer moments and area are the component trace's (bflbm_components.h), which
+// calls cluster_label_level and cluster_resolve_level below.
 // Host part: plain C++17 on top of bflbm_morph.h's host part (the levels, the refusals).  A stand-alone program defines
 // BFLBM_CLUSTER_HOST_ONLY (and the MORPH and FIELDSEL ones) and includes it after bflbm_morph.h.  HIP part: the lifecycle
 // and the sample store are those of bflbm_recorder.h, the selection that of bflbm_fieldsel.h.  Included by bflbm.hip after
@@ -167,6 +169,10 @@ inline long long cluster_bricks(int nx, int ny, int nz) {
 #include <memory>
 #include <string>
 
+// What the launches of one level work on: a stream, the replicas' box and the two arrays.  The cluster trace and the
+// component trace (bflbm_components.h) both label through cluster_label_level and cluster_resolve_level.
+struct ClusterArrays { hipStream_t stream; int nrep; long long nsites; ClusterBox B; int* parent; int* size; };
+
 struct bflbm_cluster : bflbm_sample_store {  // d_rec [capacity][nrep][nlevels][38] as long long, d_stage: the totals and one word more
   ClusterBox B;
   long long nsites = 0;
@@ -185,6 +191,7 @@ struct bflbm_cluster : bflbm_sample_store {  // d_rec [capacity][nrep][nlevels][
   }
   unsigned long long* totals() const { return reinterpret_cast<unsigned long long*>(d_stage); }
   size_t words() const { return (size_t)nrep * L.n * cluster_limits::kWords; }   // the totals; the word after them: the caps of a labels call
+  ClusterArrays arrays() const { return ClusterArrays{recorder_stream(this), nrep, nsites, B, parent, size}; }
   int observe(const double** vol, long long* rep_stride);
   int label_level(const double* vol, long long rep_stride, int l, unsigned long long* capped, long long capped_stride);
   int record() override;
@@ -426,6 +433,26 @@ int cluster_create(bflbm_ctx* c, bflbm_batch* b, int source, int var, int nlevel
   return 0;
 }
 
+// the launches that leave the parents of one level united; `capped`: where replica r's loops count their caps, at capped + r capped_stride
+int cluster_label_level(const ClusterArrays& A, const double* vol, long long rep_stride, double level, int side, unsigned long long* capped,
+                        long long capped_stride) {
+  const dim3 per_site((unsigned)((A.nsites + 255) / 256), 1, (unsigned)A.nrep);
+  hipLaunchKernelGGL(k_cluster_local, dim3((unsigned)cluster_bricks(A.B.nx, A.B.ny, A.B.nz), 1, (unsigned)A.nrep), dim3(256), 0, A.stream, vol, rep_stride,
+                     A.B, level, side, A.parent, A.size, capped, capped_stride);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_cluster_merge, per_site, dim3(256), 0, A.stream, A.B, A.parent, capped, capped_stride);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// the launch after which a global root holds its component's size and every brick-local root points at its global root
+int cluster_resolve_level(const ClusterArrays& A, unsigned long long* capped, long long capped_stride) {
+  const dim3 per_site((unsigned)((A.nsites + 255) / 256), 1, (unsigned)A.nrep);
+  hipLaunchKernelGGL(k_cluster_resolve, per_site, dim3(256), 0, A.stream, A.nsites, A.parent, A.size, capped, capped_stride);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
 
 int bflbm_cluster::observe(const double** vol, long long* rep_stride) {
@@ -435,16 +462,9 @@ int bflbm_cluster::observe(const double** vol, long long* rep_stride) {
   return 0;
 }
 
-// the launches that leave the parents of level l united; `capped`: where replica r's loops count their caps, at capped + r capped_stride
+// level l of this trace through cluster_label_level
 int bflbm_cluster::label_level(const double* vol, long long rep_stride, int l, unsigned long long* capped, long long capped_stride) {
-  const hipStream_t stream = recorder_stream(this);
-  const dim3 per_site((unsigned)((nsites + 255) / 256), 1, (unsigned)nrep);
-  hipLaunchKernelGGL(k_cluster_local, dim3((unsigned)cluster_bricks(B.nx, B.ny, B.nz), 1, (unsigned)nrep), dim3(256), 0, stream, vol, rep_stride, B,
-                     L.t[l], L.side, parent, size, capped, capped_stride);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_cluster_merge, per_site, dim3(256), 0, stream, B, parent, capped, capped_stride);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return cluster_label_level(arrays(), vol, rep_stride, L.t[l], L.side, capped, capped_stride);
 }
 
 // enqueue the observation, the four launches per level and the finishing launch of the resident state into slot n
@@ -455,14 +475,12 @@ int bflbm_cluster::record() {
   const double* vol;
   long long rep_stride;
   if (observe(&vol, &rep_stride)) return 1;
-  const dim3 per_site((unsigned)((nsites + 255) / 256), 1, (unsigned)nrep);
   const dim3 per_stats((unsigned)((nsites + kStatsSites - 1) / kStatsSites), 1, (unsigned)nrep);
   const long long stride = (long long)L.n * kWords;
   for (int l = 0; l < L.n; ++l) {
     unsigned long long* level = totals() + (long long)l * kWords;
     if (label_level(vol, rep_stride, l, level + kCapped, stride)) return 1;
-    hipLaunchKernelGGL(k_cluster_resolve, per_site, dim3(256), 0, stream, nsites, parent, size, level + kCapped, stride);
-    HIP_TRY(hipGetLastError());
+    if (cluster_resolve_level(arrays(), level + kCapped, stride)) return 1;
     hipLaunchKernelGGL(k_cluster_stats, per_stats, dim3(256), 0, stream, nsites, (const int*)parent, (const int*)size, level, stride);
     HIP_TRY(hipGetLastError());
   }

@@ -774,6 +774,89 @@ class ClusterTrace(_FieldRecorder):
         return out
 
 
+class ComponentTrace(_FieldRecorder):
+    """Per connected component of the set {v >= level} (side "above") or {v < level} (side "below") of one hydrovs /
+    hydrovsbar variable at 1 to 8 levels (the cluster trace's components and labels): size, a periodic-safe origin, the
+    extent along every axis, the integer first and second moments about the origin and the area in cell faces of the
+    `rows` components of at least `min_size` sites with the smallest labels, for every replica, recorded on the device
+    as 64-bit integers every `every` steps through the owner (a lone single-slab BinaryLBM or a BatchLBM; no rings) and
+    read once: include/bflbm.h, "Component traces"; analysis.component_table is the same rule in numpy.  Made by
+    owner.component_trace(); an owner may carry several.  Closing the owner detaches the trace: it stays readable until
+    its own close()."""
+    _abi, _label = "bflbm_component", "component_trace"
+    _geometry_types = (ctypes.c_int, ctypes.c_int, ctypes.c_longlong) + (ctypes.c_int,) * 4
+    _alias = FieldStats._alias
+
+    def __init__(self, owner, create, variable, levels, side, connectivity, min_size, rows, source, every, capacity):
+        if side not in MORPH_SIDES and side not in MORPH_SIDES.values():
+            raise ValueError(f"component_trace: side {side!r}, expected 'above' (0) or 'below' (1)")
+        if connectivity not in (6, 26):
+            raise ValueError(f"component_trace: connectivity must be 6 or 26 (got {connectivity!r})")
+        if not isinstance(variable, (str, int, np.integer)):
+            raise ValueError(f"component_trace: one variable by name or component index, got {variable!r}")
+        self._select(source, variable)
+        self.side, self.connectivity = int(MORPH_SIDES.get(side, side)), int(connectivity)
+        self.min_size, self.rows = int(min_size), int(rows)
+        self.levels = np.atleast_1d(np.asarray(levels, dtype=np.float64)).copy()
+        if self.levels.ndim != 1:
+            raise ValueError(f"component_trace: levels is a number or a list of 1..8 numbers, got shape {self.levels.shape}")
+        lv = self.levels if len(self.levels) else np.zeros(1)
+        super().__init__(owner, create, self.source, self.variables[0], len(self.levels), _ptr(lv), self.side, self.connectivity,
+                         self.min_size, self.rows, int(every), int(capacity))
+        self.n = tuple(owner.n)
+
+    names = property(_FieldRecorder._recorded_names, doc="The recorded variable by name, a list of one.")
+
+    def geometry(self):
+        """(levels, connectivity, min_size, rows, header words, row words, launches per level): what the library built."""
+        return self._geometry()
+
+    def read(self, first=0, count=None):
+        """(steps[count, B] int64, header[count, B, nlevels, 6] int64: ncomp, V, nqual, Vqual, nrows, capped,
+        rows[count, B, nlevels, rows, 18] int64: label, size, origin, extent, sum d, sum d^2, sum dx dy, dx dz, dy dz,
+        faces) of the samples first ... first + count - 1 (count None: all from `first`); synchronises the owner's
+        stream.  Raises BflbmError where a device loop hit its iteration cap (header word 5 is not zero)."""
+        first, count, b, steps = self._window(first, count)
+        record = np.empty((max(count, 0), b, len(self.levels), 6 + self.rows * 18), dtype=np.int64)
+        as_ll = ctypes.POINTER(ctypes.c_longlong)
+        check(self.lib.bflbm_component_read(self._h, first, count, record.ctypes.data_as(as_ll), steps.ctypes.data_as(as_ll)))
+        if record[..., 5].any():
+            raise _lib.BflbmError(f"component_trace: {int(record[..., 5].sum())} device loops hit their iteration cap")
+        return steps, record[..., :6].copy(), record[..., 6:].reshape(record.shape[:3] + (self.rows, 18)).copy()
+
+    def _rows(self, first, count):
+        return self.read(first, count)[2]
+
+    def sizes(self, first=0, count=None):
+        """[count, B, nlevels, rows] int64: the sizes, 0 in unused rows."""
+        return self._rows(first, count)[..., 1]
+
+    def labels_of_rows(self, first=0, count=None):
+        """[count, B, nlevels, rows] int64: the canonical labels, -1 in unused rows."""
+        return self._rows(first, count)[..., 0]
+
+    def spans(self, first=0, count=None):
+        """[count, B, nlevels, rows, 3] bool: the component covers every coordinate of the axis (x, y, z): necessary for
+        wrapping around it, not sufficient.  False in unused rows."""
+        t = self._rows(first, count)
+        return (t[..., 0:1] >= 0) & (t[..., 5:8] == np.asarray(self.n))
+
+    def areas(self, first=0, count=None):
+        """[count, B, nlevels, rows] int64: the faces towards unoccupied sites."""
+        return self._rows(first, count)[..., 17]
+
+    def centroids(self, first=0, count=None):
+        """[count, B, nlevels, rows, 3]: the centroids (x, y, z) in cell indices, like Trace.com();
+        NaN along a spanned axis and in unused rows (analysis.component_centroids)."""
+        from . import analysis
+        return analysis.component_centroids(self._rows(first, count), self.n)
+
+    def gyration(self, first=0, count=None):
+        """[count, B, nlevels, rows, 3, 3] float64: the central second-moment tensors (analysis.component_gyration)."""
+        from . import analysis
+        return analysis.component_gyration(self._rows(first, count))
+
+
 class RadialTrace(_FieldRecorder):
     """The sums of chosen hydrovs / hydrovsbar variables, of chosen products of them and of chosen projections onto the
     outward radial unit vector over the shells of width `delta` about a droplet's centre (a fixed one, or the centre of
@@ -1105,6 +1188,12 @@ class BinaryLBM(_DropletMixin):
         ("hydrovs" or "hydrovsbar") by name or component index: ClusterTrace, whose record holds the number of components,
         the largest, the sum of the squared sizes and a histogram of the sizes, and whose labels() are the components."""
         return ClusterTrace(self, "bflbm_cluster_create", variable, levels, side, connectivity, source, every, capacity)
+
+    def component_trace(self, variable, levels, side="above", connectivity=26, min_size=1, rows=64, source="hydrovs", every=1, capacity=64):
+        """Record, after every `every`-th step, per connected component of the set {v >= level} (or {v < level}) of one variable
+        of `source` its place and shape (the components are cluster_trace's): ComponentTrace, whose record tabulates, per level, the `rows` components of at least `min_size` sites with
+        the smallest labels: size, origin, extent, integer moments and area of each."""
+        return ComponentTrace(self, "bflbm_component_create", variable, levels, side, connectivity, min_size, rows, source, every, capacity)
 
     def radial_trace(self, variables, pairs=(), radials=(), centre=None, threshold=None, delta=1.0, nbins=None, source="hydrovs",
                      every=1, capacity=64):
@@ -1527,6 +1616,11 @@ class BatchLBM:
         batch step, with one observation launch, four launches per level over all replicas and one finishing launch per
         sample."""
         return ClusterTrace(self, "bflbm_batch_cluster_create", variable, levels, side, connectivity, source, every, capacity)
+
+    def component_trace(self, variable, levels, side="above", connectivity=26, min_size=1, rows=64, source="hydrovs", every=1, capacity=64):
+        """Every replica's components one by one (BinaryLBM.component_trace) after every `every`-th batch step: ComponentTrace, whose record tabulates, per level, the `rows` components of at least `min_size` sites with
+        the smallest labels: size, origin, extent, integer moments and area of each."""
+        return ComponentTrace(self, "bflbm_batch_component_create", variable, levels, side, connectivity, min_size, rows, source, every, capacity)
 
     def radial_trace(self, variables, pairs=(), radials=(), centre=None, threshold=None, delta=1.0, nbins=None, source="hydrovs",
                      every=1, capacity=64):

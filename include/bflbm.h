@@ -1050,8 +1050,9 @@ int bflbm_morph_read(bflbm_morph* t, long long first, long long count,
  *    leaves the trace's totals and every-count untouched.  Refused: null arguments, a level index outside the levels, a
  *    detached trace, an open step, a loop that hit its cap.
  *  - out of scope: rings (a link crosses the slab boundary and needs the next slab's parents; there is
- *    no bflbm_ring_cluster_create, the morphology trace's exclusion), spanning or wrapping detection of a component,
- *    per-component sums of a second variable, component tracking between samples, 18-connectivity, a noise source.
+ *    no bflbm_ring_cluster_create, the morphology trace's exclusion), per-component sums of a second variable, wrapping
+ *    (winding) detection, component tracking on the device, 18-connectivity, a noise source.  Per-component size, origin,
+ *    extent (spanning), integer moments and area are the component trace's ("Component traces" below).
  *  - what is touched on the owner: what the morphology trace's observation touches.
  *  - sampling rule, capacity, step labels, order among the recorders of one owner: those of the other traces
  *    ("cluster trace full").  An owner may carry any number of cluster traces.
@@ -1080,6 +1081,107 @@ int bflbm_cluster_read(bflbm_cluster* t, long long first, long long count,
                        long long* counts /* [count][nreplicas][nlevels][38] */,
                        long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
 int bflbm_cluster_labels(bflbm_cluster* t, int level_index, int* labels /* [nreplicas][nz][ny][nx] */);
+
+/* ---- Component traces: per connected component of a thresholded field its size, where it is, how far it reaches along
+ * every axis, the integer first and second moments of its sites and its area, recorded on the device as a time series of
+ * 64-bit integers and read once at the end.  The cluster trace reduces the components to one record per level; the
+ * ensemble trace gives one centre for the whole box, which means nothing with two droplets in it.  This one tabulates
+ * the droplets of an off-critical quench or a many-droplet box: centroid, gyration tensor and interface area of each,
+ * whether a domain has reached across the box, and, through analysis.track_components, per-droplet trajectories for
+ * analysis.msd.  A component trace is attached to one lone single-slab context or one replica batch.
+ *  - definition (stated here and nowhere else).  Inputs: the cluster trace's (a source, one component index v, nlevels in
+ *    1..8 finite levels, a side, a connectivity 6 or 26, with its semantics), min_size >= 1 (64-bit) and rows in 1..256.
+ *    Per replica and level the components and their canonical labels are exactly the cluster trace's: the label of a
+ *    component is the smallest linear index p = (z ny + y) nx + x of its sites.  A component qualifies when its size is
+ *    >= min_size.  The qualifying components are ranked by ascending label: row j belongs to the qualifying component with
+ *    j qualifying components of smaller label.  Rows >= rows are dropped and the header says so (nqual > nrows).
+ *    Arc: neighbouring sites differ by at most 1 per coordinate (modulo the extent) under either connectivity, so the
+ *    projection of a connected component on an axis is connected on the periodic axis: a single arc, or all of it.
+ *    Per axis a of extent n_a: extent_a is the number of occupied coordinates; origin_a is the one occupied coordinate
+ *    whose predecessor (c - 1) mod n_a is unoccupied; where every coordinate is occupied the origin is 0 and the component
+ *    SPANS the axis (extent_a == n_a; an axis of extent 1 is always spanned).  With d_a = (c_a - origin_a) mod n_a over the
+ *    component's sites, unwrapping a non-spanning axis from the origin is unambiguous: the sums below are those of the
+ *    unwrapped component wherever it lies across the periodic planes.  Spanning is necessary for wrapping (a closed path
+ *    of links that winds around the axis), not sufficient: a path may cover every x without a link across the x plane.
+ *    Nothing here detects wrapping.  Faces: the number of pairs (site of the component, one of the 6 axis directions)
+ *    whose periodic neighbour is unoccupied; on an axis of extent 2 the + and - neighbour are the same site and count
+ *    twice, on extent 1 the neighbour is the site itself.  Summed over all components this is the morphology trace's
+ *    S = -6 N3 + 2 N2 at the same level and side: every occupied site counts its unoccupied neighbours, 6 N3 minus the
+ *    ordered occupied pairs along the axes; per axis [o | o+] = o + o+ - o o+ gives N2 = 6 N3 - P with P the unordered
+ *    pairs, so the ordered pairs are 2 P = 12 N3 - 2 N2.
+ *    analysis.component_table restates the rule in numpy.
+ *  - sample: [replica][nlevels][6 + rows x 18] 64-bit signed integers, per level the header, then the rows:
+ *      header word 0   ncomp, the number of components            (the cluster trace's word 0)
+ *      header word 1   V, the number of occupied sites             (the cluster trace's word 1)
+ *      header word 2   nqual, the qualifying components
+ *      header word 3   Vqual, the sites in all qualifying components, tabulated or not
+ *      header word 4   nrows = min(nqual, rows)
+ *      header word 5   capped, the cluster trace's word 5: 0 in every correct run
+ *      row word 0      label               row words 2-4    origin (ox, oy, oz)      row words 5-7    extent (ex, ey, ez)
+ *      row word 1      size                row words 8-10   sum dx, sum dy, sum dz   row words 11-13  sum dx^2, dy^2, dz^2
+ *      row word 17     faces               row words 14-16  sum dx dy, sum dx dz, sum dy dz
+ *    Unused rows (j >= nrows) have label -1 and zeros elsewhere.  All are integers: a record does not depend on the number
+ *    of replicas, `every`, the capacity, the schedule, what else is attached, lone context versus replica, the launch
+ *    geometry or the order in which atomics land.
+ *  - overflow: an extent above 65536 is refused, so d_a d_b < 2^32, and nsites <= 2^31 - 1 bounds every sum of a component
+ *    by 2^31 2^32 = 2^63 (for a != b already d_a d_b < n_a n_b <= nsites).  No 32-bit accumulator holds a sum that can
+ *    exceed it: a brick's partial sums in LDS reach 512 x 2^32 and are 64-bit (csrc/bflbm_components.h argues it); the
+ *    32-bit counters count sites or roots of one workgroup (<= 1024) or qualifying roots (< 2^31).
+ *  - how a sample is taken, on the owner's stream and without a host synchronisation: the cluster trace's observation;
+ *    then per level, one after another, 9 launches: k_cluster_local, k_cluster_merge and k_cluster_resolve, the cluster
+ *    trace's own, after which a site reaches its global root in two plain loads (its brick-local root, then that root's
+ *    parent); k_component_count, k_component_scan and k_component_rank, a deterministic exclusive prefix count of the
+ *    qualifying roots in label order (per workgroup of 1024 sites, over the workgroups, inside the workgroup), which sums
+ *    header words 0..3, writes label and size into rows < rows and leaves every global root its slot or -1;
+ *    k_component_masks, one workgroup per brick of 32 x 4 x 4 sites, ORs the brick's coordinate bits per component in LDS
+ *    and flushes one 64-bit atomic OR per (component present in the brick, axis); k_component_origin turns the masks into
+ *    origin and extent per (replica, slot, axis) and clears them; k_component_moments, one workgroup per brick,
+ *    accumulates the 9 sums and the faces per component in LDS with 64-bit LDS atomics and flushes 64-bit global adds per
+ *    (component present in the brick): the global atomics per component are the bricks it touches, not its sites.  Then
+ *    ONE finishing launch, k_component_finish, writes header and rows of all levels into the slot and clears the staging.
+ *    The phases are separated by launches: no grid barrier.  What a launch reads of an earlier launch it reads with plain
+ *    loads; inside a launch a word another workgroup may touch is only ever the target of an agent-scope atomic
+ *    read-modify-write and is not read back.  The new kernels follow no parent chains; the loops of the three labelling
+ *    launches carry the cluster trace's hard cap and count into header word 5.  No scratch; static LDS 24, 16, 64, 6144, 0,
+ *    43008 and 0 bytes (count, scan, rank, masks, origin, moments, finish).
+ *  - memory per trace: parent and size, 8 bytes per site and replica (a global root's size word becomes its slot); a batch
+ *    also the dense field, 8 bytes per site and replica; per replica rows x (ceil(nx / 64) + ceil(ny / 64) + ceil(nz / 64))
+ *    mask words and 4 bytes per 1024 sites.  Traffic per site and level, derived, not measured: about 50 bytes (24 of the
+ *    labelling, 16 of count and rank, 4 + 4 of the two brick launches plus re-loads through the caches) against the 608 of
+ *    a step.
+ *  - bflbm_component_geometry reports nlevels, the connectivity, min_size, rows, the header words (6), the row words (18)
+ *    and the launches per level (9).
+ *  - out of scope: mass-weighted or second-variable sums per component (a float sum per component has no fixed order
+ *    under atomics), true wrapping (winding) detection, tracking on the device (analysis.track_components links the rows
+ *    of consecutive samples on the host), rings (no bflbm_ring_component_create, the cluster trace's exclusion),
+ *    18-connectivity.
+ *  - what is touched on the owner, sampling rule, capacity, step labels, order among the recorders of one owner: those of
+ *    the cluster trace ("component trace full").  An owner may carry any number of component traces.
+ *  - refused at creation (non-zero return, a message naming the call, before any launch, nothing allocated, the owner's
+ *    recorder list untouched): null arguments (before any device is touched), then the cluster trace's refusals in its
+ *    order and wording up to the connectivity, "min_size must be >= 1 (got %lld)", "rows must be in 1..256 (got %d)",
+ *    every < 1, capacity < 1, a replica view (use bflbm_batch_component_create), a context with nranks > 1, an open step,
+ *    more than 2^31 - 1 sites, an extent above 65536, a capacity beyond 1 TB of records, a failed allocation (the message
+ *    gives the bytes of each buffer).  An open step also refuses bflbm_component_sample, _reset and _read.
+ *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_component_read, _count,
+ *    _geometry and _destroy still work, bflbm_component_sample fails.  bflbm_component_destroy(NULL) returns 0.
+ *  - only bflbm_component_read and bflbm_component_destroy synchronise the owner's stream. */
+typedef struct bflbm_component bflbm_component;
+int bflbm_component_create(bflbm_ctx* c, int source, int var, int nlevels, const double* levels /* [nlevels] */, int side,
+                           int connectivity, long long min_size, int rows, int every, long long capacity,
+                           bflbm_component** out);
+int bflbm_batch_component_create(bflbm_batch* b, int source, int var, int nlevels, const double* levels, int side,
+                                 int connectivity, long long min_size, int rows, int every, long long capacity,
+                                 bflbm_component** out);
+int bflbm_component_destroy(bflbm_component* t);
+int bflbm_component_sample(bflbm_component* t);            /* record the resident state now (e.g. frame 0) */
+int bflbm_component_reset(bflbm_component* t);             /* forget the samples, restart the every-counter */
+int bflbm_component_count(const bflbm_component* t, long long* nsamples, int* nreplicas);
+int bflbm_component_geometry(const bflbm_component* t, int* nlevels, int* connectivity, long long* min_size, int* rows,
+                             int* header_words, int* row_words, int* launches /* per level */);
+int bflbm_component_read(bflbm_component* t, long long first, long long count,
+                         long long* record /* [count][nreplicas][nlevels][6 + rows x 18] */,
+                         long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
 
 /* ---- Radial traces: the sums of chosen fields, of chosen products of them and of chosen projections onto the outward
  * radial unit vector, over the shells of width delta about a droplet's centre, recorded on the device as a time series
