@@ -360,6 +360,7 @@ void state_replaced(bflbm_ctx* c, long long steps, int ref_kind, double total_ma
   c->ref_kind = std::max(ref_kind, 0); c->ref_kind_step = ref_kind < 0 ? -1 : steps;
   c->step_sch = -1;
   c->density_valid = false; c->com_valid = false;
+  c->inject = false;                             // injected noise belongs to the state it was injected for (every LBM_init_* draws anew)
   for (auto& b : c->fsig) for (auto& sg : b) sg = HoSig();     // the frames describe another state
   c->record_stale = true;
   (void)frames_for_next_step(c, false);

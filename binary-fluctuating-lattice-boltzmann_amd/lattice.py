@@ -1353,6 +1353,10 @@ class RingLBM(_DropletMixin):
             setattr(self.params, k, v)
         check(self.lib.bflbm_ring_set_params(self._h, ctypes.byref(self.params)))
 
+    def set_schedule(self, schedule):
+        """Every slab's schedule (BinaryLBM.set_schedule); slabs[0].resolved_schedule() says what the next step runs."""
+        check(self.lib.bflbm_ring_set_schedule(self._h, int(SCHEDULES.get(schedule, schedule))))
+
     def LBM_init_mixture(self):
         check(self.lib.bflbm_ring_init_mixture(self._h))
 

@@ -153,7 +153,10 @@ int bflbm_step(bflbm_ctx* c, int nsteps);
 int bflbm_step_count(const bflbm_ctx* c, long long* steps_done);
 /* The step counter is also the noise index of the counter-based generator (one fresh set of 33 normals per site and
  * index).  A run continued from a kBT > 0 checkpoint (main_run_job.cpp:80 step_continue, :253-270) sets it to the
- * checkpoint's absolute step after bflbm_commit_upload(c, 1), so that it does not replay the first segment's normals. */
+ * checkpoint's absolute step after bflbm_commit_upload(c, 1), so that it does not replay the first segment's normals.
+ * The counter is 64 bits wide and keeps counting; the noise index is the counter modulo 2^32, so the step after counter
+ * 2^32 - 1 draws index 0 again while bflbm_step_count reports 2^32.  Moving the counter changes the generated noise of
+ * the resident state (and what bflbm_get_noise / bflbm_get_hydrovs return), nothing else. */
 int bflbm_set_step_count(bflbm_ctx* c, long long steps_done);
 
 /* One step of a slab (nranks > 1) split so that the +-z exchange overlaps the
@@ -1278,7 +1281,16 @@ int bflbm_get_noise(bflbm_ctx* c, double* fnoise, double* gnoise, const bflbm_fa
 
 /* Test hook: feed the collision of the NEXT step with these noise moments instead of
  * the built-in generator (the reference's RNG stream is not reproducible).
- * Pass NULL,NULL to return to the generator. */
+ * Pass NULL,NULL to return to the generator.
+ * The injected moments stand where the reference keeps fnoisevs / gnoisevs of the resident state, so:
+ *  - until that step ran, bflbm_get_noise returns them and bflbm_get_hydrovs is computed with them (LBM_hydrovars reads
+ *    modes 1..3, :298-313), and no schedule resolves to 3;
+ *  - they feed ONE step: the steps after it draw generated noise again;
+ *  - a new resident state drops them: every LBM_init_* and LBM_init draws the noise of the state it made (:625, :654,
+ *    :691, :740), so bflbm_init_*, bflbm_commit_upload (with either reset_step_counter) and bflbm_tune_placement end a
+ *    pending injection;
+ *  - what leaves the state alone keeps them: bflbm_set_step_count, bflbm_set_params, bflbm_set_schedule and every
+ *    observable. */
 int bflbm_inject_noise(bflbm_ctx* c, const double* fnoise, const double* gnoise, const bflbm_fab* box);
 
 /* update_com (LBM_hydrovs.H:26-60) over this slab: sums of rho, rho*i, rho*j, rho*k
