@@ -197,6 +197,14 @@ SIGNATURES = {
     "bflbm_morph_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
     "bflbm_morph_geometry": (ctypes.c_int, [_vp] + [_P(ctypes.c_int)] * 5),
     "bflbm_morph_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _P(ctypes.c_longlong), _P(ctypes.c_longlong)]),
+    "bflbm_chord_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_batch_chord_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_chord_destroy": (ctypes.c_int, [_vp]),
+    "bflbm_chord_sample": (ctypes.c_int, [_vp]),
+    "bflbm_chord_reset": (ctypes.c_int, [_vp]),
+    "bflbm_chord_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
+    "bflbm_chord_geometry": (ctypes.c_int, [_vp] + [_P(ctypes.c_int)] * 7),
+    "bflbm_chord_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _P(ctypes.c_longlong), _P(ctypes.c_longlong)]),
     "bflbm_cluster_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
     "bflbm_batch_cluster_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
     "bflbm_cluster_destroy": (ctypes.c_int, [_vp]),

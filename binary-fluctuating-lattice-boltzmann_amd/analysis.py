@@ -620,6 +620,97 @@ def morphology_length(counts, nsites):
         return np.where(s != 0, float(nsites) / s, np.nan)
 
 
+# ---- chords: the numpy restatement of the chord trace (include/bflbm.h, "Chord traces") ----
+CHORD_MAX_LENGTH = 4096
+
+
+def chord_blocks(max_length=64):
+    """The layout of a level's W = 1 + 3 (3 + M) words: {"W": W, "occupied": 0, "x" | "y" | "z": {"chords": i,
+    "spanning": i, "long_sites": i, "hist": slice of h[1..M]}}."""
+    m = int(max_length)
+    if not 1 <= m <= CHORD_MAX_LENGTH:
+        raise ValueError(f"chord_blocks: max_length in 1..{CHORD_MAX_LENGTH} (got {max_length})")
+    out = {"W": 1 + 3 * (3 + m), "occupied": 0}
+    for a, name in enumerate("xyz"):
+        at = 1 + a * (3 + m)
+        out[name] = {"chords": at, "spanning": at + 1, "long_sites": at + 2, "hist": slice(at + 3, at + 3 + m)}
+    return out
+
+
+def _chord_axis(axis):
+    if axis in ("x", "y", "z"):
+        return axis
+    if axis in (0, 1, 2):
+        return "xyz"[axis]
+    raise ValueError(f"chord axis {axis!r}, expected 'x', 'y', 'z' or 0..2")
+
+
+def chord_counts(field_zyx, levels, side="above", max_length=64):
+    """counts[nlevels, W] int64 of include/bflbm.h, "Chord traces", in numpy: per level the occupied sites, then per axis
+    x, y, z the chords, the spanning lines, long_sites and the bins h[1..M] of the maximal runs of sites with
+    field >= level (side "above" or 0) or field < level (side "below" or 1) along the periodic lines of
+    field_zyx[nz, ny, nx], for 1..8 finite levels.  A NaN occupies nothing on either side.  Per line the runs' first and
+    last sites are found by differences with the rolled line; the k-th first site pairs with the k-th last site, after
+    the last site of a run through the seam has been moved past the line's end."""
+    v = np.asarray(field_zyx, dtype=np.float64)
+    lv = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if v.ndim != 3 or v.size == 0:
+        raise ValueError(f"chord_counts: a field [nz, ny, nx], got shape {v.shape}")
+    if lv.ndim != 1 or not (1 <= len(lv) <= MORPH_MAX_LEVELS):
+        raise ValueError(f"chord_counts: 1..{MORPH_MAX_LEVELS} levels (got shape {lv.shape})")
+    if not np.isfinite(lv).all():
+        raise ValueError(f"chord_counts: the levels must be finite (got {lv.tolist()})")
+    if side not in MORPH_SIDES and side not in MORPH_SIDES.values():
+        raise ValueError(f"chord_counts: side {side!r}, expected 'above' (0) or 'below' (1)")
+    below = bool(MORPH_SIDES.get(side, side))
+    m = int(max_length)
+    layout = chord_blocks(m)
+    out = np.zeros((len(lv), layout["W"]), dtype=np.int64)
+    for l, t in enumerate(lv):
+        with np.errstate(invalid="ignore"):
+            o = (v < t) if below else (v >= t)
+        out[l, 0] = o.sum()
+        for name, ax in (("x", 2), ("y", 1), ("z", 0)):
+            blk = layout[name]
+            lines = np.moveaxis(o, ax, -1).reshape(-1, o.shape[ax])
+            n = lines.shape[1]
+            full = lines.all(axis=1)
+            out[l, blk["spanning"]] = full.sum()
+            lines = lines[~full]
+            first = lines & ~np.roll(lines, 1, axis=1)              # a run's first site: its predecessor is unoccupied
+            last = lines & ~np.roll(lines, -1, axis=1)              # a run's last site: its successor is unoccupied
+            fl, fp = np.nonzero(first)                                # in line order, then position order
+            ll, lp = np.nonzero(last)
+            opens = np.flatnonzero(np.r_[True, ll[1:] != ll[:-1]]) if len(ll) else ll      # a line's least last site
+            seam = opens[lines[ll[opens], 0] & lines[ll[opens], -1]]  # ... belongs to the run through the seam where both ends are occupied
+            lp[seam] += n
+            key = ll * (2 * n) + lp
+            key.sort()
+            length = key - (fl * (2 * n) + fp) + 1
+            out[l, blk["chords"]] = len(length)
+            out[l, blk["long_sites"]] = length[length >= m].sum()
+            out[l, blk["hist"]] = np.bincount(np.minimum(length, m), minlength=m + 1)[1:]
+    return out
+
+
+def chord_mean_length(counts, n):
+    """[..., 3]: the mean chord (V - n_a spanning) / chords along x, y, z of counts[..., W] for the box n = (nx, ny, nz);
+    NaN where an axis has no chord."""
+    c = np.asarray(counts)
+    if c.ndim < 1 or (c.shape[-1] - 1) % 3 or c.shape[-1] < 13 or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError(f"chord_mean_length: integer counts [..., 1 + 3 (3 + M)], got shape {c.shape} of {c.dtype}")
+    if len(n) != 3:
+        raise ValueError(f"chord_mean_length: n = (nx, ny, nz), got {n!r}")
+    layout = chord_blocks((c.shape[-1] - 1) // 3 - 3)
+    v = c[..., 0].astype(np.float64)
+    out = []
+    for name, na in zip("xyz", n):
+        chords = c[..., layout[name]["chords"]].astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out.append(np.where(chords > 0, (v - float(na) * c[..., layout[name]["spanning"]]) / chords, np.nan))
+    return np.stack(out, axis=-1)
+
+
 # ---- clusters: the numpy restatement of the cluster trace (include/bflbm.h, "Cluster traces") ----
 CLUSTER_WORDS = 38
 CLUSTER_CONNECTIVITIES = (6, 26)

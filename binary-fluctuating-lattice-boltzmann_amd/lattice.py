@@ -696,6 +696,86 @@ class MorphologyTrace(_FieldRecorder):
         return analysis.morphology_length(self.read(first, count)[1], self.sites)
 
 
+class ChordTrace(_FieldRecorder):
+    """The chord-length distributions along x, y and z of the set {v >= level} (side "above") or {v < level} (side
+    "below") of one hydrovs / hydrovsbar variable at 1 to 8 levels, for every replica, recorded on the device as 64-bit
+    integers every `every` steps through the owner (a lone single-slab BinaryLBM or a BatchLBM; no rings) and read once:
+    include/bflbm.h, "Chord traces"; analysis.chord_counts is the same rule in numpy, analysis.chord_blocks the layout.
+    A chord is a maximal run of occupied sites along a periodic line; runs of max_length sites and more share the last
+    bin.  Made by owner.chord_trace(); an owner may carry several (rho and phi, or both sides).  Closing the owner
+    detaches the trace: it stays readable until its own close()."""
+    _abi, _label = "bflbm_chord", "chord_trace"
+    _geometry_types = (ctypes.c_int,) * 7
+    _alias = FieldStats._alias
+
+    def __init__(self, owner, create, variable, levels, side, max_length, source, every, capacity):
+        if side not in MORPH_SIDES and side not in MORPH_SIDES.values():
+            raise ValueError(f"chord_trace: side {side!r}, expected 'above' (0) or 'below' (1)")
+        if not isinstance(variable, (str, int, np.integer)):
+            raise ValueError(f"chord_trace: one variable by name or component index, got {variable!r}")
+        self._select(source, variable)
+        self.side = int(MORPH_SIDES.get(side, side))
+        self.levels = np.atleast_1d(np.asarray(levels, dtype=np.float64)).copy()
+        if self.levels.ndim != 1:
+            raise ValueError(f"chord_trace: levels is a number or a list of 1..8 numbers, got shape {self.levels.shape}")
+        lv = self.levels if len(self.levels) else np.zeros(1)
+        self.max_length = int(max_length)
+        super().__init__(owner, create, self.source, self.variables[0], len(self.levels), _ptr(lv), self.side, self.max_length, int(every), int(capacity))
+        self.n = tuple(owner.n)
+        self.sites = owner.n[0] * owner.n[1] * owner.n[2]
+        self.words = 1 + 3 * (3 + self.max_length)
+
+    names = property(_FieldRecorder._recorded_names, doc="The recorded variable by name, a list of one.")
+
+    def geometry(self):
+        """(levels, max_length M, words W of a level, 32-bit LDS counters of a workgroup, workgroups of the x, the y and
+        the z launch over all replicas): what the library built."""
+        return self._geometry()
+
+    def read(self, first=0, count=None):
+        """(steps[count, B] int64, counts[count, B, nlevels, W] int64: the occupied sites, then per axis x, y, z the
+        chords, the spanning lines, long_sites and h[1..M]) of the samples first ... first + count - 1 (count None: all
+        from `first`); synchronises the owner's stream."""
+        first, count, b, steps = self._window(first, count)
+        counts = np.empty((max(count, 0), b, len(self.levels), self.words), dtype=np.int64)
+        as_ll = ctypes.POINTER(ctypes.c_longlong)
+        check(self.lib.bflbm_chord_read(self._h, first, count, counts.ctypes.data_as(as_ll), steps.ctypes.data_as(as_ll)))
+        return steps, counts
+
+    def _word(self, axis, what, first, count):
+        from . import analysis
+        return self.read(first, count)[1][..., analysis.chord_blocks(self.max_length)[analysis._chord_axis(axis)][what]]
+
+    def occupied(self, first=0, count=None):
+        """[count, B, nlevels] int64: the occupied sites V."""
+        return self.read(first, count)[1][..., 0]
+
+    def chords(self, axis, first=0, count=None):
+        """[count, B, nlevels] int64: the chords along an axis ("x", "y", "z" or 0..2)."""
+        return self._word(axis, "chords", first, count)
+
+    def spanning(self, axis, first=0, count=None):
+        """[count, B, nlevels] int64: the fully occupied lines along an axis, which carry no chord."""
+        return self._word(axis, "spanning", first, count)
+
+    def hist(self, axis, first=0, count=None):
+        """[count, B, nlevels, M] int64: h[1..M] along an axis, the last bin holding the chords of M sites and more."""
+        return self._word(axis, "hist", first, count)
+
+    def mean_length(self, axis, first=0, count=None):
+        """[count, B, nlevels]: the mean chord (V - n_a spanning) / chords along an axis (analysis.chord_mean_length),
+        NaN where there is no chord."""
+        from . import analysis
+        return analysis.chord_mean_length(self.read(first, count)[1], self.n)[..., "xyz".index(analysis._chord_axis(axis))]
+
+    def pdf(self, axis, first=0, count=None):
+        """[count, B, nlevels, M]: h / chords along an axis, the fraction of the chords per bin (width 1; the last bin
+        is open-ended); NaN where there is no chord."""
+        h = self.hist(axis, first, count).astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return h / h.sum(axis=-1, keepdims=True)
+
+
 class ClusterTrace(_FieldRecorder):
     """The connected components of the set {v >= level} (side "above") or {v < level} (side "below") of one hydrovs /
     hydrovsbar variable at 1 to 8 levels under 6- or 26-connectivity on the periodic box, for every replica, labelled on
@@ -1182,6 +1262,13 @@ class BinaryLBM(_DropletMixin):
         area, twice the mean breadth and the Euler characteristic."""
         return MorphologyTrace(self, "bflbm_morph_create", variable, levels, side, source, every, capacity)
 
+    def chord_trace(self, variable, levels, side="above", max_length=64, source="hydrovs", every=1, capacity=64):
+        """Record, after every `every`-th step, the chord-length distributions along x, y and z of the set
+        {variable >= level} (side "above") or {variable < level} (side "below") at 1 to 8 levels, one variable of
+        `source` ("hydrovs" or "hydrovsbar") by name or component index; chords of max_length sites and more share the
+        last bin: ChordTrace, whose hist(axis), chords(axis), spanning(axis) and mean_length(axis) cut the record up."""
+        return ChordTrace(self, "bflbm_chord_create", variable, levels, side, max_length, source, every, capacity)
+
     def cluster_trace(self, variable, levels, side="above", connectivity=26, source="hydrovs", every=1, capacity=64):
         """Record, after every `every`-th step, the connected components of the set {variable >= level} (side "above") or
         {variable < level} (side "below") at 1 to 8 levels under 6- or 26-connectivity, one variable of `source`
@@ -1614,6 +1701,11 @@ class BatchLBM:
         every `every`-th batch step, with one observation launch, one counting launch over all replicas and one finishing
         launch per sample."""
         return MorphologyTrace(self, "bflbm_batch_morph_create", variable, levels, side, source, every, capacity)
+
+    def chord_trace(self, variable, levels, side="above", max_length=64, source="hydrovs", every=1, capacity=64):
+        """Every replica's chord-length distributions along x, y and z of a thresholded variable (BinaryLBM.chord_trace)
+        after every `every`-th batch step: ChordTrace."""
+        return ChordTrace(self, "bflbm_batch_chord_create", variable, levels, side, max_length, source, every, capacity)
 
     def cluster_trace(self, variable, levels, side="above", connectivity=26, source="hydrovs", every=1, capacity=64):
         """Every replica's connected components of a thresholded variable (BinaryLBM.cluster_trace) after every `every`-th

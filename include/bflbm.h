@@ -993,6 +993,88 @@ int bflbm_morph_read(bflbm_morph* t, long long first, long long count,
                      long long* counts /* [count][nreplicas][nlevels][4] */,
                      long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
 
+/* ---- Chord traces: the run-length (chord-length) distributions of a thresholded field along x, y and z, recorded on the
+ * device as a time series of 64-bit integer counts and read once at the end.  The morphology trace says how much interface
+ * there is, the cluster and component traces into how many pieces the set falls; this one records the distribution of the
+ * domain widths along a direction, the standard real-space measure of a coarsening or arrested mixture: its mean per axis
+ * is the stereological domain size 4V/S, its tail tells a bicontinuous sponge from a droplet phase, and the three axes
+ * against each other show anisotropy (a stripe, a sheared or confined mixture, lamellae forming), which the isotropic
+ * shell spectrum and the Minkowski counts average away.  A chord trace is attached to one lone single-slab context or one
+ * replica batch.
+ *  - definition (stated here and nowhere else).  Inputs: a source (0: hydrovs, 22 components; 1: hydrovsbar, 9
+ *    components), one component index v of that source, nlevels in 1..8 finite levels t_l, a side, and max_length M in
+ *    1..4096.  The occupancy is the morphology trace's: side 0 occupies the site (x, y, z) at level l when
+ *    v[z][y][x] >= t_l, side 1 when v[z][y][x] < t_l, a NaN occupies nothing on either side.  For an axis a of x, y, z
+ *    with extent n_a the periodic box has nsites / n_a lines, each the n_a sites that differ in the coordinate a only.
+ *      - A line whose sites are all occupied is a spanning line and carries no chord (on an axis of extent 1: every
+ *        occupied site).
+ *      - On every other line each maximal run of consecutive occupied sites is one chord of length l, 1 <= l <= n_a - 1.
+ *        The line is periodic: a run that passes from n_a - 1 to 0 is one chord.
+ *  - sample: [replica][nlevels][W] 64-bit signed integers, W = 1 + 3 (3 + M), per level in the order of the levels:
+ *      word 0                 V, the occupied sites
+ *      then one block of 3 + M words per axis, in the order x, y, z:
+ *        chords               the chords of the axis
+ *        spanning             its spanning lines
+ *        long_sites           the sum of l over the chords with l >= M
+ *        h[1] .. h[M]         h[l]: the chords of length l for l < M; h[M]: those with l >= M
+ *    Identities, exact on every state: per axis sum_l h[l] = chords and
+ *    sum_{l<M} l h[l] + long_sites + n_a spanning = V; over the axes chords_x + chords_y + chords_z = N2 - 3 N3 of the
+ *    morphology trace's counts at the same level and side, that is S = 2 (chords_x + chords_y + chords_z): every chord has
+ *    two ends and every end is one exposed face.  The mean chord along a is (V - n_a spanning) / chords.  The sums are of
+ *    integers: a record does not depend on the number of replicas, `every`, the capacity, the schedule, what else is
+ *    attached, lone context versus replica, or the launch geometry.  analysis.chord_counts restates the rule in numpy,
+ *    analysis.chord_blocks the layout.
+ *  - bflbm_chord_geometry reports nlevels, M, W, the 32-bit LDS counters of a workgroup (nlevels W) and the workgroups of
+ *    the x, y and z launches over all replicas.
+ *  - how a sample is taken, on the owner's stream and without a host synchronisation: the accumulators' observation of
+ *    the one variable, exactly as the morphology trace takes it; THREE counting launches, compiled once per number of
+ *    levels, 256 threads each, every workgroup with a private copy of its replica's record as nlevels W 32-bit counters
+ *    in dynamic LDS (4 nlevels W bytes, at most 64 KiB; no static LDS) and one 64-bit global integer add per non-zero
+ *    counter at its end.  The x launch: a wave takes a row 64 sites at a turn, one wave ballot per level gives the
+ *    block's occupancy mask, the runs that close inside the block are found from the mask by bit operations at the lane
+ *    of the closing zero, the open run is carried to the next block as a wave-uniform length, and the run through site 0
+ *    is joined with the run that ends at nx - 1 when the row is finished; V is counted here.  The y and the z launch are
+ *    one kernel with the stride and the line map as arguments: a work item is 256 consecutive lines p = o nx + x, the
+ *    lanes lie along x so that every load is a coalesced row segment, a lane marches its line and keeps per level the
+ *    open run, the head run and a bit "a zero was seen" in registers and joins head and tail at the end.  A line is
+ *    handled whole by one wave (x) or one lane (y, z): no chunks, no merge pass, no grid barrier.  Workgroups per replica
+ *    and launch: min(work items, 2048 / replicas), a work item being four rows (x) or 256 lines (y, z), and never so few
+ *    that a workgroup meets more than 2^30 sites or one work item; no counter of a workgroup passes the sites it meets,
+ *    so no 32-bit counter can wrap (csrc/bflbm_chord.h argues the corner).  Expected memory traffic: the field once per
+ *    axis, 24 bytes per site and sample.  Then ONE finishing launch, the histogram trace's, writes the totals straight
+ *    into the slot [sample][replica][nlevels][W] and sets them back to zero.  No scratch.
+ *  - no ring: a z chord crosses the slab boundaries, possibly every one of them, and a slab holds its own planes only.
+ *    There is no bflbm_ring_chord_create.  Not built on purpose: chords along diagonals, chords of a second variable, both
+ *    sides in one trace, fusing the count into the observation.
+ *  - what is touched on the owner: what the morphology trace's observation touches.  The resident state, the step
+ *    counters and everything the owner computes are unchanged.
+ *  - sampling rule, capacity, step labels, order among the recorders of one owner: those of the other traces ("chord trace
+ *    full").  An owner may carry any number of chord traces: rho and phi, or both sides.
+ *  - refused at creation (non-zero return, a message naming the call, before any launch, nothing allocated, the owner's
+ *    recorder list untouched), in this order: null arguments (before any device is touched); the morphology trace's
+ *    refusals (nlevels outside 1..8, a non-finite level, a side other than 0 or 1, a source outside 0..1, a component
+ *    index outside its source); max_length outside 1..4096; nlevels W above 16384 counters (64 KiB of LDS, the histogram
+ *    trace's cap); a plane of more than 2^30 sites; a replica view (use bflbm_batch_chord_create), a context with
+ *    nranks > 1; an open step; every < 1, capacity < 1, a capacity beyond 1 TB of records; a failed allocation (the
+ *    message gives the bytes of each buffer).  An open step also refuses bflbm_chord_sample, _reset and _read.
+ *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_chord_read, _count,
+ *    _geometry and _destroy still work, bflbm_chord_sample fails.  bflbm_chord_destroy(NULL) returns 0.
+ *  - only bflbm_chord_read and bflbm_chord_destroy synchronise the owner's stream. */
+typedef struct bflbm_chord bflbm_chord;
+int bflbm_chord_create(bflbm_ctx* c, int source, int var, int nlevels, const double* levels /* [nlevels] */, int side,
+                       int max_length /* M */, int every, long long capacity, bflbm_chord** out);
+int bflbm_batch_chord_create(bflbm_batch* b, int source, int var, int nlevels, const double* levels, int side,
+                             int max_length, int every, long long capacity, bflbm_chord** out);
+int bflbm_chord_destroy(bflbm_chord* t);
+int bflbm_chord_sample(bflbm_chord* t);                    /* record the resident state now (e.g. frame 0) */
+int bflbm_chord_reset(bflbm_chord* t);                     /* forget the samples, restart the every-counter */
+int bflbm_chord_count(const bflbm_chord* t, long long* nsamples, int* nreplicas);
+int bflbm_chord_geometry(const bflbm_chord* t, int* nlevels, int* max_length /* M */, int* words /* W */,
+                         int* lds_counters /* nlevels W */, int* groups_x, int* groups_y, int* groups_z);
+int bflbm_chord_read(bflbm_chord* t, long long first, long long count,
+                     long long* counts /* [count][nreplicas][nlevels][W] */,
+                     long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
+
 /* ---- Cluster traces: the connected components of a thresholded field, labelled on the device by a union-find over the
  * lattice and recorded as a time series of 64-bit integers, read once at the end.  The morphology trace answers "how many
  * domains" only through chi, which is the count only while no domain has a tunnel or a cavity, and never gives a size.
