@@ -205,6 +205,14 @@ SIGNATURES = {
     "bflbm_chord_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
     "bflbm_chord_geometry": (ctypes.c_int, [_vp] + [_P(ctypes.c_int)] * 7),
     "bflbm_chord_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _P(ctypes.c_longlong), _P(ctypes.c_longlong)]),
+    "bflbm_coarse_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_batch_coarse_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(ctypes.c_int), ctypes.c_int, _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), _P(ctypes.c_int), ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_coarse_destroy": (ctypes.c_int, [_vp]),
+    "bflbm_coarse_sample": (ctypes.c_int, [_vp]),
+    "bflbm_coarse_reset": (ctypes.c_int, [_vp]),
+    "bflbm_coarse_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
+    "bflbm_coarse_geometry": (ctypes.c_int, [_vp] + [_P(ctypes.c_int)] * 7),
+    "bflbm_coarse_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _P(ctypes.c_longlong)]),
     "bflbm_cluster_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
     "bflbm_batch_cluster_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
     "bflbm_cluster_destroy": (ctypes.c_int, [_vp]),

@@ -711,6 +711,75 @@ def chord_mean_length(counts, n):
     return np.stack(out, axis=-1)
 
 
+# ---- coarse fields: the numpy restatement of the coarse trace (include/bflbm.h, "Coarse traces") ----
+COARSE_MAX_VARS, COARSE_MAX_PAIRS, COARSE_MAX_BLOCK_X = 8, 16, 256
+
+
+def _coarse_triple(what, v):
+    try:
+        t = tuple(int(x) for x in v)
+    except TypeError:
+        t = ()
+    if len(t) != 3:
+        raise ValueError(f"coarse_fields: {what} is three integers (x, y, z), got {v!r}")
+    return t
+
+
+def coarse_fields(fields, pairs=(), origin=(0, 0, 0), extent=None, block=(1, 1, 1)):
+    """sums[Q, c_z, c_y, c_x] of include/bflbm.h, "Coarse traces", in numpy, operation for operation and in the header's
+    order: fields[nvars, nz, ny, nx], pairs a list of (a, b) variable slots, origin, extent and block as (x, y, z)
+    (extent None: from the origin to the end of the box).  Entry (q, Z, Y, X): the sum over the block of variable q, or of
+    the product of the pair q - nvars; the window is periodic."""
+    x = np.asarray(fields, dtype=np.float64)
+    if x.ndim != 4 or not 1 <= x.shape[0] <= COARSE_MAX_VARS or min(x.shape) < 1:
+        raise ValueError(f"coarse_fields: fields[nvars, nz, ny, nx] with 1..{COARSE_MAX_VARS} variables, got {x.shape}")
+    nv, nz, ny, nx = x.shape
+    n = (nx, ny, nz)
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    if len(pairs) > COARSE_MAX_PAIRS:
+        raise ValueError(f"coarse_fields: 0..{COARSE_MAX_PAIRS} pairs, got {len(pairs)}")
+    if any(not (0 <= a < nv and 0 <= b < nv) for a, b in pairs):
+        raise ValueError(f"coarse_fields: a pair slot outside the {nv} variables: {pairs}")
+    o = _coarse_triple("origin", origin)
+    w = tuple(na - oa for na, oa in zip(n, o)) if extent is None else _coarse_triple("extent", extent)
+    b = _coarse_triple("block", block)
+    for a in range(3):
+        if not 0 <= o[a] < n[a]:
+            raise ValueError(f"coarse_fields: origin[{'xyz'[a]}] = {o[a]} outside 0..{n[a] - 1}")
+    for a in range(3):
+        if not 1 <= w[a] <= n[a]:
+            raise ValueError(f"coarse_fields: extent[{'xyz'[a]}] = {w[a]} outside 1..{n[a]}")
+    for a in range(3):
+        if b[a] < 1 or w[a] % b[a]:
+            raise ValueError(f"coarse_fields: block[{'xyz'[a]}] = {b[a]} must be >= 1 and divide the extent {w[a]}")
+    if b[0] > COARSE_MAX_BLOCK_X:
+        raise ValueError(f"coarse_fields: block[x] = {b[0]} exceeds {COARSE_MAX_BLOCK_X}")
+    ix, iy, iz = [(o[a] + np.arange(w[a])) % n[a] for a in range(3)]                     # the periodic window
+    win = x[:, iz][:, :, iy][:, :, :, ix]                                               # [nvars, w_z, w_y, w_x]
+    terms = np.concatenate([win] + [(win[p] * win[q])[None] for p, q in pairs], axis=0)
+    cx, cy, cz = [w[a] // b[a] for a in range(3)]
+    terms = terms.reshape(len(terms), cz, b[2], cy, b[1], cx, b[0])
+    col = np.zeros((len(terms), cz, cy, cx, b[0]))
+    for dz in range(b[2]):                                 # per fine column: dz, then dy
+        for dy in range(b[1]):
+            col = col + terms[:, :, dz, :, dy, :, :]
+    out = np.zeros((len(terms), cz, cy, cx))
+    for dx in range(b[0]):                                 # then the columns of a block, left to right
+        out = out + col[..., dx]
+    return out
+
+
+def coarse_block_variance(sum_a, sum_b, sum_ab, block_sites):
+    """The covariance of a and b within every block from the block sums of a, b and a * b over block_sites = b_x b_y b_z
+    sites each: the mean of the product minus the product of the means (a is b: the block variance).  Arrays of one
+    shape."""
+    sa, sb, sab = (np.asarray(v, dtype=np.float64) for v in (sum_a, sum_b, sum_ab))
+    if not (sa.shape == sb.shape == sab.shape) or int(block_sites) < 1:
+        raise ValueError(f"coarse_block_variance: three arrays of one shape and block_sites >= 1, got {sa.shape}, {sb.shape}, {sab.shape}, {block_sites!r}")
+    m = float(int(block_sites))
+    return sab / m - (sa / m) * (sb / m)
+
+
 # ---- clusters: the numpy restatement of the cluster trace (include/bflbm.h, "Cluster traces") ----
 CLUSTER_WORDS = 38
 CLUSTER_CONNECTIVITIES = (6, 26)

@@ -776,6 +776,85 @@ class ChordTrace(_FieldRecorder):
             return h / h.sum(axis=-1, keepdims=True)
 
 
+class CoarseTrace(_FieldRecorder):
+    """The sums of chosen hydrovs / hydrovsbar variables, and of chosen products of them, over the blocks of a periodic
+    window of the box, for every replica, recorded on the device every `every` steps through the owner (a lone
+    single-slab BinaryLBM or a BatchLBM; no rings) and read once: include/bflbm.h, "Coarse traces"; analysis.coarse_fields
+    is the same arithmetic in numpy.  With block (1, 1, 1) a sample is a slice or a sub-volume, with a larger block a
+    coarse movie.  origin, extent and block are (x, y, z); extent None: from the origin to the end of the box.  Made by
+    owner.coarse_trace(); an owner may carry several.  Closing the owner detaches the trace: it stays readable until its
+    own close()."""
+    _abi, _label = "bflbm_coarse", "coarse_trace"
+    _geometry_types = (ctypes.c_int,) * 7
+
+    def __init__(self, owner, create, variables, pairs, block, origin, extent, source, every, capacity):
+        selection = self._select(source, variables, pairs)   # a lone name among the pairs: its square
+        self.origin = self._triple("origin", origin)
+        self.extent = tuple(n - o for n, o in zip(owner.n, self.origin)) if extent is None else self._triple("extent", extent)
+        self.block = self._triple("block", block)
+        super().__init__(owner, create, self.source, *selection, _ints(self.origin), _ints(self.extent), _ints(self.block), int(every), int(capacity))
+        self.block_sites = self.block[0] * self.block[1] * self.block[2]
+
+    @staticmethod
+    def _triple(what, v):
+        try:
+            t = tuple(int(x) for x in v)
+        except TypeError:
+            t = ()
+        if len(t) != 3:
+            raise ValueError(f"coarse_trace: {what} is three integers (x, y, z), got {v!r}")
+        return t
+
+    names = property(_FieldRecorder._recorded_names, doc="The recorded variables by name, in slot order.")
+
+    @property
+    def sum_names(self):
+        """The Q sums by name: the variables, then "a*b" for every pair."""
+        names = self.names
+        return names + [f"{names[a]}*{names[b]}" for a, b in self.pairs]
+
+    def geometry(self):
+        """(c_x, c_y, c_z, Q = variables + pairs, fine sites of an x-tile, work items of a replica, workgroups over all
+        replicas): what the library built."""
+        return self._geometry()
+
+    def read(self, first=0, count=None):
+        """(steps[count, B] int64, sums[count, B, Q, c_z, c_y, c_x]) of the samples first ... first + count - 1 (count
+        None: all from `first`); the variables first, then the pairs; synchronises the owner's stream."""
+        first, count, b, steps = self._window(first, count)
+        cx, cy, cz, nq = self.geometry()[:4]
+        sums = np.empty((max(count, 0), b, nq, cz, cy, cx))
+        check(self.lib.bflbm_coarse_read(self._h, first, count, _ptr(sums), steps.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        return steps, sums
+
+    def means(self, first=0, count=None):
+        """sums / (b_x b_y b_z) [count, B, Q, c_z, c_y, c_x]: the block averages."""
+        return self.read(first, count)[1] / float(self.block_sites)
+
+    def block_variance(self, pair_slot, first=0, count=None):
+        """[count, B, c_z, c_y, c_x]: the covariance of the pair's two variables within every block, the mean of the
+        product minus the product of the means (analysis.coarse_block_variance); for a pair (a, a) the block variance."""
+        from . import analysis
+        p = int(pair_slot)
+        if not 0 <= p < len(self.pairs):
+            raise ValueError(f"coarse_trace: pair slot {pair_slot!r} outside the {len(self.pairs)} pairs")
+        sums = self.read(first, count)[1]
+        a, b = self.pairs[p]
+        return analysis.coarse_block_variance(sums[:, :, a], sums[:, :, b], sums[:, :, len(self.variables) + p], self.block_sites)
+
+    def write_plotfiles(self, root, replica=0):
+        """One AMReX-format plotfile directory per sample of `replica`, named plotfile.concatenate(root, step): the coarse
+        cells are the box, the components the block sums under sum_names, the step the replica's counter at the sample
+        (two samples of one step share a directory: the later one stays).  plotfile.read_plotfile reads them back.
+        Returns the directory names."""
+        from . import plotfile
+        steps, sums = self.read()
+        if not 0 <= int(replica) < sums.shape[1]:
+            raise ValueError(f"coarse_trace: replica {replica!r} outside the {sums.shape[1]} replicas")
+        return [plotfile.write_plotfile(plotfile.concatenate(root, int(s[replica])), frame[replica], self.sum_names, time=float(s[replica]), step=int(s[replica]))
+                for s, frame in zip(steps, sums)]
+
+
 class ClusterTrace(_FieldRecorder):
     """The connected components of the set {v >= level} (side "above") or {v < level} (side "below") of one hydrovs /
     hydrovsbar variable at 1 to 8 levels under 6- or 26-connectivity on the periodic box, for every replica, labelled on
@@ -1269,6 +1348,14 @@ class BinaryLBM(_DropletMixin):
         last bin: ChordTrace, whose hist(axis), chords(axis), spanning(axis) and mean_length(axis) cut the record up."""
         return ChordTrace(self, "bflbm_chord_create", variable, levels, side, max_length, source, every, capacity)
 
+    def coarse_trace(self, variables, pairs=(), block=(1, 1, 1), origin=(0, 0, 0), extent=None, source="hydrovs", every=1, capacity=64):
+        """Record, after every `every`-th step, the sums of the `variables` of `source` ("hydrovs" or "hydrovsbar"; names or
+        component indices) and of the products of the `pairs` of them over the blocks of `block` = (b_x, b_y, b_z) sites of
+        the periodic window that starts at `origin` and has `extent` sites (x, y, z; None: to the end of the box), as a
+        time series of coarse fields on the device: CoarseTrace, whose read(), means(), block_variance(pair) and
+        write_plotfiles(root) give the record.  Block (1, 1, 1) records the window itself: a slice or a sub-volume."""
+        return CoarseTrace(self, "bflbm_coarse_create", variables, pairs, block, origin, extent, source, every, capacity)
+
     def cluster_trace(self, variable, levels, side="above", connectivity=26, source="hydrovs", every=1, capacity=64):
         """Record, after every `every`-th step, the connected components of the set {variable >= level} (side "above") or
         {variable < level} (side "below") at 1 to 8 levels under 6- or 26-connectivity, one variable of `source`
@@ -1706,6 +1793,11 @@ class BatchLBM:
         """Every replica's chord-length distributions along x, y and z of a thresholded variable (BinaryLBM.chord_trace)
         after every `every`-th batch step: ChordTrace."""
         return ChordTrace(self, "bflbm_batch_chord_create", variable, levels, side, max_length, source, every, capacity)
+
+    def coarse_trace(self, variables, pairs=(), block=(1, 1, 1), origin=(0, 0, 0), extent=None, source="hydrovs", every=1, capacity=64):
+        """Every replica's block sums over a window (BinaryLBM.coarse_trace) after every `every`-th batch step, with one
+        observation launch and one summing launch over all replicas per sample: CoarseTrace."""
+        return CoarseTrace(self, "bflbm_batch_coarse_create", variables, pairs, block, origin, extent, source, every, capacity)
 
     def cluster_trace(self, variable, levels, side="above", connectivity=26, source="hydrovs", every=1, capacity=64):
         """Every replica's connected components of a thresholded variable (BinaryLBM.cluster_trace) after every `every`-th

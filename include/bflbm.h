@@ -1075,6 +1075,84 @@ int bflbm_chord_read(bflbm_chord* t, long long first, long long count,
                      long long* counts /* [count][nreplicas][nlevels][W] */,
                      long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
 
+/* ---- Coarse traces: the sums of chosen fields, and of chosen products of them, over the blocks of a window of the box,
+ * recorded on the device as a time series of coarse fields and read once at the end.  Every other recorder reduces the
+ * observed fields to scalars, profiles, spectra, histograms, counts or tables; this one keeps a field in space over time:
+ * the slices and renders of Viewer.ipynb and Visualization.ipynb, a movie of a coarsening mixture or of a droplet that
+ * drifts through the box, without downloading hydrovs (22 fields of 8 bytes per site and frame).  With block 1 a sample is
+ * a slice or a sub-volume, with block 4 x 4 x 4 a 128^3 movie of a 512^3 box at 1/64 of the bytes; with pairs it carries
+ * the block sums of products, from which the block variances and the block-size scaling of the density fluctuations
+ * follow, the real-space twin of the flat S(k) of Mixture.ipynb.  A coarse trace is attached to one lone single-slab
+ * context or one replica batch.
+ *  - definition (stated here and nowhere else).  Inputs: a source (0: hydrovs, 22 components; 1: hydrovsbar, 9
+ *    components), nvars in 1..8 distinct component indices of that source, npairs in 0..16 pairs (a, b) of variable SLOTS
+ *    (positions in the variable list), a == b allowed, Q = nvars + npairs; a window of the periodic box n = (nx, ny, nz)
+ *    by origin[3] (x, y, z), 0 <= o_a < n_a, and extent[3], 1 <= w_a <= n_a: site i of the window along the axis a is
+ *    (o_a + i) mod n_a, so a window may run through the seam; block[3] with b_a >= 1, b_a dividing w_a, and b_x <= 256.
+ *    The window holds c_a = w_a / b_a blocks along a; block (X, Y, Z) holds the window sites i_a = b_a K_a + d_a,
+ *    0 <= d_a < b_a.  A site's term is x_q for q < nvars and x_a * x_b for the pair q - nvars: the product rounded once
+ *    and then added, never contracted (-ffp-contract=off), as the profile trace forms its products.  Entry
+ *    (q, Z, Y, X) of a sample is the sum of the terms of q over the sites of the block, in this order, which the box,
+ *    the window and the block fix alone (never the launch geometry, the batch around a replica, `every`, the capacity,
+ *    the schedule, what else is attached, lone context versus replica):
+ *      per fine column d_x of the block:   C(d_x) = +0.0;  for d_z = 0 .. b_z-1:  for d_y = 0 .. b_y-1:  C = C + term
+ *      then the block:                     S = +0.0;  for d_x = 0 .. b_x-1:  S = S + C(d_x)
+ *    These are sums, not means: the reader divides by b_x b_y b_z.  A NaN stays in its block.  With block (1, 1, 1) a
+ *    sample is the window itself (a -0.0 reads +0.0).  analysis.coarse_fields restates this in numpy, operation for
+ *    operation; analysis.coarse_block_variance turns the sums of a, b and a * b into the covariance within every block.
+ *  - sample: [replica][Q][c_z][c_y][c_x] doubles, the variables first, then the pairs.
+ *  - bflbm_coarse_geometry reports c_x, c_y, c_z, Q, the fine sites of an x-tile (floor(256 / b_x) b_x), the work items
+ *    of a replica (c_z c_y ceil(w_x / x-tile)) and the workgroups of the launch over all replicas.
+ *  - how a sample is taken, on the owner's stream and without a host synchronisation: the accumulators' observation,
+ *    exactly as the profile trace takes it (a lone context: into the scratch state buffer; a batch: one launch over all
+ *    replicas, only the chosen variables, into a buffer of the trace); then ONE launch, compiled once per number of
+ *    variables, 256 threads, which writes the slot [sample][replica] directly: no totals, no finishing launch, no
+ *    atomics.  A work item is (Z, Y, x-tile): an x-tile is floor(256 / b_x) b_x fine sites of a window row, so no block
+ *    straddles a tile.  A lane owns one fine column and marches d_z, d_y with four rows' loads in flight; the lanes lie
+ *    along x, so every global load of a wave is a contiguous row segment of 8-byte elements, or two where the wave meets
+ *    the seam, never a lane-strided one; a site's variables are loaded once and the products are formed in registers.
+ *    After the march the Q column sums pass through LDS once (2048 Q bytes of dynamic LDS, no static LDS) and the first
+ *    lane of every block adds its b_x columns left to right and stores.  Work items of at most 64 (128) lanes share a
+ *    workgroup four (two) at a time; workgroups per replica: min(turns, 2048 / replicas), a workgroup striding over its
+ *    turns.  A block that is tall in y and z is marched by ONE lane per column and a wide one added by one lane: no
+ *    chunks, no merge pass; blocks of a few sites per axis are what this is built for.  Expected memory traffic:
+ *    8 nvars bytes read per window site and sample, 8 Q / (b_x b_y b_z) written, against the 608 of a step.  The
+ *    8-byte loads, the four rows in flight and the 2048 workgroups are untimed heuristics.  No scratch.
+ *  - no ring: a block may straddle two slabs, and gathering field-sized blocks onto slab 0 needs a layout decision of its
+ *    own.  There is no bflbm_ring_coarse_create.  Not built on purpose: the noise source, output other than doubles,
+ *    b_x > 256, a merge pass for tall blocks.
+ *  - what is touched on the owner: what the profile trace's observation touches.  The resident state, the step counters
+ *    and everything the owner computes are unchanged.
+ *  - sampling rule, capacity, step labels, order among the recorders of one owner: those of the other traces ("coarse
+ *    trace full").  An owner may carry any number of coarse traces: a slice and a coarse volume, say.
+ *  - refused at creation (non-zero return, a message naming the call, before any launch, nothing allocated, the owner's
+ *    recorder list untouched), in this order: null arguments (before any device is touched; pair_a and pair_b may be
+ *    NULL only where npairs == 0); a source outside 0..1, nvars outside 1..8, npairs outside 0..16, a component index
+ *    outside its source, a repeated variable, a pair slot outside 0..nvars-1; an origin outside 0..n_a-1, then an extent
+ *    outside 1..n_a, then per axis a block < 1 or one that does not divide the extent, then b_x > 256; more than 2^30
+ *    work items per replica; a replica view (use bflbm_batch_coarse_create), a context with nranks > 1; an open step;
+ *    every < 1, capacity < 1; a capacity beyond 1 TB of records; a failed allocation (the message gives the bytes of
+ *    each buffer).  An open step also refuses bflbm_coarse_sample, _reset and _read.
+ *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_coarse_read, _count,
+ *    _geometry and _destroy still work, bflbm_coarse_sample fails.  bflbm_coarse_destroy(NULL) returns 0.
+ *  - only bflbm_coarse_read and bflbm_coarse_destroy synchronise the owner's stream. */
+typedef struct bflbm_coarse bflbm_coarse;
+int bflbm_coarse_create(bflbm_ctx* c, int source, int nvars, const int* vars, int npairs,
+                        const int* pair_a /* or NULL if npairs == 0 */, const int* pair_b, const int* origin /* [3]: x, y, z */,
+                        const int* extent /* [3] */, const int* block /* [3] */, int every, long long capacity, bflbm_coarse** out);
+int bflbm_batch_coarse_create(bflbm_batch* b, int source, int nvars, const int* vars, int npairs,
+                              const int* pair_a, const int* pair_b, const int* origin, const int* extent, const int* block,
+                              int every, long long capacity, bflbm_coarse** out);
+int bflbm_coarse_destroy(bflbm_coarse* t);
+int bflbm_coarse_sample(bflbm_coarse* t);                  /* record the resident state now (e.g. frame 0) */
+int bflbm_coarse_reset(bflbm_coarse* t);                   /* forget the samples, restart the every-counter */
+int bflbm_coarse_count(const bflbm_coarse* t, long long* nsamples, int* nreplicas);
+int bflbm_coarse_geometry(const bflbm_coarse* t, int* cx, int* cy, int* cz, int* nsums /* Q */, int* tile_sites,
+                          int* items /* work items per replica */, int* groups /* workgroups over all replicas */);
+int bflbm_coarse_read(bflbm_coarse* t, long long first, long long count,
+                      double* sums /* [count][nreplicas][Q][c_z][c_y][c_x] */,
+                      long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
+
 /* ---- Cluster traces: the connected components of a thresholded field, labelled on the device by a union-find over the
  * lattice and recorded as a time series of 64-bit integers, read once at the end.  The morphology trace answers "how many
  * domains" only through chi, which is the count only while no domain has a tunnel or a cavity, and never gives a size.
