@@ -780,6 +780,111 @@ def coarse_block_variance(sum_a, sum_b, sum_ab, block_sites):
     return sab / m - (sa / m) * (sb / m)
 
 
+# ---- lag records: the numpy restatement of the lag trace (include/bflbm.h, "Lag traces") ----
+LAG_MAX_VARS, LAG_MAX_PAIRS, LAG_MAX_ORIGINS = 8, 8, 16
+
+
+def lag_slots(nsamples, norigins, origin_stride):
+    """held[nsamples, R] int64: the sample whose origin slot r holds at sample n, after sample n has taken its own (-1: the
+    slot is empty).  Sample n with n % E == 0 takes an origin into slot (n / E) % R."""
+    ns, r, e = int(nsamples), int(norigins), int(origin_stride)
+    if ns < 0 or not 1 <= r <= LAG_MAX_ORIGINS or e < 1:
+        raise ValueError(f"lag_slots: nsamples >= 0, 1..{LAG_MAX_ORIGINS} origins and a stride >= 1, got {nsamples!r}, {norigins!r}, {origin_stride!r}")
+    held = np.full((ns, r), -1, dtype=np.int64)
+    for n in range(ns):
+        if n > 0:
+            held[n] = held[n - 1]
+        if n % e == 0:
+            held[n, (n // e) % r] = n
+    return held
+
+
+def _z_sum(profile):
+    """The planes z = 0 .. nz-1 of sums[Q, nz] in sequence, from +0.0."""
+    out = np.zeros(profile.shape[0])
+    for z in range(profile.shape[1]):
+        out = out + profile[:, z]
+    return out
+
+
+def lag_record(frames, steps, pairs, norigins, origin_stride=1, persist_slot=-1, persist_level=0.0):
+    """(now[n, nvars], origin_steps[n, R] int64, alive[n, R] int64, corr[n, R, npairs]) of include/bflbm.h, "Lag traces",
+    in numpy, operation for operation and in the header's order: frames[n, nvars, nz, ny, nx] the observed variables at
+    the samples of one replica, steps[n] its step counter at each, pairs a list of (a, b) variable slots.  Every double
+    sum is plane_profiles(..., axis=2) summed over z in sequence."""
+    x = np.asarray(frames, dtype=np.float64)
+    steps = np.asarray(steps, dtype=np.int64)
+    if x.ndim != 5 or not 1 <= x.shape[1] <= LAG_MAX_VARS or steps.shape != x.shape[:1]:
+        raise ValueError(f"lag_record: frames[n, nvars, nz, ny, nx] with 1..{LAG_MAX_VARS} variables and steps[n], got {x.shape} and {steps.shape}")
+    ns, nv = x.shape[:2]
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    if not 1 <= len(pairs) <= LAG_MAX_PAIRS or any(not (0 <= a < nv and 0 <= b < nv) for a, b in pairs):
+        raise ValueError(f"lag_record: 1..{LAG_MAX_PAIRS} pairs of slots within the {nv} variables, got {pairs}")
+    ps = int(persist_slot)
+    if not -1 <= ps < nv or (ps >= 0 and not np.isfinite(persist_level)):
+        raise ValueError(f"lag_record: persist_slot in -1..{nv - 1} and a finite level, got {persist_slot!r}, {persist_level!r}")
+    held = lag_slots(ns, norigins, origin_stride)
+    r = held.shape[1]
+    now = np.zeros((ns, nv))
+    origin_steps = np.full((ns, r), -1, dtype=np.int64)
+    alive = np.full((ns, r), -1, dtype=np.int64)
+    corr = np.full((ns, r, len(pairs)), np.nan)
+    bits = np.zeros((r,) + x.shape[2:], dtype=bool)        # a site's bit per slot
+    lagged = [(a, nv + b) for a, b in pairs]               # the current variables, then the origin's
+    level = np.float64(persist_level)
+    for n in range(ns):
+        now[n] = _z_sum(plane_profiles(x[n], (), axis=2))
+        with np.errstate(invalid="ignore"):
+            side = x[n, ps] >= level if ps >= 0 else None  # a NaN: false
+        for k in range(r):
+            o = held[n, k]
+            if o < 0:
+                continue
+            origin_steps[n, k] = steps[o]
+            corr[n, k] = _z_sum(plane_profiles(np.concatenate([x[n], x[o]]), lagged, axis=2))[2 * nv:]
+            if ps >= 0:
+                if o == n:
+                    bits[k] = True                         # the origin is taken: every site's bit is set
+                with np.errstate(invalid="ignore"):
+                    bits[k] &= side == (x[o, ps] >= level)
+                alive[n, k] = np.count_nonzero(bits[k])
+    return now, origin_steps, alive, corr
+
+
+def lag_average(steps, origin_steps, values):
+    """(lags, mean[nlags], origins[nlags] int64): values[n, R] of a lag record averaged over the origins by
+    lag = steps[n] - origin_steps[n, r], in steps; empty slots (origin_step < 0) and NaN values are left out."""
+    steps = np.asarray(steps, dtype=np.int64)
+    osteps = np.asarray(origin_steps, dtype=np.int64)
+    v = np.asarray(values, dtype=np.float64)
+    if osteps.ndim != 2 or steps.shape != osteps.shape[:1] or v.shape != osteps.shape:
+        raise ValueError(f"lag_average: steps[n], origin_steps[n, R] and values[n, R], got {steps.shape}, {osteps.shape}, {v.shape}")
+    lag = steps[:, None] - osteps
+    use = (osteps >= 0) & ~np.isnan(v)
+    lags = np.unique(lag[use])
+    mean = np.array([v[use & (lag == d)].mean() for d in lags], dtype=np.float64)
+    count = np.array([np.count_nonzero(use & (lag == d)) for d in lags], dtype=np.int64)
+    return lags, mean, count
+
+
+def lag_connected(steps, origin_steps, corr, now_a, now_b, nsites):
+    """corr[n, R] of the pair (a, b) minus now_a[n] * now_b[the origin's own sample] / nsites: the connected part.  NaN
+    where the origin's own sample is not in the record (an empty slot, or a window read without it)."""
+    steps = np.asarray(steps, dtype=np.int64)
+    osteps = np.asarray(origin_steps, dtype=np.int64)
+    c, na, nb = (np.asarray(v, dtype=np.float64) for v in (corr, now_a, now_b))
+    if osteps.ndim != 2 or c.shape != osteps.shape or not (steps.shape == na.shape == nb.shape == osteps.shape[:1]) or int(nsites) < 1:
+        raise ValueError(f"lag_connected: steps[n], origin_steps[n, R], corr[n, R], now_a[n], now_b[n], got {steps.shape}, {osteps.shape}, {c.shape}, {na.shape}, {nb.shape}")
+    out = np.full(c.shape, np.nan)
+    where = {int(s): n for n, s in reversed(list(enumerate(steps)))}   # the first sample of a step
+    for n in range(osteps.shape[0]):
+        for k in range(osteps.shape[1]):
+            o = where.get(int(osteps[n, k])) if osteps[n, k] >= 0 else None
+            if o is not None and o <= n:
+                out[n, k] = c[n, k] - na[n] * nb[o] / float(int(nsites))
+    return out
+
+
 # ---- clusters: the numpy restatement of the cluster trace (include/bflbm.h, "Cluster traces") ----
 CLUSTER_WORDS = 38
 CLUSTER_CONNECTIVITIES = (6, 26)

@@ -855,6 +855,88 @@ class CoarseTrace(_FieldRecorder):
                 for s, frame in zip(steps, sums)]
 
 
+class LagTrace(_FieldRecorder):
+    """Two-time correlations of chosen hydrovs / hydrovsbar variables against `origins` time origins kept on the device,
+    for every replica, recorded every `every` steps through the owner (a lone single-slab BinaryLBM or a BatchLBM; no
+    rings) and read once: include/bflbm.h, "Lag traces"; analysis.lag_record is the same rule in numpy.  Every
+    `origin_stride`-th sample takes an origin (a copy of the variables of every site) into the next of the slots; every
+    sample records, per held origin, corr = sum_x a(x, now) * b(x, origin) for every pair (a, b) and, with
+    persist=(variable, level), the sites whose side of the level has not changed at any sample since the origin.  Made by
+    owner.lag_trace(); an owner may carry several.  Closing the owner detaches the trace: it stays readable until its own
+    close()."""
+    _abi, _label = "bflbm_lag", "lag_trace"
+    _geometry_types = (ctypes.c_int,) * 7 + (ctypes.c_longlong,) * 2
+
+    def __init__(self, owner, create, variables, pairs, origins, origin_stride, persist, source, every, capacity):
+        selection = self._select(source, variables, pairs)   # a lone name among the pairs: the variable with itself
+        if persist is None:
+            self.persist_slot, self.persist_level = -1, 0.0
+        else:
+            try:
+                which, level = persist
+            except (TypeError, ValueError):
+                raise ValueError(f"lag_trace: persist = (variable, level) or None, got {persist!r}") from None
+            self.persist_slot, self.persist_level = self._slot(which), float(level)
+        self.origins, self.origin_stride = int(origins), int(origin_stride)
+        super().__init__(owner, create, self.source, *selection, self.origins, self.origin_stride, self.persist_slot, self.persist_level,
+                         int(every), int(capacity))
+        self.sites = owner.n[0] * owner.n[1] * owner.n[2]
+
+    names = property(_FieldRecorder._recorded_names, doc="The recorded variables by name, in slot order.")
+
+    def geometry(self):
+        """(nvars, npairs, origins R, origin_stride E, words W of a replica's sample, sites of a tile, tiles of a plane,
+        bytes of the origins, bytes of the masks): what the library built."""
+        return self._geometry()
+
+    def read(self, first=0, count=None):
+        """(steps[count, B] int64, now[count, B, nvars], origin_steps[count, B, R] int64 (-1: an empty slot),
+        alive[count, B, R] int64 (-1: no persistence, or an empty slot), corr[count, B, R, npairs] (NaN: an empty slot)) of
+        the samples first ... first + count - 1 (count None: all from `first`): views of the sample's 8-byte words;
+        synchronises the owner's stream."""
+        first, count, b, steps = self._window(first, count)
+        nv, npairs, r = len(self.variables), len(self.pairs), self.origins
+        words = np.empty((max(count, 0), b, nv + r * (2 + npairs)))
+        check(self.lib.bflbm_lag_read(self._h, first, count, _ptr(words), steps.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        slots = words[..., nv:].reshape(words.shape[0], b, r, 2 + npairs)
+        return steps, words[..., :nv], slots[..., 0].view(np.int64), slots[..., 1].view(np.int64), slots[..., 2:]
+
+    def _pair_index(self, pair):
+        if isinstance(pair, (int, np.integer)):
+            p = int(pair)
+            if not 0 <= p < len(self.pairs):
+                raise ValueError(f"lag_trace: pair {pair!r} outside the {len(self.pairs)} pairs")
+            return p
+        want = (self._slot(pair), self._slot(pair)) if isinstance(pair, str) else (self._slot(pair[0]), self._slot(pair[1]))
+        if want not in self.pairs:
+            raise ValueError(f"lag_trace: {pair!r} is not one of the recorded pairs")
+        return self.pairs.index(want)
+
+    def correlation(self, pair, connected=False, replica=0):
+        """(lags in steps, the mean of corr over the origins at every lag, the origins per lag) of one pair (by index,
+        by (a, b) of names or slots, or a lone name) and one replica; connected: minus now_a(sample) now_b(origin's
+        sample) / sites (analysis.lag_connected), where the origin's own sample is in the record."""
+        from . import analysis
+        p = self._pair_index(pair)
+        steps, now, osteps, _, corr = self.read()
+        k = int(replica)
+        values = corr[:, k, :, p]
+        if connected:
+            a, b = self.pairs[p]
+            values = analysis.lag_connected(steps[:, k], osteps[:, k], values, now[:, k, a], now[:, k, b], self.sites)
+        return analysis.lag_average(steps[:, k], osteps[:, k], values)
+
+    def persistence(self, replica=0):
+        """(lags in steps, the mean over the origins of alive / sites at every lag, the origins per lag) of one replica."""
+        from . import analysis
+        if self.persist_slot < 0:
+            raise ValueError("lag_trace: made without persist=(variable, level)")
+        steps, _, osteps, alive, _ = self.read()
+        k = int(replica)
+        values = np.where(alive[:, k] >= 0, alive[:, k] / float(self.sites), np.nan)
+        return analysis.lag_average(steps[:, k], osteps[:, k], values)
+
+
 class ClusterTrace(_FieldRecorder):
     """The connected components of the set {v >= level} (side "above") or {v < level} (side "below") of one hydrovs /
     hydrovsbar variable at 1 to 8 levels under 6- or 26-connectivity on the periodic box, for every replica, labelled on
@@ -1356,6 +1438,15 @@ class BinaryLBM(_DropletMixin):
         write_plotfiles(root) give the record.  Block (1, 1, 1) records the window itself: a slice or a sub-volume."""
         return CoarseTrace(self, "bflbm_coarse_create", variables, pairs, block, origin, extent, source, every, capacity)
 
+    def lag_trace(self, variables, pairs, origins=8, origin_stride=1, persist=None, source="hydrovs", every=1, capacity=64):
+        """Record, after every `every`-th step, the two-time correlations of the `variables` of `source` ("hydrovs" or
+        "hydrovsbar"; names or component indices) against `origins` time origins kept on the device: every
+        `origin_stride`-th sample takes an origin, every sample records sum_x a(x, now) * b(x, origin) per held origin and
+        pair (a, b) of `pairs` (a lone name: the variable with itself) and, with persist=(variable, level), the sites whose
+        side of the level has not changed since the origin: LagTrace, whose read(), correlation(pair) and persistence()
+        give the record."""
+        return LagTrace(self, "bflbm_lag_create", variables, pairs, origins, origin_stride, persist, source, every, capacity)
+
     def cluster_trace(self, variable, levels, side="above", connectivity=26, source="hydrovs", every=1, capacity=64):
         """Record, after every `every`-th step, the connected components of the set {variable >= level} (side "above") or
         {variable < level} (side "below") at 1 to 8 levels under 6- or 26-connectivity, one variable of `source`
@@ -1798,6 +1889,12 @@ class BatchLBM:
         """Every replica's block sums over a window (BinaryLBM.coarse_trace) after every `every`-th batch step, with one
         observation launch and one summing launch over all replicas per sample: CoarseTrace."""
         return CoarseTrace(self, "bflbm_batch_coarse_create", variables, pairs, block, origin, extent, source, every, capacity)
+
+    def lag_trace(self, variables, pairs, origins=8, origin_stride=1, persist=None, source="hydrovs", every=1, capacity=64):
+        """Every replica's two-time correlations against origins kept on the device (BinaryLBM.lag_trace) after every
+        `every`-th batch step, with one observation launch and one summing launch over all replicas per sample; an
+        origin carries each replica's own step counter: LagTrace."""
+        return LagTrace(self, "bflbm_batch_lag_create", variables, pairs, origins, origin_stride, persist, source, every, capacity)
 
     def cluster_trace(self, variable, levels, side="above", connectivity=26, source="hydrovs", every=1, capacity=64):
         """Every replica's connected components of a thresholded variable (BinaryLBM.cluster_trace) after every `every`-th

@@ -1153,6 +1153,93 @@ int bflbm_coarse_read(bflbm_coarse* t, long long first, long long count,
                       double* sums /* [count][nreplicas][Q][c_z][c_y][c_x] */,
                       long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
 
+/* ---- Lag traces: two-time correlations of chosen fields against time origins kept on the device, recorded as a time
+ * series and read once at the end.  Every other recorder reduces the fields of ONE instant.  The velocity autocorrelation
+ * sum_x u(x, t0 + lag) . u(x, t0) of an equilibrium run and its long-time tail, the density autocorrelations, the two-time
+ * function C(t, t_w) = sum_x phi(x, t) phi(x, t_w) of a quench and the persistence P(t, t_w), the fraction of sites whose
+ * side of a level has not changed since t_w, need TWO; the mode trace gives them at up to 64 wavevectors only, and through
+ * the host they cost a hydrovs download per sample.  A lag trace keeps per-site copies of earlier samples (origins) on the
+ * device and reads them back at every sample.  It is attached to one lone single-slab context or one replica batch.
+ *  - definition (stated here and nowhere else).  Inputs: a source (0: hydrovs, 22 components; 1: hydrovsbar, 9
+ *    components), nvars in 1..8 distinct component indices of that source, npairs in 1..8 pairs (a, b) of variable SLOTS
+ *    (positions in the variable list), a == b allowed, norigins R in 1..16, origin_stride E >= 1, persist_slot (-1 for
+ *    none, or a slot in 0..nvars-1) and a finite persist_level.
+ *    Origins: the samples are counted n = 0, 1, ... from creation or from the last reset.  At a sample with n % E == 0
+ *    the recorder first takes an origin into slot (n / E) % R: it copies the nvars observed variables of every site and
+ *    stores the owner's step counter (on a batch each replica's own counter); a used slot is overwritten.  The sample is
+ *    then recorded, so every origin appears at lag 0.  The lags covered are 0 to about R E samples.
+ *    Sample layout: per replica W = nvars + R (2 + npairs) 8-byte words: now[v], the sum over all sites of variable v at
+ *    this sample (double); then per slot r: origin_step[r] (int64, -1 while the slot is empty), alive[r] (int64, -1 if
+ *    persist_slot < 0 or the slot is empty) and corr[r][p] = sum_x v_a(x, now) * v_b(x, origin r) (double, NaN for an
+ *    empty slot), a the first and b the second slot of pair p.  The product is rounded once and then added, never
+ *    contracted (-ffp-contract=off), as the profile trace forms its products.  A NaN in a field propagates.
+ *    Persistence: s(v) = (v >= persist_level), an IEEE double comparison: a NaN gives false, a value equal to the level
+ *    is above.  Each site has one bit per slot.  A slot's bit is set at every site when its origin is taken; at every
+ *    sample, the origin's own sample included, the bit is ANDed with s(v now) == s(v at origin r), v the variable of
+ *    persist_slot; alive[r] is the number of set bits.  The bit is checked at samples only, so P depends on `every`: a
+ *    site that crosses the level and returns between two samples stays alive.
+ *    Order of the double sums: fixed by the box alone.  Per lattice plane z it is the profile trace's axis-z order (tiles
+ *    of 2048 consecutive dense sites; thread t of 256 adds the sites t, t + 256, ... in that order, a site past the plane
+ *    adding +0.0; then the tree v[t] += v[t + w], w = 128 .. 1; then the tiles are added in tile order from +0.0); after
+ *    that the planes are added in the sequence z = 0 .. nz-1, from +0.0.  So now[v] equals the sequential z sum of a
+ *    profile trace (axis z) record of the same state, bit for bit, and corr of a just-taken origin equals the same sum
+ *    of that trace's pair (a, b).  The integers are exact whatever the launch geometry.  A record does not depend on the
+ *    batch around a replica, on the capacity, on the schedule or on what else is attached.  analysis.lag_record restates
+ *    this in numpy, operation for operation; analysis.lag_slots is the slot schedule, analysis.lag_average the average
+ *    over origins by lag, analysis.lag_connected the connected part.
+ *  - bflbm_lag_geometry reports nvars, npairs, R, E, W, the sites of a tile (2048), the tiles of a plane and the bytes of
+ *    the origins ([replica][R][nvars][nsites] doubles) and of the masks ([replica][nsites] 16-bit words, 0 without
+ *    persistence).
+ *  - how a sample is taken, on the owner's stream and without a host synchronisation: the accumulators' observation,
+ *    exactly as the profile trace takes it (a lone context: into the scratch state buffer; a batch: one launch over all
+ *    replicas, only the chosen variables, into a buffer of the trace); at a sample that takes an origin one small launch
+ *    per 32 replicas that writes the slot's label; then ONE summing launch, compiled once per number of variables, grid
+ *    (tiles of a plane, planes, replicas), 256 threads: a thread loads the current values of its 8 turns once (16-byte
+ *    loads where the plane is aligned) and keeps them in registers, adds them into now, stores them into the slot that
+ *    takes an origin (whose products then use the registers), and loops over the live slots with the origin's values
+ *    streaming through: per slot and pair one per-thread sum, the tree, one partial per (plane, tile, slot, pair).  With
+ *    persistence it loads the site's 16-bit mask once, updates every live bit from the values in registers and stores it;
+ *    the set bits are counted by wave ballots, one LDS add per wave and slot, one 64-bit global integer add per non-zero
+ *    counter and workgroup.  Two small finishing launches: the tiles of a plane in order; then the planes in sequence,
+ *    the counters and the origin labels into the slot [sample][replica][W], and the counters back to zero.  No atomics
+ *    on doubles, no scratch, no grid barrier.  Expected memory traffic per site and sample, derived: 8 nvars (1 + L)
+ *    bytes read, L the live slots, 8 nvars written at an origin sample, 4 for the mask: 408 bytes with three velocity
+ *    components and 16 origins, against the 608 of a step.
+ *  - no ring: there is no bflbm_ring_lag_create.  It would be easy later (per-site data stays on its slab, and the
+ *    partials gather in plane order as the profile trace's do); it is not built.  Not built on purpose either: the noise
+ *    source, more than 16 origins, logarithmically spaced origins, per-site lagged products.
+ *  - what is touched on the owner: what the profile trace's observation touches.  The resident state, the step counters
+ *    and everything the owner computes are unchanged.
+ *  - sampling rule, capacity, step labels, order among the recorders of one owner: those of the other traces ("lag trace
+ *    full").  bflbm_lag_reset also empties the slots and restarts n.  An owner may carry any number of lag traces.
+ *  - refused at creation (non-zero return, a message naming the call, before any launch, nothing allocated, the owner's
+ *    recorder list untouched), in this order: null arguments (before any device is touched); a source outside 0..1,
+ *    nvars outside 1..8, npairs outside 1..8, a component index outside its source, a repeated variable, a pair slot
+ *    outside 0..nvars-1; R outside 1..16, E < 1, persist_slot outside -1..nvars-1, a non-finite level when a slot is
+ *    given; every < 1, capacity < 1, a capacity beyond 1 TB of records; a replica view (use bflbm_batch_lag_create), a
+ *    context with nranks > 1; an open step; more than 65535 planes; a failed allocation (the message gives the bytes of
+ *    the origins, the masks, the stage buffer and the records).  An open step also refuses bflbm_lag_sample, _reset and
+ *    _read.
+ *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_lag_read, _count,
+ *    _geometry and _destroy still work, bflbm_lag_sample fails.  bflbm_lag_destroy(NULL) returns 0.
+ *  - only bflbm_lag_read and bflbm_lag_destroy synchronise the owner's stream. */
+typedef struct bflbm_lag bflbm_lag;
+int bflbm_lag_create(bflbm_ctx* c, int source, int nvars, const int* vars, int npairs, const int* pair_a, const int* pair_b,
+                     int norigins, int origin_stride, int persist_slot /* or -1 */, double persist_level, int every,
+                     long long capacity, bflbm_lag** out);
+int bflbm_batch_lag_create(bflbm_batch* b, int source, int nvars, const int* vars, int npairs, const int* pair_a, const int* pair_b,
+                           int norigins, int origin_stride, int persist_slot, double persist_level, int every,
+                           long long capacity, bflbm_lag** out);
+int bflbm_lag_destroy(bflbm_lag* t);
+int bflbm_lag_sample(bflbm_lag* t);                        /* record the resident state now (e.g. frame 0) */
+int bflbm_lag_reset(bflbm_lag* t);                         /* forget the samples and the origins, restart both counters */
+int bflbm_lag_count(const bflbm_lag* t, long long* nsamples, int* nreplicas);
+int bflbm_lag_geometry(const bflbm_lag* t, int* nvars, int* npairs, int* norigins, int* origin_stride, int* words /* W */,
+                       int* tile_sites, int* tiles_per_plane, long long* origin_bytes, long long* mask_bytes);
+int bflbm_lag_read(bflbm_lag* t, long long first, long long count,
+                   double* words /* [count][nreplicas][W] 8-byte words, copied bit for bit: doubles and int64 */,
+                   long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
+
 /* ---- Cluster traces: the connected components of a thresholded field, labelled on the device by a union-find over the
  * lattice and recorded as a time series of 64-bit integers, read once at the end.  The morphology trace answers "how many
  * domains" only through chi, which is the count only while no domain has a tunnel or a cavity, and never gives a size.
