@@ -6,7 +6,7 @@ The product path needs the HIP library csrc/libbflbm.so; there is no CPU fallbac
 """
 from . import _lib
 from ._lib import BflbmError, Params, Domain, Fab, NVEL, NHYDRO, NHYDROBAR, HALO_STATE, HALO_NEXT, HALO_UPLOAD
-from .lattice import BinaryLBM, RingLBM, BatchLBM, Trace, InterfaceTrace, ShapeTrace, SpectrumTrace, ModeTrace, FieldStats, ProfileTrace, HistogramTrace, MorphologyTrace, ChordTrace, CoarseTrace, LagTrace, ClusterTrace, ComponentTrace, RadialTrace, default_params, make_fab, rng_site_normals, fused_plan_query, sweep_plan_query
+from .lattice import BinaryLBM, RingLBM, BatchLBM, Trace, InterfaceTrace, ShapeTrace, SpectrumTrace, ModeTrace, FieldStats, ProfileTrace, HistogramTrace, MorphologyTrace, ChordTrace, CoarseTrace, LagTrace, MomentTrace, ClusterTrace, ComponentTrace, RadialTrace, default_params, make_fab, rng_site_normals, fused_plan_query, sweep_plan_query
 from .slab import SlabLattice, LocalSlabRing, slab_bounds
 from . import plotfile
 from . import analysis
@@ -14,5 +14,5 @@ from . import structfact
 from .structfact import BatchStructFact
 from . import run_job
 
-__all__ = ["RingLBM", "BatchLBM", "Trace", "InterfaceTrace", "ShapeTrace", "SpectrumTrace", "ModeTrace", "FieldStats", "ProfileTrace", "HistogramTrace", "MorphologyTrace", "ChordTrace", "CoarseTrace", "LagTrace", "ClusterTrace", "ComponentTrace", "RadialTrace", "BatchStructFact", "SlabLattice", "LocalSlabRing", "slab_bounds", "BinaryLBM", "default_params", "make_fab", "rng_site_normals", "fused_plan_query", "sweep_plan_query", "BflbmError",
+__all__ = ["RingLBM", "BatchLBM", "Trace", "InterfaceTrace", "ShapeTrace", "SpectrumTrace", "ModeTrace", "FieldStats", "ProfileTrace", "HistogramTrace", "MorphologyTrace", "ChordTrace", "CoarseTrace", "LagTrace", "MomentTrace", "ClusterTrace", "ComponentTrace", "RadialTrace", "BatchStructFact", "SlabLattice", "LocalSlabRing", "slab_bounds", "BinaryLBM", "default_params", "make_fab", "rng_site_normals", "fused_plan_query", "sweep_plan_query", "BflbmError",
            "Params", "Domain", "Fab", "NVEL", "NHYDRO", "NHYDROBAR"]

@@ -221,6 +221,14 @@ SIGNATURES = {
     "bflbm_lag_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
     "bflbm_lag_geometry": (ctypes.c_int, [_vp] + [_P(ctypes.c_int)] * 7 + [_P(ctypes.c_longlong)] * 2),
     "bflbm_lag_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _P(ctypes.c_longlong)]),
+    "bflbm_moment_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_batch_moment_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
+    "bflbm_moment_destroy": (ctypes.c_int, [_vp]),
+    "bflbm_moment_sample": (ctypes.c_int, [_vp]),
+    "bflbm_moment_reset": (ctypes.c_int, [_vp]),
+    "bflbm_moment_count": (ctypes.c_int, [_vp, _P(ctypes.c_longlong), _P(ctypes.c_int)]),
+    "bflbm_moment_geometry": (ctypes.c_int, [_vp] + [_P(ctypes.c_int)] * 3),
+    "bflbm_moment_read": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _P(ctypes.c_longlong)]),
     "bflbm_cluster_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
     "bflbm_batch_cluster_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _P(_vp)]),
     "bflbm_cluster_destroy": (ctypes.c_int, [_vp]),

@@ -885,6 +885,132 @@ def lag_connected(steps, origin_steps, corr, now_a, now_b, nsites):
     return out
 
 
+# ---- moment records: the numpy restatement of the moment trace (include/bflbm.h, "Moment traces") ----
+MOMENT_MODES, MOMENT_WORDS = 19, 95
+# b[a]: the norms of the basis vectors of the moment transform (LBM_d3q19.H:56-76), the weight of mode a in equipartition
+MOMENT_NORMS = (1.0, 1. / 3., 1. / 3., 1. / 3., 2. / 3., 4. / 3., 4. / 9., 1. / 9., 1. / 9., 1. / 9.,
+                2. / 3., 2. / 3., 2. / 3., 2. / 9., 2. / 9., 2. / 9., 2.0, 4. / 3., 4. / 9.)
+_MOMENT_NAMES = ("rho", "jx", "jy", "jz",                               # density and momentum
+                 "s_tr", "s_xx", "s_ww", "s_xy", "s_yz", "s_xz",        # stress: trace, 3 xx - cc, yy - zz, the three shears
+                 "g_jx", "g_jy", "g_jz", "g_hx", "g_hy", "g_hz",        # ghost vectors: (3 cc - 5) c, and the plane differences
+                 "g_tr", "g_xx", "g_ww")                                # ghost scalars: the fourth-order partners of s_tr, s_xx, s_ww
+
+
+def moment_names():
+    """The 19 modes of one fluid in the order of the transform (LBM_d3q19.H:100-156): rho, jx, jy, jz; the six stress
+    moments s_tr (c.c - 1 summed: the bulk mode), s_xx (3 cx^2 - c.c), s_ww (cy^2 - cz^2), s_xy, s_yz, s_xz; the ghost
+    moments g_jx..g_jz ((3 c.c - 5) c), g_hx..g_hz (the differences between the planes' momenta) and g_tr, g_xx, g_ww."""
+    return list(_MOMENT_NAMES)
+
+
+def _quad(q0, q1, q2, q3):
+    """The four signed sums of a coordinate plane's diagonal populations, accumulated left to right (csrc/bflbm_site.h, d_quad)."""
+    u = q0 - q1 + q2 - q3
+    v = q0 - q1 - q2 + q3
+    w = q0 + q1 - q2 - q3
+    t = q0 + q1 + q2 + q3
+    return u, v, w, t
+
+
+def moments_of(f):
+    """m[19, ...] = moments(f[19, ...]) with the association of csrc/bflbm_site.h's d_moments, which is the reference's
+    (LBM_d3q19.H:100-156): the doubles equal the oracle's orc_moments."""
+    f = np.asarray(f, dtype=np.float64)
+    if f.ndim < 1 or f.shape[0] != MOMENT_MODES:
+        raise ValueError(f"moments_of: populations[19, ...], got shape {f.shape}")
+    dif = [f[1 + 2 * a] - f[2 + 2 * a] for a in range(3)]
+    tot = [f[1 + 2 * a] + f[2 + 2 * a] for a in range(3)]
+    xy_u, xy_v, xy_w, xy_t = _quad(f[7], f[8], f[9], f[10])             # u: x-momentum, v: y-momentum
+    yz_u, yz_v, yz_w, yz_t = _quad(f[11], f[12], f[13], f[14])          # u: y-momentum, v: z-momentum
+    xz_u, xz_v, xz_w, xz_t = _quad(f[15], f[16], f[17], f[18])          # u: x-momentum, v: z-momentum
+    rest = f[0]
+    shell1 = tot[0] + tot[1] + tot[2]
+    shell2 = xy_t + yz_t + xz_t
+    m = np.empty_like(f)
+    m[0] = rest + shell1 + shell2
+    m[1] = dif[0] + xy_u + xz_u
+    m[2] = dif[1] + yz_u + xy_v
+    m[3] = dif[2] + xz_v + yz_v
+    m[4] = shell2 - rest
+    m[5] = 3. * tot[0] - shell1 + shell2 - 3. * yz_t
+    m[6] = tot[1] - tot[2] + xy_t - xz_t
+    m[7] = xy_w
+    m[8] = yz_w
+    m[9] = xz_w
+    m[10] = m[1] - 3. * dif[0]
+    m[11] = m[2] - 3. * dif[1]
+    m[12] = m[3] - 3. * dif[2]
+    m[13] = xy_u - xz_u
+    m[14] = yz_u - xy_v
+    m[15] = xz_v - yz_v
+    m[16] = m[0] - 3. * shell1
+    m[17] = shell1 - 3. * tot[0] + shell2 - 3. * yz_t
+    m[18] = tot[2] - tot[1] + xy_t - xz_t
+    return m
+
+
+def moment_terms(f, g):
+    """terms[95, nz, ny, nx]: what every site adds to the 95 words of a sample: the 38 moments (19 fluid + a), their
+    squares and the 19 products mf_a mg_a, each product rounded once."""
+    f, g = np.asarray(f, dtype=np.float64), np.asarray(g, dtype=np.float64)
+    if f.ndim != 4 or f.shape[0] != MOMENT_MODES or g.shape != f.shape:
+        raise ValueError(f"moment_record: f[19, nz, ny, nx] and g of the same shape, got {f.shape} and {g.shape}")
+    mf, mg = moments_of(f), moments_of(g)
+    return np.concatenate([mf, mg, mf * mf, mg * mg, mf * mg], axis=0)
+
+
+def moment_record(f, g):
+    """sums[95] of include/bflbm.h, "Moment traces", in numpy, operation for operation and in the header's order: f, g the
+    populations [19, nz, ny, nx] that populations() returns.  Every sum is plane_profiles(..., axis=2) of its term summed
+    over z in sequence: the lag trace's order for `now`.  Taken plane by plane, so a large box needs the terms of one plane."""
+    f, g = np.asarray(f, dtype=np.float64), np.asarray(g, dtype=np.float64)
+    if f.ndim != 4 or f.shape[0] != MOMENT_MODES or g.shape != f.shape:
+        raise ValueError(f"moment_record: f[19, nz, ny, nx] and g of the same shape, got {f.shape} and {g.shape}")
+    out = np.zeros(MOMENT_WORDS)
+    for z in range(f.shape[1]):                            # the planes in sequence, from +0.0
+        out = out + plane_profiles(moment_terms(f[:, z:z + 1], g[:, z:z + 1]), (), axis=2)[:, 0]
+    return out
+
+
+def _moment_blocks(sums, who):
+    s = np.asarray(sums, dtype=np.float64)
+    if s.ndim < 1 or s.shape[-1] != MOMENT_WORDS:
+        raise ValueError(f"{who}: sums[..., 95], got shape {s.shape}")
+    n = MOMENT_MODES
+    return s[..., :n], s[..., n:2 * n], s[..., 2 * n:3 * n], s[..., 3 * n:4 * n], s[..., 4 * n:]
+
+
+def moment_variances(sums, nsites):
+    """(var_f, var_g, var_total)[..., 19] of records sums[..., 95] over boxes of nsites sites: per mode the spatial variance
+    sq / n - (sum / n)^2, and the same of the total fluid's moment mf + mg, whose square sum is sq_f + 2 cross + sq_g."""
+    sf, sg, qf, qg, x = _moment_blocks(sums, "moment_variances")
+    n = float(int(nsites))
+    if n < 1:
+        raise ValueError(f"moment_variances: nsites >= 1, got {nsites!r}")
+    var = lambda s, q: q / n - (s / n) * (s / n)
+    return var(sf, qf), var(sg, qg), var(sf + sg, qf + 2. * x + qg)
+
+
+def equipartition(sums, nsites):
+    """(e_f, e_g, e_total)[..., 19]: every mode's variance (moment_variances) over its weight b[a] (MOMENT_NORMS), relative
+    to the mean of that ratio over the three momentum modes.  For a thermalised uniform mixture every entry of the
+    non-conserved modes is about the same number (1 where the modes share one temperature); rho is conserved at every
+    site by the collision and need not be."""
+    b = np.array(MOMENT_NORMS)
+    out = []
+    for v in moment_variances(sums, nsites):
+        r = v / b
+        out.append(r / r[..., 1:4].mean(axis=-1, keepdims=True))
+    return tuple(out)
+
+
+def stress_series(sums):
+    """The box sums of the total fluid's stress moments 4..9, sum_f + sum_g: [..., 6] in the order s_tr, s_xx, s_ww, s_xy,
+    s_yz, s_xz.  The off-diagonal ones are the input of a Green-Kubo integral (time_correlation gives the correlation)."""
+    sf, sg = _moment_blocks(sums, "stress_series")[:2]
+    return sf[..., 4:10] + sg[..., 4:10]
+
+
 # ---- clusters: the numpy restatement of the cluster trace (include/bflbm.h, "Cluster traces") ----
 CLUSTER_WORDS = 38
 CLUSTER_CONNECTIVITIES = (6, 26)

@@ -1780,6 +1780,7 @@ int bflbm_sweep_plan_query(const int n[3], int schedule, int noise, int slab_pla
 #include "bflbm_chord.h"
 #include "bflbm_coarse.h"
 #include "bflbm_lag.h"
+#include "bflbm_moment.h"
 #include "bflbm_cluster.h"
 #include "bflbm_components.h"
 #include "bflbm_radial.h"

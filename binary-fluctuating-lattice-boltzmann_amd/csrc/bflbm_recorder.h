@@ -2,7 +2,7 @@
 // (bflbm_trace.h), interface traces (bflbm_iface.h), shape traces (bflbm_shape.h), structure factors (bflbm_sf.h,
 // bflbm_sf_ring.h, bflbm_batch_sf.h), spectrum traces (bflbm_spectrum.h, bflbm_spectrum_ring.h), mode traces (bflbm_modes.h), field
 // statistics (bflbm_fstat.h), profile traces (bflbm_profile.h), histogram traces (bflbm_hist.h), morphology traces
-// (bflbm_morph.h), chord traces (bflbm_chord.h), coarse traces (bflbm_coarse.h), lag traces (bflbm_lag.h), cluster traces (bflbm_cluster.h), component traces (bflbm_components.h) and radial traces (bflbm_radial.h).  A recorder is attached to a lone context, a batch or a ring of more than one slab, is served after
+// (bflbm_morph.h), chord traces (bflbm_chord.h), coarse traces (bflbm_coarse.h), lag traces (bflbm_lag.h), moment traces (bflbm_moment.h), cluster traces (bflbm_cluster.h), component traces (bflbm_components.h) and radial traces (bflbm_radial.h).  A recorder is attached to a lone context, a batch or a ring of more than one slab, is served after
 // every step on the owner's stream(s) in creation order, survives its owner detached (readable, no longer fed) and is
 // destroyed by its own call ("Recorders").  A ring serves its recorders from bflbm_ring_step only, after the
 // bflbm_step_finish of every slab; its samples carry slab 0's step counter and its records live on slab 0's device,

@@ -937,6 +937,62 @@ class LagTrace(_FieldRecorder):
         return analysis.lag_average(steps[:, k], osteps[:, k], values)
 
 
+MOMENT_MODES, MOMENT_WORDS = 19, 95
+
+
+class MomentTrace(_Recorder):
+    """The box sums of all 19 kinetic moments m = M f of both fluids, of their squares and of the products of the two
+    fluids' moments mode by mode, for every replica, recorded on the device every `every` steps through the owner (a lone
+    single-slab BinaryLBM or a BatchLBM; no rings) and read once: include/bflbm.h, "Moment traces";
+    analysis.moment_record is the same arithmetic in numpy, analysis.moment_variances, analysis.equipartition and
+    analysis.stress_series turn a record into the variance per mode, the equipartition ratios and the Green-Kubo input.
+    Made by owner.moment_trace(); an owner may carry several.  Closing the owner detaches the trace: it stays readable
+    until its own close()."""
+    _abi = "bflbm_moment"
+    _geometry_types = (ctypes.c_int,) * 3
+
+    def __init__(self, owner, create, every, capacity):
+        super().__init__(owner, create, int(every), int(capacity))
+        self.sites = owner.n[0] * owner.n[1] * owner.n[2]
+
+    def _owner_closing(self):
+        """The owner's close(): the library detaches the trace; what it recorded stays readable until close()."""
+        _unregister(self.owner, self)
+
+    def geometry(self):
+        """(words W of a replica's sample, sites of a tile, tiles of a plane): what the library built."""
+        return self._geometry()
+
+    def read(self, first=0, count=None):
+        """(steps[count, B] int64, sums[count, B, 95]) of the samples first ... first + count - 1 (count None: all from
+        `first`); synchronises the owner's stream."""
+        first, count, b, steps = self._window(first, count)
+        sums = np.empty((max(count, 0), b, MOMENT_WORDS))
+        check(self.lib.bflbm_moment_read(self._h, first, count, _ptr(sums), steps.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        return steps, sums
+
+    @staticmethod
+    def _fluid(fluid):
+        k = {"f": 0, "g": 1}.get(fluid, fluid)
+        if k not in (0, 1):
+            raise ValueError(f"moment_trace: fluid {fluid!r}, expected 0 / 'f' or 1 / 'g'")
+        return int(k)
+
+    def sums(self, fluid, first=0, count=None):
+        """sum_x m_a(x) of one fluid (0 / "f" or 1 / "g"): [count, B, 19]."""
+        k = self._fluid(fluid)
+        return self.read(first, count)[1][..., MOMENT_MODES * k:MOMENT_MODES * (k + 1)]
+
+    def squares(self, fluid, first=0, count=None):
+        """sum_x m_a(x)^2 of one fluid: [count, B, 19]."""
+        k = self._fluid(fluid)
+        return self.read(first, count)[1][..., MOMENT_MODES * (2 + k):MOMENT_MODES * (3 + k)]
+
+    def cross(self, first=0, count=None):
+        """sum_x mf_a(x) mg_a(x): [count, B, 19]."""
+        return self.read(first, count)[1][..., 4 * MOMENT_MODES:]
+
+
 class ClusterTrace(_FieldRecorder):
     """The connected components of the set {v >= level} (side "above") or {v < level} (side "below") of one hydrovs /
     hydrovsbar variable at 1 to 8 levels under 6- or 26-connectivity on the periodic box, for every replica, labelled on
@@ -1447,6 +1503,13 @@ class BinaryLBM(_DropletMixin):
         give the record."""
         return LagTrace(self, "bflbm_lag_create", variables, pairs, origins, origin_stride, persist, source, every, capacity)
 
+    def moment_trace(self, every=1, capacity=64):
+        """Record, after every `every`-th step, the box sums of all 19 kinetic moments of both fluids, of their squares
+        and of the products mf_a mg_a of the two fluids' moments, 95 doubles a sample, with one summing launch that reads
+        the populations once and one finishing launch: MomentTrace, whose read(), sums(fluid), squares(fluid) and cross()
+        give the record."""
+        return MomentTrace(self, "bflbm_moment_create", every, capacity)
+
     def cluster_trace(self, variable, levels, side="above", connectivity=26, source="hydrovs", every=1, capacity=64):
         """Record, after every `every`-th step, the connected components of the set {variable >= level} (side "above") or
         {variable < level} (side "below") at 1 to 8 levels under 6- or 26-connectivity, one variable of `source`
@@ -1895,6 +1958,12 @@ class BatchLBM:
         `every`-th batch step, with one observation launch and one summing launch over all replicas per sample; an
         origin carries each replica's own step counter: LagTrace."""
         return LagTrace(self, "bflbm_batch_lag_create", variables, pairs, origins, origin_stride, persist, source, every, capacity)
+
+    def moment_trace(self, every=1, capacity=64):
+        """Every replica's box sums of the 19 kinetic moments of both fluids, their squares and cross products
+        (BinaryLBM.moment_trace) after every `every`-th batch step, with one summing launch over all replicas and one
+        finishing launch per sample: MomentTrace."""
+        return MomentTrace(self, "bflbm_batch_moment_create", every, capacity)
 
     def cluster_trace(self, variable, levels, side="above", connectivity=26, source="hydrovs", every=1, capacity=64):
         """Every replica's connected components of a thresholded variable (BinaryLBM.cluster_trace) after every `every`-th

@@ -1240,6 +1240,66 @@ int bflbm_lag_read(bflbm_lag* t, long long first, long long count,
                    double* words /* [count][nreplicas][W] 8-byte words, copied bit for bit: doubles and int64 */,
                    long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
 
+/* ---- Moment traces: the box sums of all 19 kinetic moments of both fluids, of their squares and of the products of the two
+ * fluids' moments mode by mode, recorded as a time series and read once at the end.  The thermal noise is applied per mode,
+ * to all 19 moments of each fluid (LBM_binary.H:73-132); every other recorder reads hydrovs, hydrovsbar or the injected
+ * noise moments, and of the moments m = M f of the resident state only density and momentum ever leave the step.  Whether
+ * all modes are thermalised (equipartition per mode), the box sum of the off-diagonal stress that a Green-Kubo integral
+ * needs at every step, and whether the two fluids' kinetic modes fluctuate together or against each other otherwise cost
+ * a download of 38 populations per site and sample.  A moment trace is attached to one lone single-slab context or one
+ * replica batch.
+ *  - definition (stated here and nowhere else).  No inputs besides the cadence: there are no variable lists and no pair
+ *    lists.  At every site mf = moments(f) and mg = moments(g), f and g the populations that bflbm_download_fg returns (the
+ *    reference's fold / gold) and moments the transform of LBM_d3q19.H:100-156 with the association of its expressions, so
+ *    the doubles are those the step's own collision forms.  Global moment index i = 19 fluid + a, fluid 0 (f) or 1 (g),
+ *    a = 0..18: the numbering of the noise source (fa0..fa18, ga0..ga18).
+ *    Sample layout: per replica W = 95 doubles: sum[i] (words 0..37) = sum over all sites x of m_i(x); sq[i] (words
+ *    38..75) = sum_x m_i(x) * m_i(x); cross[a] (words 76..94) = sum_x mf_a(x) * mg_a(x), a = 0..18.  Every product is
+ *    rounded once and then added, never contracted (-ffp-contract=off), as the profile trace forms its products.  A NaN
+ *    stays in its sum: it shows in exactly the words its moments enter.
+ *    Order of every sum: the lag trace's order for `now` ("Lag traces", Order of the double sums), with m_i, m_i * m_i or
+ *    mf_a * mg_a in the place of the variable.  So the record depends on the box alone: it is reproducible bit for bit,
+ *    independent of the schedule in force, of the batch around a replica, of the capacity and of what else is attached.
+ *    analysis.moment_record restates this in numpy, operation for operation;
+ *    analysis.moment_names names the modes, analysis.moment_variances, analysis.equipartition and analysis.stress_series
+ *    cut a record up.
+ *  - bflbm_moment_geometry reports W (95), the sites of a tile (2048) and the tiles of a plane.
+ *  - how a sample is taken, on the owner's stream and without a host synchronisation: ONE summing launch, grid (tiles of
+ *    a plane, planes, replicas), 256 threads, which takes a lone context by its resident buffer and a batch by the
+ *    replicas' records: per site the pull of the 38 populations, the transform twice, 95 accumulators in registers, every
+ *    one with a compile-time index; the tree 12 accumulators at a time through two LDS buffers in turn (49152 bytes of
+ *    static LDS); one partial per (word, tile): [replica][z][95][tiles].  One finishing launch, grid (95, replicas): the
+ *    tiles of every plane in tile order, then the planes in sequence, straight into the slot [sample][replica][95].
+ *    No atomics, no scratch, no
+ *    grid barrier.  Expected memory traffic per site and sample, derived: 304 bytes read against the 608 of a step,
+ *    nothing written but 95 x tiles partials per plane.
+ *  - no ring: there is no bflbm_ring_moment_create.  It would be easy later (the summing launch takes a slab as it takes a
+ *    lone context, and the partials gather in plane order as the profile trace's do); it is not built.
+ *  - not built on purpose: a source in the field selection, per-site output, density-normalised or windowed sums, the
+ *    deviation from the local equilibrium, arbitrary pairs of modes, a Green-Kubo integral.
+ *  - what is touched on the owner: nothing.  The resident state is read; the scratch state buffer, the densities, the
+ *    step counters and the noise index are neither written nor moved.
+ *  - sampling rule, capacity, step labels, order among the recorders of one owner: those of the other traces ("moment
+ *    trace full").  An owner may carry any number of moment traces.
+ *  - refused at creation (non-zero return, a message naming the call, before any launch, nothing allocated, the owner's
+ *    recorder list untouched), in this order: null arguments (before any device is touched); every < 1, capacity < 1, a
+ *    capacity beyond 1 TB of records; a replica view (use bflbm_batch_moment_create), a context with nranks > 1; an open step; more than 65535 planes, a plane beyond a 32-bit site index,
+ *    more than 65535 replicas; a failed allocation.  An open step also refuses bflbm_moment_sample, _reset and _read.
+ *  - lifetime: the trace owns its buffers.  Destroying the owner first detaches the trace: bflbm_moment_read, _count,
+ *    _geometry and _destroy still work, bflbm_moment_sample fails.  bflbm_moment_destroy(NULL) returns 0.
+ *  - only bflbm_moment_read and bflbm_moment_destroy synchronise the owner's stream. */
+typedef struct bflbm_moment bflbm_moment;
+int bflbm_moment_create(bflbm_ctx* c, int every, long long capacity, bflbm_moment** out);
+int bflbm_batch_moment_create(bflbm_batch* b, int every, long long capacity, bflbm_moment** out);
+int bflbm_moment_destroy(bflbm_moment* t);
+int bflbm_moment_sample(bflbm_moment* t);                  /* record the resident state now (e.g. frame 0) */
+int bflbm_moment_reset(bflbm_moment* t);                   /* forget the samples and restart the every-counter */
+int bflbm_moment_count(const bflbm_moment* t, long long* nsamples, int* nreplicas);
+int bflbm_moment_geometry(const bflbm_moment* t, int* words /* W = 95 */, int* tile_sites, int* tiles_per_plane);
+int bflbm_moment_read(bflbm_moment* t, long long first, long long count,
+                      double* sums /* [count][nreplicas][95] */,
+                      long long* steps /* [count][nreplicas], nullable: each replica's step counter at the sample */);
+
 /* ---- Cluster traces: the connected components of a thresholded field, labelled on the device by a union-find over the
  * lattice and recorded as a time series of 64-bit integers, read once at the end.  The morphology trace answers "how many
  * domains" only through chi, which is the count only while no domain has a tunnel or a cavity, and never gives a size.
